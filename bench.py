@@ -15,6 +15,12 @@ finish (render + accumulate + gather), timed synchronously after the timed loop.
     python bench.py [--gpus N --steps K --warmup W]     (N > 1: starts N ranks itself)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step,
+the configuration). --dump-outputs DIR also writes the last timed step's frame to DIR/frame.npy.
+Everything below takes frames or processes of its own and runs only with --full: the lone-frame
+latency and wall clock, the counting frame and the roofline, parity, the corrected-camera frames,
+the drop-in call's times and the CPU baseline.
+
 parity: rank 0 hashes the last timed frame and compares it with the reference's own whole-frame
 digest (tests/golden/fullframe.json, made from the reference's CPU path by
 tests/golden/make_fullframe.py): "matches_reference" is true only if every bit agrees.
@@ -75,8 +81,16 @@ def parse():
     ap.add_argument("--traversal", default="cull", choices=["cull", "brute"],
                     help="cull: exact cluster culling (same bits); brute: every sphere, as the reference")
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip dropin_first_ms / dropin_repeat_ms")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else the line can carry: "
+                         "lone-frame latency and wall clock, the counting frame and roofline, parity with the "
+                         "reference's digest, corrected-camera frames, the drop-in call, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step (rank 0's output) to DIR/frame.npy as float32; "
+                         "a frame over 64 MB as a fixed, seeded sample of its rows (indices in DIR/frame_rows.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-dropin", action="store_true",
+                    help="with --full: skip dropin_first_ms / dropin_repeat_ms")
     ap.add_argument("--cpu-rows", type=int, default=240, help="rows in the CPU-baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every core this job may use (cpu_info)")
     ap.add_argument("--rehearse-world", type=int, default=0,
@@ -98,8 +112,8 @@ def parse():
                     help="kept for old scripts: every line now carries parity.frame_sha256 (the last timed frame's "
                          "sha256 on rank 0) and its comparison with the reference's digest")
     ap.add_argument("--corrected-steps", type=int, default=5,
-                    help="frames of the same workload with the corrected camera, reported as corrected_camera "
-                         "(0: skip)")
+                    help="with --full: frames of the same workload with the corrected camera, reported as "
+                         "corrected_camera (0: skip)")
     ap.add_argument("--rehearse-gather", action="store_true",
                     help="with --rehearse-world N: stand in for rank 0's gather with its device work on the "
                          "caller stream (the N-1 peer tiles copied into the gather buffer, then the "
@@ -182,6 +196,24 @@ def parity_record(frame_np, config, W, H, row_offset, row_stride, seed, camera, 
         rec["note"] = "fast variant: within the stated tolerance, not bitwise by design"
     rec["reference"] = "tests/golden/fullframe.json[%s] (oracle/_ref/ref_harness_pcg, the reference's CPU path)" % config
     return rec
+
+
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(dirname, frame_np):
+    """--dump-outputs: the last timed step's frame as rank 0's caller receives it (rows x W x 3),
+    DIR/frame.npy in float32 (u8 output converted, values kept). A frame over the limit is cut to
+    a fixed, seeded sample of its rows, ascending, whose indices go to DIR/frame_rows.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = np.ascontiguousarray(frame_np, dtype=np.float32)
+    if a.nbytes + 4096 > DUMP_LIMIT:
+        keep = (DUMP_LIMIT - 8192) // (a[0].nbytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+        np.save(os.path.join(dirname, "frame_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(dirname, "frame.npy"), a)
 
 
 def lib_sha256():
@@ -527,20 +559,22 @@ def main():
 
     # the reference's entry returns the frame in host memory (cuda_impl.cu:449-452): the frame
     # wall clock ends with the device->host copy into a pinned buffer
-    host_frame = torch.empty(out_frame().shape, dtype=out_frame().dtype, pin_memory=True) if rank == 0 else None
+    host_frame = torch.empty(out_frame().shape, dtype=out_frame().dtype, pin_memory=True) \
+        if rank == 0 and args.full else None
     parity = {}
     # frames of the timed kernels this process renders (scripts/pmc_json.py divides its counters
     # by it: a frame is one pass alone, or several ring passes beside other frames)
     issued = [0]
 
-    def measure(cam, steps, warmup, check_parity=False):
+    def measure(cam, steps, warmup, check_parity=False, dump=None):
         """warmup untimed frames, then `steps` frames timed between barriers + syncs (max over
-        ranks), then one frame alone three times on the device (its latency, median) and three
+        ranks); a plain run ends there (latency, spans and counts None). With --full: then one
+        frame alone three times on the device (its latency, median) and three
         times including the copy of the frame to host memory (the frame wall clock), then one
         frame of the counting kernel (the same paths and bits, plus tallies of segments and
         executed tests: the work of every frame of this workload, which the timed frames do not
         tally). check_parity: rank 0 compares the last timed frame with the reference's digests
-        (outside the timed region)."""
+        (outside the timed region). dump: rank 0 writes that frame there (dump_outputs)."""
         def step(count_segments):
             ds.render(cam, params, tile.data_ptr(), stream.cuda_stream, seg.data_ptr() if count_segments else None)
             issued[0] += 0 if count_segments else 1
@@ -568,10 +602,19 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
-        spans = ds.kernel_times(steps)  # HIP-event spans of the timed frames' render launches
-        if check_parity and rank == 0:
+        if (check_parity or dump) and rank == 0:
             # a rehearsal checks its own rows (the stood-in gather buffer holds copies of them)
             frame = (tile8 if rgb8 else tile).cpu().numpy() if rehearse else out_frame().cpu().numpy()
+            if dump:
+                dump_outputs(dump, frame)
+        if not args.full:
+            if distributed:
+                t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                elapsed = float(t[0].item())
+            return elapsed, None, None, None, None
+        spans = ds.kernel_times(steps)  # HIP-event spans of the timed frames' render launches
+        if check_parity and rank == 0:
             off, stride = (0, 1) if not rehearse else (params.row_offset, params.row_stride)
             parity.update(parity_record(frame, args.config, W, H, off, stride, args.seed, args.camera,
                                         args.variant, args.output))
@@ -604,10 +647,12 @@ def main():
         return elapsed, (latency, wall_clock), spans, counts, counts_all
 
     def summary(elapsed, lat_wall, spans, counts, counts_all, steps):
-        latency, wall_clock = lat_wall
-        segments, sph_tests, box_tests = counts
         primaries = (W * rows if rehearse else W * H) * spp * steps
         period = elapsed / steps
+        if counts is None:  # a plain run: the timed steps alone
+            return {"value": primaries / elapsed / 1e6, "ms_per_step": period * 1e3}
+        latency, wall_clock = lat_wall
+        segments, sph_tests, box_tests = counts
         # executed work per frame on this rank: every ray-sphere test (20 FLOP)
         # and every cluster-box slab test (19 FLOP) the kernel ran
         flop_frame = (sph_tests * FLOP_PER_TEST + box_tests * FLOP_PER_BOX) / steps
@@ -628,41 +673,21 @@ def main():
 
     mode = rt.CORRECTED if args.camera == "corrected" else rt.REFERENCE
     cam = rt.Camera.cuda(W, H) if compat else rt.Camera.default(W, H, mode)
-    main_m = summary(*measure(cam, args.steps, args.warmup, check_parity=not compat), args.steps)
+    main_m = summary(*measure(cam, args.steps, args.warmup, check_parity=args.full and not compat,
+                              dump=args.dump_outputs), args.steps)
     usage = ds.usage()  # the cut of the timed frames (before the corrected-camera frames)
     corr = None
-    if args.corrected_steps > 0 and not compat and args.camera == "reference":
+    if args.full and args.corrected_steps > 0 and not compat and args.camera == "reference":
         # the representative path-tracing load (7 segments per primary): the corrected camera
         # (direction - origin) on the same workload, a few frames after the headline ones
         corr = summary(*measure(rt.Camera.default(W, H, rt.CORRECTED), args.corrected_steps, 1),
                        args.corrected_steps)
-    if rank == 0:
-        r3 = lambda x: round(x, 3) if x is not None else None  # noqa: E731
-        rec = {
-            "metric": "Mrays/sec + frame wall-clock, huge-scene 1280x720x128spp @1/2/4/8 GPU",
-            "value": round(main_m["value"], 3),
-            "unit": "Mrays/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": r3(main_m["ms_per_step"]),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (reference huge scene, std::mt19937 seed 1234; per-sample PCG32 seed %d)" % args.seed,
-            "config": {"workload": WORKLOAD[args.config], "scene": f"{scene_name} ({n_spheres} spheres)",
-                       "width": W, "height": H, "spp": spp, "max_depth": depth, "camera": args.camera,
-                       "kernel": "compat_kernel (cuda_impl.cu semantics, bit-exact vs its restatement)" if compat else
-                       ("fast (FMA, stated tolerance)" if args.variant == "fast" else f"{args.variant} (bit-exact)")
-                       + f", {args.traversal}", "parallelism": f"row-interleaved x{world}, RCCL gather of "
-                       + ("u8 (gamma epilogue per rank)" if rgb8 else "f32") + " tiles",
-                       "output": args.output, "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
-                       "hw_queues_env": hw_env,
-                       # the scene's rt_options (library defaults, RT_OPTIONS, --options): deep-path
-                       # split (DESIGN §4.1) and the lone-pass size below which passes are not split
-                       "deep_split": opts.deep_split, "deep_min_items": opts.deep_min_items,
-                       "options": {k: getattr(opts, k) for k, _ in rt.abi.RtOptions._fields_ if k != "size"}},
+    r3 = lambda x: round(x, 3) if x is not None else None  # noqa: E731
+
+    def full_record(rec):
+        """--full: what the frames after the timed steps measured (lone frames, the counting
+        frame, parity, corrected camera), the drop-in call and the CPU baseline, added to rec."""
+        rec.update({
             # ms_per_step is the steady-state period of a frame stream (frames in flight);
             # frame_wall_ms is ONE frame alone, start to finish, ending with the frame in host
             # memory as the reference's entry returns it (render, accumulate, gather, D2H copy
@@ -671,13 +696,6 @@ def main():
             "frame_wall_ms": r3(main_m["frame_wall_ms"]),
             "frame_device_ms": r3(main_m["frame_latency_ms"]),
             "frame_latency_ms": r3(main_m["frame_latency_ms"]),
-            # render streams the timed frames rotated over (frames in flight), the workspaces and
-            # the samples per pass (rt_scene_usage_get after the run)
-            "frames_in_flight": usage["render_streams"], "workspaces": usage["workspaces"], "frames_issued": issued[0],
-            "pass_samples": usage["pass_samples"],
-            # device memory the scene held for the timed frames: HBM footprint of the product
-            # (scene blobs, counters, slot workspaces, deep-path queues), and the workspaces alone
-            "hbm_footprint_bytes": usage["device_bytes"], "hbm_workspace_bytes": usage["workspace_bytes"],
             "segments_per_primary": round(main_m["segments_per_primary"], 4),
             "msegments_per_s": round(main_m["msegments_per_s"], 1),
             "gtests_per_s": round(main_m["gtests_per_s"], 2),
@@ -699,7 +717,7 @@ def main():
                 "per_launch_span_ms": r3(main_m["span_ms"]),
                 "per_launch_span_achieved": r3(main_m["span_achieved"]),
             },
-        }
+        })
         v = {"exact": 0, "scalar": 1, "fast": 2, "wavefront": 0}[args.variant]
         cull = 0 if args.traversal == "brute" or v == 1 else 7
         kname = TIMED_KERNEL_NAMES if (v, cull) == (0, 7) else f"render_kernel<{v}, {cull}, false, false, false>"
@@ -729,6 +747,62 @@ def main():
                 "msegments_per_s": round(corr["msegments_per_s"], 1), "gtests_per_s": round(corr["gtests_per_s"], 2),
                 "roofline_achieved": r3(corr["achieved"]), "roofline_frac": round(corr["achieved"] / PEAK_FP32_TFLOPS, 4),
                 "effective_tflops": round(corr["effective_tflops"], 2)}
+        if rehearse and args.rehearse_gather:
+            # the N-GPU frame as one rank sees it, REHEARSED ON ONE GPU, NOT MEASURED: its share's
+            # lone frame with the gather's device work stood in (the N-1 peer tiles copied into
+            # the gather buffer, the de-interleave) and the whole frame copied to host memory,
+            # plus the peers' tiles over xGMI, which one GPU cannot run: each peer sends its
+            # tile on its own link at once, estimated at 50 GB/s per link
+            tile_bytes = rows * W * (3 if rgb8 else 12)
+            xgmi_ms = tile_bytes / 50e9 * 1e3
+            rec["rehearsal_projection"] = {
+                "n_gpus": rehearse, "share_period_ms": r3(main_m["ms_per_step"]),
+                "share_frame_wall_ms": r3(main_m["frame_wall_ms"]),
+                "xgmi_tile_bytes": tile_bytes, "xgmi_estimate_ms": round(xgmi_ms, 4),
+                "projected_frame_wall_ms": r3(main_m["frame_wall_ms"] + xgmi_ms),
+                "note": "rehearsed on one GPU, not measured: rank 0's rows alone, the gather's device copies "
+                        "and the full-frame D2H copy stood in; xGMI transfer time estimated"}
+        if world == 1 and not rehearse and not compat and args.variant == "exact" and args.traversal == "cull" \
+                and not args.no_dropin:
+            rec.update(dropin_timing(arrays, cam, W, H, spp, depth, args.seed))
+        if world == 1 and not args.no_cpu_baseline and not rehearse:
+            rec["cpu_baseline"] = cpu_baseline(CONFIGS[args.config], args.camera, args.seed, args.cpu_rows,
+                                               args.cpu_threads)
+
+    if rank == 0:
+        rec = {
+            "metric": "Mrays/sec + frame wall-clock, huge-scene 1280x720x128spp @1/2/4/8 GPU",
+            "value": round(main_m["value"], 3),
+            "unit": "Mrays/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": r3(main_m["ms_per_step"]),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic (reference huge scene, std::mt19937 seed 1234; per-sample PCG32 seed %d)" % args.seed,
+            "config": {"workload": WORKLOAD[args.config], "scene": f"{scene_name} ({n_spheres} spheres)",
+                       "width": W, "height": H, "spp": spp, "max_depth": depth, "camera": args.camera,
+                       "kernel": "compat_kernel (cuda_impl.cu semantics, bit-exact vs its restatement)" if compat else
+                       ("fast (FMA, stated tolerance)" if args.variant == "fast" else f"{args.variant} (bit-exact)")
+                       + f", {args.traversal}", "parallelism": f"row-interleaved x{world}, RCCL gather of "
+                       + ("u8 (gamma epilogue per rank)" if rgb8 else "f32") + " tiles",
+                       "output": args.output, "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+                       "hw_queues_env": hw_env,
+                       # the scene's rt_options (library defaults, RT_OPTIONS, --options): deep-path
+                       # split (DESIGN §4.1) and the lone-pass size below which passes are not split
+                       "deep_split": opts.deep_split, "deep_min_items": opts.deep_min_items,
+                       "options": {k: getattr(opts, k) for k, _ in rt.abi.RtOptions._fields_ if k != "size"}},
+            # render streams the timed frames rotated over (frames in flight), the workspaces and
+            # the samples per pass (rt_scene_usage_get after the run)
+            "frames_in_flight": usage["render_streams"], "workspaces": usage["workspaces"], "frames_issued": issued[0],
+            "pass_samples": usage["pass_samples"],
+            # device memory the scene held for the timed frames: HBM footprint of the product
+            # (scene blobs, counters, slot workspaces, deep-path queues), and the workspaces alone
+            "hbm_footprint_bytes": usage["device_bytes"], "hbm_workspace_bytes": usage["workspace_bytes"],
+        }
         if rehearse:
             rr = args.rehearse_rank
             rows_desc = (f"rows {params.row_offset}..{params.row_offset + rows - 1}" if args.rehearse_blocks
@@ -737,27 +811,8 @@ def main():
                                 + ("gather's device copies stood in on the caller stream" if args.rehearse_gather
                                    else "no gather") + "; value = "
                                 f"this rank's Mrays/s, x{rehearse} for the ideal {rehearse}-GPU job")
-            if args.rehearse_gather:
-                # the N-GPU frame as one rank sees it, REHEARSED ON ONE GPU, NOT MEASURED: its share's
-                # lone frame with the gather's device work stood in (the N-1 peer tiles copied into
-                # the gather buffer, the de-interleave) and the whole frame copied to host memory,
-                # plus the peers' tiles over xGMI, which one GPU cannot run: each peer sends its
-                # tile on its own link at once, estimated at 50 GB/s per link
-                tile_bytes = rows * W * (3 if rgb8 else 12)
-                xgmi_ms = tile_bytes / 50e9 * 1e3
-                rec["rehearsal_projection"] = {
-                    "n_gpus": rehearse, "share_period_ms": r3(main_m["ms_per_step"]),
-                    "share_frame_wall_ms": r3(main_m["frame_wall_ms"]),
-                    "xgmi_tile_bytes": tile_bytes, "xgmi_estimate_ms": round(xgmi_ms, 4),
-                    "projected_frame_wall_ms": r3(main_m["frame_wall_ms"] + xgmi_ms),
-                    "note": "rehearsed on one GPU, not measured: rank 0's rows alone, the gather's device copies "
-                            "and the full-frame D2H copy stood in; xGMI transfer time estimated"}
-        if world == 1 and not rehearse and not compat and args.variant == "exact" and args.traversal == "cull" \
-                and not args.no_dropin:
-            rec.update(dropin_timing(arrays, cam, W, H, spp, depth, args.seed))
-        if world == 1 and not args.no_cpu_baseline and not rehearse:
-            rec["cpu_baseline"] = cpu_baseline(CONFIGS[args.config], args.camera, args.seed, args.cpu_rows,
-                                               args.cpu_threads)
+        if args.full:
+            full_record(rec)
         print(json.dumps(rec), flush=True)
     ds.close()
     if distributed:

@@ -13,8 +13,8 @@
 #     everything else (app::data, save_to_file("image_cuda.ppm"), the dead CPU loop) unchanged.
 # Built with -D_DEBUG, the reference's debug frame size (main.cxx:25-27: 512x256, 16 spp), so the
 # test can compare its PPM with the reference's own render of that frame.
-# Output: examples/_ref/ref_main_dropin (git-ignored; travels to the GPU box, rpath to the
-# in-tree library). Never copies reference sources into the repository.
+# Output: oracle/_ref/ref_main_dropin, beside the reference's CPU harnesses (git-ignored; rpath to
+# the in-tree library). Never copies reference sources into the repository.
 set -euo pipefail
 REF=${RT_REFERENCE:-/root/reference}
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"

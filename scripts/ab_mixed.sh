@@ -11,7 +11,7 @@ for r in $(seq 1 "${ROUNDS:-3}"); do
   for spec in "${SPECS[@]}"; do
     IFS='|' read -r tag lib opt <<< "$spec"
     if [ "$lib" = default ]; then unset RT_LIB_PATH; else export RT_LIB_PATH=$PWD/$lib; fi
-    timeout -k 10 200 python bench.py --no-cpu-baseline --corrected-steps 0 ${BENCH_ARGS:-} --options "$opt" > "$O/${tag}_r$r.json" 2> "$O/${tag}_r$r.err"
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --corrected-steps 0 ${BENCH_ARGS:-} --options "$opt" > "$O/${tag}_r$r.json" 2> "$O/${tag}_r$r.err"
     rc=$?; unset RT_LIB_PATH
     if [ $rc -ne 0 ]; then echo "FAIL $tag r$r rc=$rc"; tail -3 "$O/${tag}_r$r.err"; exit $rc; fi
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(f\"{sys.argv[2]:10s} period {d['ms_per_step']:.3f} lone {d['frame_device_ms']:.3f} hbm {d['hbm_footprint_bytes']/2**30:.2f} GiB parity {d['parity'].get('matches_reference')}\")" "$O/${tag}_r$r.json" "$tag"

@@ -22,14 +22,14 @@ for s in ${STEPS:-smoke pytest bench prof}; do
     probe)  step probe 60 ./scripts/_bin/lds_oob_probe ;;
     new)    step new 600 python -u -m pytest ${NEW_TESTS:-tests} -m gpu -v --timeout 200 --timeout-method thread ;;
     rehearse) for n in ${REHEARSE_N:-2 4 8}; do
-                step rehearse_n$n 600 python bench.py --rehearse-world $n --rehearse-gather --no-cpu-baseline --corrected-steps 0 ${BENCH_ARGS:-}
+                step rehearse_n$n 600 python bench.py --full --rehearse-world $n --rehearse-gather --no-cpu-baseline --corrected-steps 0 ${BENCH_ARGS:-}
               done ;;
     pytest) step pytest 900 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout-method thread ;;
-    stock)  step stock 600 python bench.py --hw-queues 0 --no-cpu-baseline ${BENCH_ARGS:-} ;;
-    bench)  step bench 600 python bench.py ${BENCH_ARGS:-} ;;
+    stock)  step stock 600 python bench.py --full --hw-queues 0 --no-cpu-baseline ${BENCH_ARGS:-} ;;
+    bench)  step bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
     ab)     step ab 900 python scripts/ab_variants.py --rounds ${AB_ROUNDS:-5} --variants ${AB_VARIANTS:-exact:cull,fast:cull} ;;
     abl)    RT_LIB_PATH=$PWD/scripts/_abl/librt_mi355x.so step abl 900 python scripts/ab_variants.py --rounds ${AB_ROUNDS:-5} --variants ${AB_VARIANTS:-exact:cull,fast:cull} ;;
-    prof)   step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --no-cpu-baseline --corrected-steps 0 ${BENCH_ARGS:-} ;;
+    prof)   step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --full --no-cpu-baseline --corrected-steps 0 ${BENCH_ARGS:-} ;;
   esac
 done
 echo "=== done"

@@ -12,7 +12,7 @@ for lib in ${LIBS:-default}; do
   n=$(echo "$lib" | tr -c 'a-zA-Z0-9' '_')
   if [ "$lib" = default ]; then unset RT_LIB_PATH; else export RT_LIB_PATH=$PWD/$lib; fi
   timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d "$O/$n" -o run -- \
-    python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --corrected-steps 0 ${ARGS:-} > "$O/$n.log" 2>&1
+    python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --corrected-steps 0 ${ARGS:-} > "$O/$n.log" 2>&1
   rc=$?; if [ $rc -ne 0 ]; then echo "FAILED rc=$rc: $lib"; tail -5 "$O/$n.log"; exit $rc; fi
   python3 - "$O/$n" "$lib" <<'PY'
 import csv, glob, sys, collections

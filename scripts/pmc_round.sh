@@ -15,7 +15,7 @@ while read -r line; do
   [ -z "$line" ] && continue
   i=$((i+1))
   echo "=== pass $i: $line"
-  timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $line --output-format csv -d "$OUT/p$i" -o run -- python3 bench.py $ARGS > "$OUT/p$i.log" 2>&1
+  timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $line --output-format csv -d "$OUT/p$i" -o run -- python3 bench.py --full $ARGS > "$OUT/p$i.log" 2>&1
   rc=$?
   echo "rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/p$i.log"; exit $rc; fi

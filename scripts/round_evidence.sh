@@ -15,7 +15,7 @@ cp gpurun_out/${T}pmc/pmc_render.json profiles/pmc_render_c3.json  # (this copy 
 TAG=$T STEPS="bench prof" STRICT=1 bash scripts/gpu_round.sh || exit $?
 mkdir -p gpurun_out/${T}reh
 for n in 1 2 4 8; do
-  if [ $n = 1 ]; then a=""; else a="--rehearse-world $n --rehearse-gather"; fi
+  if [ $n = 1 ]; then a="--full"; else a="--full --rehearse-world $n --rehearse-gather"; fi
   timeout -k 10 300 python bench.py $a --no-cpu-baseline --corrected-steps 0 > gpurun_out/${T}reh/n$n.json 2> gpurun_out/${T}reh/n$n.err || exit $?
 done
 echo ALLDONE

@@ -17,8 +17,8 @@ on the GPU and compare by digest.
 --dropin: the frame the reference's own main() renders in its debug build (src/main.cxx:23-27:
 512x256, 16 spp, simple scene, depth 64), written by the reference's app::save_to_file
 (main.cxx:87-101) to dropin_simple_512x256_s16.ppm, with its digests in dropin.json — what
-examples/_ref/ref_main_dropin (the reference's main() with the INTEGRATION.md swap,
-examples/build_ref_dropin.sh) must reproduce on the GPU.
+oracle/_ref/ref_main_dropin (the reference's main() with the INTEGRATION.md swap,
+oracle/build_ref_dropin.sh) must reproduce on the GPU.
 """
 import hashlib
 import json

@@ -1,9 +1,9 @@
 """The C++ drop-in (include/rt_render_impl.hpp) against the reference's own output.
 
 Two binaries:
-* examples/_ref/ref_main_dropin — the REFERENCE's main() (src/main.cxx:104-118) with the
+* oracle/_ref/ref_main_dropin — the REFERENCE's main() (src/main.cxx:104-118) with the
   INTEGRATION.md swap applied to a scratch copy and compiled against librt_mi355x.so by
-  examples/build_ref_dropin.sh: its real raytracer::data / primitives::sphere /
+  oracle/build_ref_dropin.sh: its real raytracer::data / primitives::sphere /
   material::types / math::u8vec3, `rt::render_impl(raytracer_data, ...)` where `cuda_impl`
   was called (main.cxx:114), its own app::save_to_file. Built in its debug frame size
   (512x256, 16 spp). Its PPM must match the PPM the reference's CPU path writes for that frame
@@ -23,7 +23,7 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(REPO, "raytracinginoneweekend_amd")
 GOLDEN = os.path.join(REPO, "tests", "golden")
-REF_DROPIN = os.path.join(REPO, "examples", "_ref", "ref_main_dropin")
+REF_DROPIN = os.path.join(REPO, "oracle", "_ref", "ref_main_dropin")
 
 
 def _build(tmp_path):
@@ -65,7 +65,7 @@ def test_reference_main_dropin_throws_without_device(tmp_path):
     """The reference's main() does not catch: like cuda_impl's check_errors (cuda_impl.cu:101-114)
     the drop-in throws std::runtime_error, which terminates the program."""
     if not os.path.exists(REF_DROPIN):
-        pytest.skip("examples/_ref/ref_main_dropin not built (needs /root/reference: build())")
+        pytest.skip("oracle/_ref/ref_main_dropin not built (build() makes it where the reference is)")
     if _has_device():
         pytest.skip("device present: covered by the gpu test")
     r = subprocess.run([REF_DROPIN], capture_output=True, text=True, cwd=tmp_path)
@@ -78,7 +78,7 @@ def test_reference_main_dropin_matches_reference_ppm(tmp_path):
     image_cuda.ppm (main.cxx:116); it equals the reference CPU path's PPM of the same frame
     (header byte for byte, texels within 1 LSB: device pow vs glibc powf), and its texels are
     exactly the library's u8 epilogue of a frame whose f32 bits are the reference's."""
-    assert os.path.exists(REF_DROPIN), "examples/_ref/ref_main_dropin missing: run build() where the reference is"
+    assert os.path.exists(REF_DROPIN), "oracle/_ref/ref_main_dropin missing: run build() where the reference is"
     meta = json.load(open(os.path.join(GOLDEN, "dropin.json")))
     r = subprocess.run([REF_DROPIN], capture_output=True, text=True, cwd=tmp_path, timeout=120)
     assert r.returncode == 0, r.stderr
