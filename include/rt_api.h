@@ -312,6 +312,45 @@ int rt_scene_destroy(rt_scene *scene);
  * enqueued on `stream`, so results appear in stream order.                                   */
 int rt_render_device(rt_scene *scene, const rt_camera *camera, const rt_params *params,
                      float *d_rgb, void *stream, uint64_t *d_segments);
+/* ---- first-hit feature buffers --------------------------------------
+ * The guide buffers a denoiser or compositor takes, for the pass rt_params describes. Sample s
+ * of a pixel is the beauty render's sample s (same key with the frame's spp, same streams, same
+ * camera::ray; max_depth is not used), so samples 0..samples-1 are the beauty's first ones.
+ * Its first hit is hit_world (raytracer.hxx:94-118). Per sample:
+ *   albedo  the hit sphere's material albedo, whatever its kind; on a miss the sky's colour
+ *           background(.5 unit_direction(d).y + 1) (main.cxx:71 with an attenuation of 1)
+ *   normal  (p - c) / r (raytracer.hxx:71; a negative radius flips it); (0, 0, 0) on a miss
+ *   depth   hit.time: t in units of the un-normalised ray direction d; 0 on a miss
+ *   alpha   1 on a hit, 0 on a miss
+ * A pixel's value of each float plane is the samples' sum in the blocked order of main.cxx:205
+ * divided by float(samples). sphere_id is the index (in the caller's array) of the sphere sample
+ * 0 hits, or 0xffffffff. Rows and layout follow rt_params as for the beauty (row_offset,
+ * row_stride, num_rows; packed or RT_FLAG_FULL_FRAME); one-channel planes are indexed
+ * row * width + x. Only the planes given are written. RT_FLAG_BRUTE_FORCE is honoured (same
+ * bits); RT_FLAG_FAST_MATH, RT_FLAG_SCALAR_SCENE, RT_FLAG_WAVEFRONT and RT_FLAG_CUDA_COMPAT
+ * return RT_ERR_UNSUPPORTED, as does a scene whose geometry does not fit LDS.              */
+typedef struct rt_aov_buffers {
+    uint32_t size;        /* sizeof(rt_aov_buffers): the record's revision              */
+    uint32_t samples;     /* samples 0..samples-1 of every pixel; 0 = params->spp       */
+    float *albedo;        /* rows x width x 3, or NULL: plane not wanted                */
+    float *normal;        /* rows x width x 3, or NULL                                  */
+    float *depth;         /* rows x width, or NULL                                      */
+    float *alpha;         /* rows x width, or NULL                                      */
+    uint32_t *sphere_id;  /* rows x width, or NULL                                      */
+} rt_aov_buffers;
+/* Device pointers; one kernel enqueued on `stream` (a hipStream_t, or NULL), results in stream
+ * order, no host synchronisation (the first call with a camera and rows computes the pass's
+ * dealing order on the host and uploads it). Ordered like any other call on the scene.      */
+int rt_render_aov_device(rt_scene *scene, const rt_camera *camera, const rt_params *params,
+                         const rt_aov_buffers *aov, void *stream);
+/* Host pointers, synchronous, through the cached per-device context of rt_render_f32. With
+ * RT_FLAG_FULL_FRAME only the rendered rows of the caller's planes are written. stats
+ * (optional): primaries = segments = width * rows * samples, kernel_ms, wall_ms; the test
+ * counters are 0.                                                                            */
+int rt_render_aov(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
+                  uint32_t n_materials, const rt_camera *camera, const rt_params *params,
+                  const rt_aov_buffers *aov, rt_stats *stats);
+
 /* Device memory a scene holds and how its renders are cut (after the last render call).  */
 typedef struct rt_scene_usage {
     uint64_t device_bytes;     /* every device allocation of the scene                       */

@@ -93,12 +93,26 @@ class RtStats(C.Structure):
     ]
 
 
+class RtAovBuffers(C.Structure):
+    """rt_aov_buffers (include/rt_api.h): the first-hit feature planes of a call, NULL = not wanted."""
+    _fields_ = [
+        ("size", C.c_uint32), ("samples", C.c_uint32),
+        ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p),
+        ("sphere_id", C.c_void_p),
+    ]
+
+
+# the planes of rt_aov_buffers: name -> (channels, numpy dtype, value of a pixel no call wrote)
+AOV_PLANES = {"albedo": (3, np.float32, 0), "normal": (3, np.float32, 0), "depth": (1, np.float32, 0),
+              "alpha": (1, np.float32, 0), "sphere_id": (1, np.uint32, 0xffffffff)}
+
 SPHERE_DTYPE = np.dtype([("center", "<f4", (3,)), ("radius", "<f4"), ("material", "<u4")])
 MATERIAL_DTYPE = np.dtype([("kind", "<u4"), ("albedo", "<f4", (3,)), ("param", "<f4")])
 assert SPHERE_DTYPE.itemsize == C.sizeof(RtSphere) == 20
 assert MATERIAL_DTYPE.itemsize == C.sizeof(RtMaterial) == 20
 assert C.sizeof(RtParams) == 40
 assert C.sizeof(RtOptions) == 64 and C.sizeof(RtSceneUsage) == 56
+assert C.sizeof(RtAovBuffers) == 48
 
 
 def ptr(arr, ctype=C.c_void_p):

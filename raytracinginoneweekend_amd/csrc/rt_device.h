@@ -222,6 +222,28 @@ struct KSky {
     unsigned long long *segments;  // optional: adds n_pix * spp segments (no sphere test)
 };
 
+// The first-hit feature buffers (aov_kernel, rt_aov.hip): one wave per 64-pixel
+// block of the pass's enumeration (positions 64 b .. 64 b + 63 of the permuted enumeration), one
+// lane per pixel, samples [0, samples) of the frame's spp in order. The scene fields carry the
+// names closest_hit reads from its parameter record (KParams).
+struct KAov {
+    FrameConsts fc;                // the frame (fc.spp keys the samples; fc.sample_begin unused)
+    const uint32_t *block_perm;    // the pass's dealing order (KParams::block_perm), or null
+    uint32_t n_blocks;             // ceil(n_pixels / 64)
+    uint32_t sky_block0;           // blocks from here on are proven sky: no closest hit (n_blocks: none)
+    uint32_t samples;              // 1..fc.spp
+    uint32_t full_frame;
+    // scene (KParams)
+    const float4 *blob;
+    uint32_t lds_units, n_geo, n_always, clus_offset;
+    uint32_t n_supers, supers_offset, use_root, transpose_max, fast_roots;
+    float clus_pad;
+    uint32_t shade_offset, shade_lds, n_spheres;
+    // outputs, each optional: rows x W (x 3), laid out as rt_params says
+    float *albedo, *normal, *depth, *alpha;
+    uint32_t *sphere_id;
+};
+
 // The wavefront variant's ray queue (structure of arrays, capacity cap rays): f = [9][cap]
 // floats {o.xyz, d.xyz, attenuation.xyz}, then the data-stream state, the item index (slot) and
 // the segment count of each ray; count = rays in the queue.

@@ -44,6 +44,10 @@ hipError_t occupancy_wave_bounce(int cull, int *blocks_per_cu, size_t lds);
 hipError_t occupancy_compat(int *blocks_per_cu);
 hipError_t launch_epilogue(const float *in, uint8_t *out, uint64_t n, hipStream_t stream);
 hipError_t launch_sky(const KSky &k, hipStream_t stream);
+// rt_aov.hip
+hipError_t launch_aov(int cull, const KAov &k, uint32_t grid, hipStream_t stream);
+hipError_t occupancy_aov(int cull, int *blocks_per_cu, size_t lds);
+hipError_t static_lds_aov(int cull, size_t *bytes);
 } // namespace rt
 
 namespace {
@@ -199,6 +203,10 @@ struct rt_scene {
     // transposed-test records and per-lane arrays; hipFuncGetAttributes)
     size_t static_lds[2] = {0, 0};
     size_t static_lds_pairs = 0;  // the culled kernel's sample-pair instantiation (its parked colours)
+    // aov_kernel (rt_render_aov_device), on first use: static LDS per traversal (~0 = unknown) and
+    // blocks per CU [culled][shade records in LDS] (-1 = unknown)
+    size_t static_lds_aov[2] = {~static_cast<size_t>(0), ~static_cast<size_t>(0)};
+    int occ_aov[2][2] = {{-1, -1}, {-1, -1}};
     // the last render's cut (rt_scene_usage_get)
     uint32_t used_streams = 0, used_ws = 0, used_pass = 0, used_deep = 0, used_pairs = 0, used_split = 0;
     uint32_t used_lead = 0, used_sky = 0;  // the last pass's tile classes
@@ -263,6 +271,27 @@ int check_params(const rt_params *p)
     if (p->flags & ~(RT_FLAG_FULL_FRAME | RT_FLAG_FAST_MATH | RT_FLAG_SCALAR_SCENE | RT_FLAG_BRUTE_FORCE | RT_FLAG_CUDA_COMPAT |
                      RT_FLAG_WAVEFRONT))
         return fail(RT_ERR_INVALID, "params: unknown flag");
+    return RT_OK;
+}
+
+// The arguments of the feature-buffer calls, decided before any HIP call.
+int check_aov(const rt_params *p, const rt_aov_buffers *a, const char *who)
+{
+    const std::string w(who);
+    if (!a) return fail(RT_ERR_INVALID, w + ": null aov");
+    if (a->size != sizeof(rt_aov_buffers))
+        return fail(RT_ERR_INVALID, w + ": aov size " + std::to_string(a->size) + " is not sizeof(rt_aov_buffers) = " +
+                                        std::to_string(sizeof(rt_aov_buffers)));
+    if (int rc = check_params(p); rc != RT_OK) return rc;
+    if (a->samples > p->spp)
+        return fail(RT_ERR_INVALID, w + ": aov samples " + std::to_string(a->samples) + " exceed spp " + std::to_string(p->spp));
+    if (!a->albedo && !a->normal && !a->depth && !a->alpha && !a->sphere_id)
+        return fail(RT_ERR_INVALID, w + ": no plane requested");
+    static const struct { uint32_t bit; const char *name; } unsupported[] = {
+        {RT_FLAG_FAST_MATH, "RT_FLAG_FAST_MATH"}, {RT_FLAG_SCALAR_SCENE, "RT_FLAG_SCALAR_SCENE"},
+        {RT_FLAG_WAVEFRONT, "RT_FLAG_WAVEFRONT"}, {RT_FLAG_CUDA_COMPAT, "RT_FLAG_CUDA_COMPAT"}};
+    for (const auto &u : unsupported)
+        if (p->flags & u.bit) return fail(RT_ERR_UNSUPPORTED, w + ": " + u.name + " is not supported (the exact kernel only)");
     return RT_OK;
 }
 
@@ -691,10 +720,10 @@ int rt_render_device(rt_scene *sc, const rt_camera *camera, const rt_params *par
 }
 
 namespace {
-int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
-                       uint64_t *d_segments)
+// The camera, frame, rows and pixel decomposition of the pass that camera + P describe, into k
+// (every render entry point fills them the same way); k.n_pixels = 0: no rows to render.
+int frame_params(const rt_scene *sc, const rt_camera *camera, const rt_params &P, rt::KParams &k, const char *who)
 {
-    rt::KParams k{};
     for (int c = 0; c < 3; ++c) {
         k.org[c] = camera->origin[c];
         k.llc[c] = camera->lower_left_corner[c];
@@ -714,8 +743,7 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     k.inc_data = ((2ull * P.seed) << 1u) | 1ull;
     k.inc_cam = ((2ull * P.seed + 1ull) << 1u) | 1ull;
     const uint64_t n_pixels = static_cast<uint64_t>(P.width) * k.num_rows;
-    if (n_pixels == 0) return RT_OK;
-    if (n_pixels >= (1ull << 31)) return fail(RT_ERR_INVALID, "rt_render_device: more than 2^31 pixels in one call");
+    if (n_pixels >= (1ull << 31)) return fail(RT_ERR_INVALID, std::string(who) + ": more than 2^31 pixels in one call");
     k.n_pixels = static_cast<uint32_t>(n_pixels);
     // 64-pixel tiles (one wave's lanes for one sample), 8 x 8 (the kernel's decomposition takes
     // 2^lw x 64/2^lw; 16x4, 32x2 and 64x1 measured alike or slower for strided row shares:
@@ -727,7 +755,16 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     k.tiled_rows = tiled ? (k.num_rows / th) * th : 0u;
     k.n_spheres = sc->n_spheres;
     k.n_materials = sc->n_materials;
+    return RT_OK;
+}
 
+int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
+                       uint64_t *d_segments)
+{
+    rt::KParams k{};
+    if (int rc = frame_params(sc, camera, P, k, "rt_render_device"); rc) return rc;
+    const uint64_t n_pixels = k.n_pixels;
+    if (n_pixels == 0) return RT_OK;
 
     // Variant: exact (bit-exact) or fast (tolerance); clustered culling unless brute force is
     // asked for; the scalar-cache A/B variant is brute force only. Each needs its blob in LDS
@@ -1376,9 +1413,97 @@ int render_compat(rt_scene *sc, const rt_camera *camera, const rt_params &P, flo
     RT_HIP(hipEventRecord(sc->ev_end[ring], st));
     return RT_OK;
 }
+
+// The first-hit feature buffers: one launch of aov_kernel on the caller's
+// stream, the pass's blocks in its dealing order (pass_order) so that the blocks proven sky skip
+// the closest-hit test. It reads the scene and the order's permutation and writes the caller's
+// planes: no workspace, nothing that grows with the samples.
+int render_aov_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, const rt_aov_buffers &A, hipStream_t st)
+{
+    rt::KParams k{};
+    if (int rc = frame_params(sc, camera, P, k, "rt_render_aov_device"); rc) return rc;
+    if (k.n_pixels == 0) return RT_OK;
+    fill_frame_consts(k);
+    const rt_options &O = sc->opt;
+    const bool cull = !(P.flags & RT_FLAG_BRUTE_FORCE) && sc->n_clusters[1] > 0;
+    const int b = cull ? 1 : 0, cull_mode = cull ? 7 : 0;
+    if (sc->static_lds_aov[b] == ~static_cast<size_t>(0)) RT_HIP(rt::static_lds_aov(cull_mode, &sc->static_lds_aov[b]));
+    const size_t static_lds = sc->static_lds_aov[b];
+    if (static_cast<size_t>(sc->shade_offset[b]) * 16u + static_lds > sc->max_lds)
+        return fail(RT_ERR_UNSUPPORTED, "rt_render_aov_device: scene too large for LDS");
+    rt::KAov a{};
+    a.fc = k.fc;
+    a.samples = A.samples ? A.samples : P.spp;
+    a.full_frame = k.full_frame;
+    a.n_blocks = (k.n_pixels + 63u) / 64u;
+    a.blob = reinterpret_cast<const float4 *>(sc->blob[b]);
+    a.n_geo = sc->n_geo[b];
+    a.n_always = sc->n_always[b];
+    a.clus_offset = sc->clus_offset[b];
+    a.clus_pad = sc->clus_pad[b];
+    a.n_supers = sc->n_supers[b];
+    a.supers_offset = sc->supers_offset[b];
+    a.use_root = (O.diag & RT_DIAG_NO_ROOT_BOX) ? 0u : 1u;
+    a.transpose_max = O.transpose_max;
+    a.fast_roots = sc->in_fast_range && camera_in_fast_range(*camera) && !(O.diag & RT_DIAG_IEEE_ROOTS) ? 1u : 0u;
+    a.shade_offset = sc->shade_offset[b];
+    a.n_spheres = sc->n_spheres;
+    // the shading records join the geometry in LDS unless that costs workgroups per CU, as for the
+    // render kernels; RT_DIAG_SHADE_LDS / RT_DIAG_SHADE_GLOBAL force the choice (same bits)
+    auto occ_for = [&](int in_lds, int *out) -> int {
+        int &o = sc->occ_aov[b][in_lds];
+        if (o < 0) {
+            RT_HIP(rt::occupancy_aov(cull_mode, &o, static_cast<size_t>(in_lds ? sc->blob_units[b] : sc->shade_offset[b]) * 16u));
+            o = std::max(o, 1);
+        }
+        *out = o;
+        return RT_OK;
+    };
+    const bool shade_fits = static_cast<size_t>(sc->blob_units[b]) * 16u + static_lds <= sc->max_lds;
+    int occ_geo = 0, occ_all = 0;
+    if (int rc = occ_for(0, &occ_geo); rc) return rc;
+    if (shade_fits)
+        if (int rc = occ_for(1, &occ_all); rc) return rc;
+    a.shade_lds = shade_fits && ((O.diag & RT_DIAG_SHADE_LDS) ? true : (O.diag & RT_DIAG_SHADE_GLOBAL) ? false : occ_all >= occ_geo);
+    a.lds_units = a.shade_lds ? sc->blob_units[b] : sc->shade_offset[b];
+    const int occ = a.shade_lds ? occ_all : occ_geo;
+    // the dealing order and its proven-sky blocks, under the beauty's conditions for sky_kernel
+    const rt_scene::Order *ord = nullptr;
+    if (sc->has_geom && cull && !(O.diag & RT_DIAG_NATURAL_ORDER))
+        if (int rc = pass_order(sc, *camera, k, &ord); rc) return rc;
+    a.block_perm = ord ? ord->d_perm : nullptr;
+    const bool sky = a.block_perm && ord->t.n_sky && !(O.diag & RT_DIAG_NO_SKY);
+    a.sky_block0 = sky ? static_cast<uint32_t>(ord->t.perm.size() - ord->t.n_sky) : a.n_blocks;
+    a.albedo = A.albedo;
+    a.normal = A.normal;
+    a.depth = A.depth;
+    a.alpha = A.alpha;
+    a.sphere_id = A.sphere_id;
+    const uint32_t grid = static_cast<uint32_t>(
+        std::max<uint64_t>(1, std::min<uint64_t>(static_cast<uint64_t>(occ) * sc->cu_count, (a.n_blocks + 3u) / 4u)));
+    if (O.diag & RT_DIAG_VERBOSE)
+        std::fprintf(stderr, "[rt] aov cull=%d shade_lds=%u lds=%zu B occ=%d WG/CU cus=%d grid=%u blocks=%u sky_blocks=%u "
+                             "ordered=%d samples=%u of %u\n",
+                     cull_mode, a.shade_lds, static_cast<size_t>(a.lds_units) * 16u, occ, sc->cu_count, grid, a.n_blocks,
+                     a.n_blocks - a.sky_block0, a.block_perm ? 1 : 0, a.samples, P.spp);
+    RT_HIP(rt::launch_aov(cull_mode, a, grid, st));
+    return RT_OK;
+}
 } // namespace
 
 extern "C" {
+
+int rt_render_aov_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, const rt_aov_buffers *aov,
+                         void *stream)
+{
+    if (int rc = check_aov(params, aov, "rt_render_aov_device"); rc != RT_OK) return rc;
+    if (!sc || !camera) return fail(RT_ERR_INVALID, "rt_render_aov_device: null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RT_HIP(hipSetDevice(sc->device));
+    if (int rc = stream_enter(sc, st); rc != RT_OK) return rc;
+    if (int rc = render_aov_impl(sc, camera, *params, *aov, st); rc != RT_OK) return rc;
+    return stream_leave(sc, st);
+}
 
 int rt_render_cuda_impl(uint32_t width, uint32_t height, uint8_t *rgb_out)
 {
@@ -1510,6 +1635,8 @@ struct SyncContext {
     uint8_t *d_u8 = nullptr;
     size_t u8_bytes = 0;
     uint64_t *d_seg = nullptr;
+    void *d_aov = nullptr;  // rt_render_aov: the requested planes, one after the other
+    size_t aov_bytes = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 std::mutex g_sync_mu;  // one synchronous render at a time per process (the reference's entry is not re-entrant)
@@ -1521,12 +1648,34 @@ void sync_release(int dev, SyncContext &c)
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(dev);
     if (c.sc) rt_scene_destroy(c.sc);
-    for (void *p : {(void *)c.d_rgb, (void *)c.d_u8, (void *)c.d_seg})
+    for (void *p : {(void *)c.d_rgb, (void *)c.d_u8, (void *)c.d_seg, c.d_aov})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : {c.e0, c.e1})
         if (e) (void)hipEventDestroy(e);
     c = SyncContext{};
     (void)hipSetDevice(prev);
+}
+
+// The device's context holds this scene under the current process-default options: kept if it
+// does already, rebuilt otherwise (g_sync_mu held).
+int sync_scene(int dev, SyncContext &cx, const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
+               uint32_t n_materials)
+{
+    rt_options opt;
+    if (int rc = rt_get_default_options(&opt); rc) return rc;
+    std::vector<unsigned char> key(sizeof(rt_sphere) * n_spheres + sizeof(rt_material) * n_materials + sizeof(opt));
+    unsigned char *k = key.data();
+    if (n_spheres) std::memcpy(k, spheres, sizeof(rt_sphere) * n_spheres);
+    k += sizeof(rt_sphere) * n_spheres;
+    std::memcpy(k, materials, sizeof(rt_material) * n_materials);
+    k += sizeof(rt_material) * n_materials;
+    std::memcpy(k, &opt, sizeof(opt));
+    if (!cx.sc || key != cx.key) {
+        sync_release(dev, cx);
+        if (int rc = rt_scene_create(spheres, n_spheres, materials, n_materials, dev, &cx.sc); rc) return rc;
+        cx.key.swap(key);
+    }
+    return RT_OK;
 }
 
 // Synchronous host-buffer render on the current device (the cuda_impl replacement).
@@ -1541,22 +1690,7 @@ int render_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_material 
     RT_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(g_sync_mu);
     SyncContext &cx = g_sync[dev];
-    {
-        rt_options opt;
-        if (int rc = rt_get_default_options(&opt); rc) return rc;
-        std::vector<unsigned char> key(sizeof(rt_sphere) * n_spheres + sizeof(rt_material) * n_materials + sizeof(opt));
-        unsigned char *k = key.data();
-        if (n_spheres) std::memcpy(k, spheres, sizeof(rt_sphere) * n_spheres);
-        k += sizeof(rt_sphere) * n_spheres;
-        std::memcpy(k, materials, sizeof(rt_material) * n_materials);
-        k += sizeof(rt_material) * n_materials;
-        std::memcpy(k, &opt, sizeof(opt));
-        if (!cx.sc || key != cx.key) {
-            sync_release(dev, cx);
-            if (int rc = rt_scene_create(spheres, n_spheres, materials, n_materials, dev, &cx.sc); rc) return rc;
-            cx.key.swap(key);
-        }
-    }
+    if (int rc = sync_scene(dev, cx, spheres, n_spheres, materials, n_materials); rc) return rc;
     rt_scene *sc = cx.sc;
     const rt_params &P = *params;
     const uint64_t rows = (P.flags & RT_FLAG_FULL_FRAME) ? P.height : rows_of(P);
@@ -1615,9 +1749,97 @@ int render_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_material 
     return rc;
 }
 
+// Synchronous feature buffers into host planes, through the same cached context: the planes are
+// rendered into one device buffer and copied out (full frame: the rendered rows only).
+int render_aov_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
+                    const rt_camera *camera, const rt_params *params, const rt_aov_buffers *aov, rt_stats *stats)
+{
+    if (int rc = check_aov(params, aov, "rt_render_aov"); rc != RT_OK) return rc;
+    if (!camera) return fail(RT_ERR_INVALID, "rt_render_aov: null camera");
+    if ((n_spheres && !spheres) || !materials || !n_materials) return fail(RT_ERR_INVALID, "rt_render_aov: null scene");
+    const auto t0 = std::chrono::steady_clock::now();
+    int dev = 0;
+    RT_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_sync_mu);
+    SyncContext &cx = g_sync[dev];
+    if (int rc = sync_scene(dev, cx, spheres, n_spheres, materials, n_materials); rc) return rc;
+    const rt_params &P = *params;
+    const bool full = (P.flags & RT_FLAG_FULL_FRAME) != 0u;
+    const uint64_t rows = rows_of(P), rows_out = full ? P.height : rows;
+    const uint32_t samples = aov->samples ? aov->samples : P.spp;
+    // the planes asked for, packed into the context's buffer (256-byte aligned)
+    struct Plane { void *host; uint32_t channels; size_t at; };
+    Plane planes[5] = {{aov->albedo, 3, 0}, {aov->normal, 3, 0}, {aov->depth, 1, 0}, {aov->alpha, 1, 0}, {aov->sphere_id, 1, 0}};
+    size_t total = 0;
+    for (Plane &pl : planes)
+        if (pl.host) {
+            pl.at = total;
+            total += (static_cast<size_t>(rows_out) * P.width * pl.channels * 4u + 255u) & ~static_cast<size_t>(255u);
+        }
+    int rc = RT_OK;
+    auto chk = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+        return rc == RT_OK;
+    };
+    if (cx.aov_bytes < total || !cx.d_aov) {
+        if (cx.d_aov) chk(hipFree(cx.d_aov), "hipFree");
+        cx.d_aov = nullptr;
+        cx.aov_bytes = 0;
+        if (chk(hipMalloc(&cx.d_aov, std::max<size_t>(total, 256)), "hipMalloc")) cx.aov_bytes = total;
+    }
+    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
+    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
+    float ms = 0.f;
+    if (rc == RT_OK && rows) {
+        char *base = static_cast<char *>(cx.d_aov);
+        auto dptr = [&](const Plane &pl) -> void * { return pl.host ? base + pl.at : nullptr; };
+        rt_aov_buffers d{static_cast<uint32_t>(sizeof(rt_aov_buffers)), samples,
+                         static_cast<float *>(dptr(planes[0])), static_cast<float *>(dptr(planes[1])),
+                         static_cast<float *>(dptr(planes[2])), static_cast<float *>(dptr(planes[3])),
+                         static_cast<uint32_t *>(dptr(planes[4]))};
+        chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
+        if (rc == RT_OK) rc = rt_render_aov_device(cx.sc, camera, params, &d, nullptr);
+        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
+        // the copies on the null stream follow the kernel
+        for (const Plane &pl : planes) {
+            if (rc != RT_OK || !pl.host) continue;
+            const size_t row_bytes = static_cast<size_t>(P.width) * pl.channels * 4u;
+            if (!full) {
+                chk(hipMemcpy(pl.host, base + pl.at, rows * row_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+            } else {
+                const size_t st = P.row_stride ? P.row_stride : 1u, first = P.row_offset * row_bytes;
+                chk(hipMemcpy2D(static_cast<char *>(pl.host) + first, st * row_bytes, base + pl.at + first, st * row_bytes,
+                                row_bytes, rows, hipMemcpyDeviceToHost),
+                    "hipMemcpy2D");
+            }
+        }
+        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_render_aov");
+        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
+    }
+    if (rc != RT_OK) {
+        // a failed call leaves no state behind: the next one starts from a new context
+        const std::string msg = g_error;
+        sync_release(dev, cx);
+        g_error = msg;
+    }
+    if (rc == RT_OK && stats) {
+        *stats = rt_stats{};
+        stats->primaries = stats->segments = static_cast<uint64_t>(P.width) * rows * samples;
+        stats->kernel_ms = ms;
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
+
+int rt_render_aov(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
+                  const rt_camera *camera, const rt_params *params, const rt_aov_buffers *aov, rt_stats *stats)
+{
+    return render_aov_host(spheres, n_spheres, materials, n_materials, camera, params, aov, stats);
+}
 
 int rt_release_cached(void)
 {

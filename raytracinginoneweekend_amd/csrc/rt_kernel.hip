@@ -859,6 +859,9 @@ __device__ __forceinline__ float4 gld4(const float4 *p, uint32_t i)
     const __attribute__((address_space(1))) float *g = (const __attribute__((address_space(1))) float *)(p + i);
     return make_float4(g[0], g[1], g[2], g[3]);
 }
+// RT_DEVICE_FUNCTIONS_ONLY: a translation unit that includes this file for the device functions
+// above (rt_aov.hip) compiles none of the kernels and launchers below
+#ifndef RT_DEVICE_FUNCTIONS_ONLY
 // sphere ib's dielectric record {1 / ior, x(ior), x(1 / ior), shortcut word}, x(r) = (1 - r) / (1 + r),
 // from LDS or global memory (the blob's tail)
 template <int V, class KP>
@@ -2452,5 +2455,6 @@ hipError_t launch_epilogue(const float *in, uint8_t *out, uint64_t n, hipStream_
     hipLaunchKernelGGL(epilogue_rgb8_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, in, out, n);
     return hipGetLastError();
 }
+#endif  // RT_DEVICE_FUNCTIONS_ONLY
 
 } // namespace rt

@@ -3,6 +3,8 @@
 render_f32 / render_rgb8   synchronous, host numpy buffers (rt_render_f32 / rt_render_rgb8)
 DeviceScene.render         async on a caller stream into a device buffer (rt_render_device),
                            the path bench.py times with inputs resident in HBM
+render_aov / DeviceScene.render_aov   first-hit feature buffers for a denoiser or compositor
+                           (rt_render_aov / rt_render_aov_device)
 MultiContext               row tiles over ranks (devices), gathered to rank 0 (rt_multi_*)
 save_ppm                   app::save_to_file (src/main.cxx:87-101), rt_write_ppm
 """
@@ -113,6 +115,31 @@ def render_rgb8(scene, params, camera=None):
                                len(m), C.byref(_cam(camera, params)), C.byref(params),
                                abi.ptr(out, C.POINTER(C.c_uint8)), C.byref(st)))
     return out, st
+
+
+def aov_buffers(pointers, samples=0):
+    """An rt_aov_buffers record from a dict plane name -> address (absent or 0: not wanted)."""
+    unknown = set(pointers) - set(abi.AOV_PLANES)
+    if unknown:
+        raise KeyError(f"rt_aov_buffers has no plane {sorted(unknown)!r}")
+    return abi.RtAovBuffers(C.sizeof(abi.RtAovBuffers), samples, *(pointers.get(n) or None for n in abi.AOV_PLANES))
+
+
+def render_aov(scene, params, camera=None, samples=0, planes=tuple(abi.AOV_PLANES)):
+    """First-hit feature buffers (rt_render_aov) of samples 0..samples-1 (0: every
+    sample) of the pass `params` describes, as a dict plane name -> array: albedo and normal
+    float32 (rows, width, 3), depth and alpha float32 (rows, width), sphere_id uint32 (rows,
+    width). Full frame: rows the call does not render hold 0 (sphere_id: 0xffffffff)."""
+    s, m = _scene_arrays(scene)
+    rows, w = _out_rows(params), params.width
+    out = {n: np.full((rows, w, ch) if ch > 1 else (rows, w), fill, dtype=dt)
+           for n, (ch, dt, fill) in abi.AOV_PLANES.items() if n in planes}
+    if len(out) != len(set(planes)):
+        raise KeyError(f"unknown plane in {planes!r}")
+    rec = aov_buffers({n: a.ctypes.data for n, a in out.items()}, samples)
+    check(lib().rt_render_aov(abi.ptr(s, C.POINTER(abi.RtSphere)), len(s), abi.ptr(m, C.POINTER(abi.RtMaterial)),
+                              len(m), C.byref(_cam(camera, params)), C.byref(params), C.byref(rec), None))
+    return out
 
 
 def tile_order(scene, params, camera=None):
@@ -236,6 +263,14 @@ class DeviceScene:
         check(lib().rt_render_device(self.handle, C.byref(_cam(camera, params)), C.byref(params),
                                      C.c_void_p(d_rgb), C.c_void_p(stream or 0),
                                      C.c_void_p(d_segments) if d_segments else None))
+
+    def render_aov(self, camera, params, buffers, samples=0, stream=None):
+        """Enqueue the first-hit feature buffers (rt_render_aov_device) on `stream`: `buffers` is a
+        dict plane name (albedo, normal, depth, alpha, sphere_id) -> device address, laid out as
+        `params` says; samples 0..samples-1 of every pixel (0: all of params.spp)."""
+        rec = aov_buffers(buffers, samples)
+        check(lib().rt_render_aov_device(self.handle, C.byref(_cam(camera, params)), C.byref(params), C.byref(rec),
+                                         C.c_void_p(stream or 0)))
 
     def usage(self):
         """rt_scene_usage_get: device bytes held and the last render's cut, as a dict."""
