@@ -351,6 +351,88 @@ int rt_render_aov(const rt_sphere *spheres, uint32_t n_spheres, const rt_materia
                   uint32_t n_materials, const rt_camera *camera, const rt_params *params,
                   const rt_aov_buffers *aov, rt_stats *stats);
 
+/* ---- edge-avoiding à-trous denoiser over the feature buffers ----------
+ * The 5x5 B3-spline à-trous wavelet filter of Dammertz et al. 2010, guided by the planes of
+ * rt_render_aov, with a compact polynomial edge-stopping function in place of the Gaussian so
+ * that the result is reproducible bit for bit: all arithmetic is binary32, every operation
+ * rounded on its own (add, multiply, max, one division per pixel and channel; no exp or pow).
+ *
+ * Planes are packed row-major, width x height, pitch = width: beauty[h][w][3] (required),
+ * optional guides albedo[h][w][3], normal[h][w][3], depth[h][w] exactly as rt_render_aov writes
+ * them, output out[h][w][3].
+ *
+ * Edge function: edge(d2, r) = m * m with m = fmaxf(0.0f, 1.0f - d2 * r), r = 1.0f / (sigma *
+ * sigma) (one float product, one IEEE division, on the host). The colour term of level l uses
+ * sigma = sigma_color * 2^-l (exact).
+ *
+ * One level l, step s = 1 << l, input image C, output D. For pixel p = (x, y): sumw = 0,
+ * sum[3] = 0; the taps j = -2..2 (outer loop), i = -2..2 (inner loop), q = (x + i s, y + j s);
+ * a tap outside the image is skipped (nothing is added). w = h[|i|] * h[|j|] with h = {0.375f,
+ * 0.25f, 0.0625f}, then the terms that are on are multiplied into w in this order:
+ *   colour  d = C(q) - C(p) per channel, d2 = (d.r d.r + d.g d.g) + d.b d.b, w = w * edge(d2, r_c)
+ *   normal  the same d2 over the normal plane, with r_n
+ *   depth   dz = depth(q) - depth(p), d2 = dz dz, with r_z
+ *   albedo  the same d2 over the albedo plane, with r_a
+ * then sumw = sumw + w and sum[c] = sum[c] + w * C(q)[c] (a product, then a sum), and at the end
+ * D(p)[c] = sum[c] / sumw (IEEE division; sumw >= 9/64, the centre tap has d2 = 0). A term is on
+ * when its plane is given and its sigma is not 0 (colour: sigma_color not 0). The guides are
+ * never filtered: every level reads the caller's planes. Sky pixels have normal 0 and depth 0 on
+ * both sides, so d2 = 0 between them.
+ *
+ * Levels: C_0 = beauty, C_{l+1} = D_l; the last level writes `out`, the levels before it
+ * alternate between `scratch` and `out` so that this holds. beauty and the guides are never
+ * written.
+ *
+ * RT_DENOISE_DEMODULATE (needs albedo): A'(q)[c] = fmaxf(albedo(q)[c], 0.0078125f), C_0(q)[c] =
+ * beauty(q)[c] / A'(q)[c], and the last level stores (sum[c] / sumw) * A'(p)[c]. On a pixel whose
+ * samples all miss the albedo is the beauty pixel's own bits, so the sky demodulates to a constant.
+ *
+ * Every argument is checked before any HIP call; RT_ERR_INVALID names the field: a size
+ * mismatch, zero width or height (or one above 65536), levels outside 1..6, a negative or
+ * non-finite sigma, a zero sigma_normal or sigma_depth for a plane that is given, a sigma_color so
+ * small that 1 / sigma^2 is not finite at the last level, unknown flags, DEMODULATE without
+ * albedo, a null beauty or out, scratch null with levels > 1 (device call), out or scratch equal
+ * to an input or to each other. NaN or infinite pixel values give unspecified output.          */
+typedef struct rt_denoise_params {
+    uint32_t size;            /* sizeof(rt_denoise_params): the record's revision                */
+    uint32_t width, height;
+    uint32_t levels;          /* 1..6; level l taps at spacing 1 << l                            */
+    float sigma_color;        /* > 0; 0 = colour term off. Level l uses sigma_color * 2^-l       */
+    float sigma_normal;       /* used only with a normal plane; > 0                              */
+    float sigma_depth;        /* used only with a depth plane; > 0                               */
+    float sigma_albedo;       /* used only with an albedo plane; > 0; 0 = term off (the albedo
+                                 may still serve RT_DENOISE_DEMODULATE)                          */
+    uint32_t flags;           /* rt_denoise_flags                                                */
+} rt_denoise_params;
+enum rt_denoise_flags {
+    RT_DENOISE_DEMODULATE = 1u << 0,  /* filter beauty / albedo', multiply back at the end       */
+    RT_DENOISE_DIRECT = 1u << 1       /* A/B: every level by the direct-load kernel; same bits   */
+};
+typedef struct rt_denoise_buffers {
+    uint32_t size;            /* sizeof(rt_denoise_buffers)                                      */
+    const float *beauty, *albedo, *normal, *depth;
+    float *out;
+    float *scratch;           /* w*h*3 floats; may be NULL when levels == 1                      */
+} rt_denoise_buffers;
+/* The defaults (DESIGN.md §4.9 records the sweep that chose them) for a width x height image.   */
+int rt_denoise_params_default(uint32_t width, uint32_t height, rt_denoise_params *out);
+/* Device pointers on the current device; one launch per level on `stream` (a hipStream_t, or
+ * NULL), no host synchronisation, no allocation. Small steps take the tiled kernel (taps from
+ * LDS), the others the direct one; RT_DENOISE_DIRECT forces the direct one everywhere.          */
+int rt_denoise_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
+                      void *stream);
+/* Measurement (the A/B behind that choice): level `level` (< params->levels) of that run alone,
+ * reading buffers->beauty as the level's input C_level and writing buffers->out; scratch is not
+ * used. By the tiled kernel wherever its LDS image fits (steps 1, 2 and 4), whatever the library
+ * would choose for that level; by the direct one with RT_DENOISE_DIRECT. Same bits.           */
+int rt_denoise_level_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
+                            uint32_t level, void *stream);
+/* Host pointers, synchronous; scratch is ignored, the device buffers are the library's (kept in
+ * the cached per-device context rt_release_cached frees). stats (optional): kernel_ms, wall_ms;
+ * the counters are 0.                                                                           */
+int rt_denoise(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
+               rt_stats *stats);
+
 /* Device memory a scene holds and how its renders are cut (after the last render call).  */
 typedef struct rt_scene_usage {
     uint64_t device_bytes;     /* every device allocation of the scene                       */

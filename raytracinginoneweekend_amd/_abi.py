@@ -27,6 +27,9 @@ RT_FLAG_BRUTE_FORCE = 1 << 3
 RT_FLAG_CUDA_COMPAT = 1 << 4  # semantics of src/CUDA/cuda_impl.cu
 RT_FLAG_WAVEFRONT = 1 << 5  # A/B: per-segment launches with HBM ray queues (same bits)
 
+RT_DENOISE_DEMODULATE = 1 << 0  # filter beauty / albedo', multiply back at the end
+RT_DENOISE_DIRECT = 1 << 1  # A/B: every level by the direct-load kernel (same bits)
+
 
 class RtSphere(C.Structure):
     _fields_ = [("center", C.c_float * 3), ("radius", C.c_float), ("material", C.c_uint32)]
@@ -102,6 +105,27 @@ class RtAovBuffers(C.Structure):
     ]
 
 
+class RtDenoiseParams(C.Structure):
+    """rt_denoise_params (include/rt_api.h): the à-trous denoiser's image size, levels and sigmas."""
+    _fields_ = [
+        ("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("levels", C.c_uint32),
+        ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+        ("sigma_albedo", C.c_float), ("flags", C.c_uint32),
+    ]
+
+
+class RtDenoiseBuffers(C.Structure):
+    """rt_denoise_buffers (include/rt_api.h): the planes of a denoise call, NULL = guide not given."""
+    _fields_ = [
+        ("size", C.c_uint32),
+        ("beauty", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p),
+        ("out", C.c_void_p), ("scratch", C.c_void_p),
+    ]
+
+
+# the planes of rt_denoise_buffers: name -> channels
+DENOISE_PLANES = {"beauty": 3, "albedo": 3, "normal": 3, "depth": 1, "out": 3, "scratch": 3}
+
 # the planes of rt_aov_buffers: name -> (channels, numpy dtype, value of a pixel no call wrote)
 AOV_PLANES = {"albedo": (3, np.float32, 0), "normal": (3, np.float32, 0), "depth": (1, np.float32, 0),
               "alpha": (1, np.float32, 0), "sphere_id": (1, np.uint32, 0xffffffff)}
@@ -113,6 +137,7 @@ assert MATERIAL_DTYPE.itemsize == C.sizeof(RtMaterial) == 20
 assert C.sizeof(RtParams) == 40
 assert C.sizeof(RtOptions) == 64 and C.sizeof(RtSceneUsage) == 56
 assert C.sizeof(RtAovBuffers) == 48
+assert C.sizeof(RtDenoiseParams) == 36 and C.sizeof(RtDenoiseBuffers) == 56
 
 
 def ptr(arr, ctype=C.c_void_p):

@@ -75,6 +75,11 @@ def _declare(L):
                                            C.c_void_p]),
         "rt_render_aov": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, P(abi.RtCamera),
                                     P(abi.RtParams), P(abi.RtAovBuffers), P(abi.RtStats)]),
+        "rt_denoise_params_default": (C.c_int, [C.c_uint32, C.c_uint32, P(abi.RtDenoiseParams)]),
+        "rt_denoise_device": (C.c_int, [P(abi.RtDenoiseParams), P(abi.RtDenoiseBuffers), C.c_void_p]),
+        "rt_denoise_level_device": (C.c_int, [P(abi.RtDenoiseParams), P(abi.RtDenoiseBuffers), C.c_uint32,
+                                              C.c_void_p]),
+        "rt_denoise": (C.c_int, [P(abi.RtDenoiseParams), P(abi.RtDenoiseBuffers), P(abi.RtStats)]),
         "rt_scene_kernel_times": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float), P(C.c_uint32)]),
         "rt_scene_debug_counters": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_int]),
         "rt_scene_debug_timeline": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_uint32, P(C.c_uint32)]),

@@ -244,6 +244,17 @@ struct KAov {
     uint32_t *sphere_id;
 };
 
+// One level of the à-trous denoiser (rt_denoise.hip): `in` is the level's input
+// C (level 0: the beauty, divided by A' on load when the run demodulates), the guides are the
+// caller's planes (null when their term is off; albedo also serves the demodulation).
+struct KDenoise {
+    const float *in, *albedo, *normal, *depth;
+    float *out;
+    uint32_t W, H, step;        // step = 1 << level
+    float r_c, r_n, r_z, r_a;   // 1 / sigma^2 of each term, computed on the host
+    uint32_t demod_out;         // the run's last level: the result times A'(p)
+};
+
 // The wavefront variant's ray queue (structure of arrays, capacity cap rays): f = [9][cap]
 // floats {o.xyz, d.xyz, attenuation.xyz}, then the data-stream state, the item index (slot) and
 // the segment count of each ray; count = rays in the queue.

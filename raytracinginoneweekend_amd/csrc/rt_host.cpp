@@ -48,6 +48,9 @@ hipError_t launch_sky(const KSky &k, hipStream_t stream);
 hipError_t launch_aov(int cull, const KAov &k, uint32_t grid, hipStream_t stream);
 hipError_t occupancy_aov(int cull, int *blocks_per_cu, size_t lds);
 hipError_t static_lds_aov(int cull, size_t *bytes);
+// rt_denoise.hip
+hipError_t launch_denoise(const KDenoise &k, uint32_t terms, bool demod_in, bool tiled, hipStream_t stream);
+size_t denoise_tiled_lds(uint32_t terms, uint32_t step);
 } // namespace rt
 
 namespace {
@@ -1637,6 +1640,8 @@ struct SyncContext {
     uint64_t *d_seg = nullptr;
     void *d_aov = nullptr;  // rt_render_aov: the requested planes, one after the other
     size_t aov_bytes = 0;
+    void *d_dn = nullptr;   // rt_denoise: the inputs, out and scratch, one after the other
+    size_t dn_bytes = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 std::mutex g_sync_mu;  // one synchronous render at a time per process (the reference's entry is not re-entrant)
@@ -1648,7 +1653,7 @@ void sync_release(int dev, SyncContext &c)
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(dev);
     if (c.sc) rt_scene_destroy(c.sc);
-    for (void *p : {(void *)c.d_rgb, (void *)c.d_u8, (void *)c.d_seg, c.d_aov})
+    for (void *p : {(void *)c.d_rgb, (void *)c.d_u8, (void *)c.d_seg, c.d_aov, c.d_dn})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : {c.e0, c.e1})
         if (e) (void)hipEventDestroy(e);
@@ -1831,9 +1836,192 @@ int render_aov_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_mater
     return rc;
 }
 
+
+// ---- the à-trous denoiser (include/rt_api.h; kernels in rt_denoise.hip) ----------------------
+// Levels with a step up to this take the tiled kernel: at 1280x720 with every guide it takes 0.77
+// of the direct kernel's time at steps 1 and 2 and 1.03 at step 4, where its halo is as large as
+// its tile (profiles/denoise/time_c3.txt). Its LDS image at step 2 is 37.5 KiB.
+constexpr uint32_t kDenoiseTiledMaxStep = 2;
+// The largest step the tiled kernel can take at all (rt_denoise_level_device's A/B): its LDS image
+// with every guide is then 60 KiB, the most a launch gets without asking for more.
+constexpr uint32_t kDenoiseTiledFits = 4;
+constexpr uint32_t kDenoiseMaxSide = 65536;
+
+// Every argument check of the denoiser, before any HIP call (use_scratch: the call uses
+// buffers.scratch). terms: the edge terms that are on.
+int check_denoise(const rt_denoise_params *p, const rt_denoise_buffers *b, bool use_scratch, const char *who,
+                  uint32_t *terms)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!p || !b) return fail(RT_ERR_INVALID, w + "null argument");
+    if (p->size != sizeof(rt_denoise_params)) return fail(RT_ERR_INVALID, w + "params.size is not sizeof(rt_denoise_params)");
+    if (b->size != sizeof(rt_denoise_buffers)) return fail(RT_ERR_INVALID, w + "buffers.size is not sizeof(rt_denoise_buffers)");
+    if (!p->width || p->width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
+    if (!p->height || p->height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    if (p->levels < 1u || p->levels > 6u) return fail(RT_ERR_INVALID, w + "levels must be 1..6");
+    const struct { const char *name; float v; } sig[4] = {{"sigma_color", p->sigma_color}, {"sigma_normal", p->sigma_normal},
+                                                          {"sigma_depth", p->sigma_depth}, {"sigma_albedo", p->sigma_albedo}};
+    for (const auto &s : sig)
+        if (!std::isfinite(s.v) || s.v < 0.f) return fail(RT_ERR_INVALID, w + s.name + " must be finite and not negative");
+    if (p->flags & ~static_cast<uint32_t>(RT_DENOISE_DEMODULATE | RT_DENOISE_DIRECT))
+        return fail(RT_ERR_INVALID, w + "unknown bits in flags");
+    if (!b->beauty) return fail(RT_ERR_INVALID, w + "beauty is null");
+    if (!b->out) return fail(RT_ERR_INVALID, w + "out is null");
+    if (b->normal && p->sigma_normal == 0.f) return fail(RT_ERR_INVALID, w + "sigma_normal is 0 with a normal plane");
+    if (b->depth && p->sigma_depth == 0.f) return fail(RT_ERR_INVALID, w + "sigma_depth is 0 with a depth plane");
+    if ((p->flags & RT_DENOISE_DEMODULATE) && !b->albedo)
+        return fail(RT_ERR_INVALID, w + "RT_DENOISE_DEMODULATE needs the albedo plane");
+    if (p->sigma_color != 0.f) {
+        const float s = p->sigma_color * std::ldexp(1.f, -static_cast<int>(p->levels - 1u));
+        if (!std::isfinite(1.0f / (s * s))) return fail(RT_ERR_INVALID, w + "sigma_color is too small for this many levels");
+    }
+    for (const auto &s : {sig[1], sig[2], sig[3]})
+        if (s.v != 0.f && !std::isfinite(1.0f / (s.v * s.v))) return fail(RT_ERR_INVALID, w + s.name + " is too small");
+    const bool need_scratch = use_scratch && p->levels > 1u;
+    if (need_scratch && !b->scratch) return fail(RT_ERR_INVALID, w + "scratch is null with levels > 1");
+    const float *const scratch = use_scratch ? b->scratch : nullptr;
+    for (const float *in : {b->beauty, b->albedo, b->normal, b->depth}) {
+        if (in && in == b->out) return fail(RT_ERR_INVALID, w + "out is also an input plane");
+        if (in && in == scratch) return fail(RT_ERR_INVALID, w + "scratch is also an input plane");
+    }
+    if (scratch && scratch == b->out) return fail(RT_ERR_INVALID, w + "scratch is also out");
+    *terms = (p->sigma_color != 0.f ? 1u : 0u) | (b->normal ? 2u : 0u) | (b->depth ? 4u : 0u) |
+             (b->albedo && p->sigma_albedo != 0.f ? 8u : 0u);
+    return RT_OK;
+}
+
+float denoise_r(float sigma) { return 1.0f / (sigma * sigma); }
+
+// Enqueue levels [first, last] of the run `p` describes: level l reads `in` when l == first and
+// the previous level's output otherwise; the last one writes b.out, those before it alternate
+// between b.scratch and b.out so that it does. Steps up to tiled_max_step take the tiled kernel.
+int denoise_levels(const rt_denoise_params &p, const rt_denoise_buffers &b, uint32_t terms, uint32_t first,
+                   uint32_t last, uint32_t tiled_max_step, hipStream_t stream)
+{
+    const bool demod = (p.flags & RT_DENOISE_DEMODULATE) != 0u;
+    rt::KDenoise k{};
+    k.albedo = (terms & 8u) || demod ? b.albedo : nullptr;
+    k.normal = b.normal;
+    k.depth = b.depth;
+    k.W = p.width;
+    k.H = p.height;
+    k.r_n = (terms & 2u) ? denoise_r(p.sigma_normal) : 0.f;
+    k.r_z = (terms & 4u) ? denoise_r(p.sigma_depth) : 0.f;
+    k.r_a = (terms & 8u) ? denoise_r(p.sigma_albedo) : 0.f;
+    const float *in = b.beauty;
+    for (uint32_t l = first; l <= last; ++l) {
+        k.in = in;
+        k.out = ((last - l) & 1u) ? b.scratch : b.out;
+        k.step = 1u << l;
+        k.r_c = (terms & 1u) ? denoise_r(p.sigma_color * std::ldexp(1.f, -static_cast<int>(l))) : 0.f;
+        k.demod_out = demod && l + 1u == p.levels;
+        const bool tiled = !(p.flags & RT_DENOISE_DIRECT) && k.step <= tiled_max_step;
+        RT_HIP(rt::launch_denoise(k, terms, demod && l == 0u, tiled, stream));
+        in = k.out;
+    }
+    return RT_OK;
+}
+
+// Synchronous denoise of host planes through the cached per-device context's buffer.
+int denoise_host(const rt_denoise_params *params, const rt_denoise_buffers *buffers, rt_stats *stats)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise(params, buffers, false, "rt_denoise", &terms); rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    int dev = 0;
+    RT_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_sync_mu);
+    SyncContext &cx = g_sync[dev];
+    const rt_denoise_params &P = *params;
+    const size_t n = static_cast<size_t>(P.width) * P.height;
+    // beauty, albedo, normal, depth, out, scratch packed into the context's buffer (256-byte aligned)
+    struct Plane { const float *host; uint32_t channels; size_t at; };
+    Plane planes[6] = {{buffers->beauty, 3, 0}, {buffers->albedo, 3, 0}, {buffers->normal, 3, 0},
+                       {buffers->depth, 1, 0},  {buffers->out, 3, 0},    {P.levels > 1u ? buffers->out : nullptr, 3, 0}};
+    size_t total = 0;
+    for (Plane &pl : planes)
+        if (pl.host) {
+            pl.at = total;
+            total += (n * pl.channels * 4u + 255u) & ~static_cast<size_t>(255u);
+        }
+    int rc = RT_OK;
+    auto chk = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+        return rc == RT_OK;
+    };
+    if (cx.dn_bytes < total || !cx.d_dn) {
+        if (cx.d_dn) chk(hipFree(cx.d_dn), "hipFree");
+        cx.d_dn = nullptr;
+        cx.dn_bytes = 0;
+        if (chk(hipMalloc(&cx.d_dn, std::max<size_t>(total, 256)), "hipMalloc")) cx.dn_bytes = total;
+    }
+    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
+    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
+    float ms = 0.f;
+    if (rc == RT_OK) {
+        char *base = static_cast<char *>(cx.d_dn);
+        auto dptr = [&](const Plane &pl) { return pl.host ? reinterpret_cast<float *>(base + pl.at) : nullptr; };
+        for (int i = 0; i < 4; ++i)
+            if (rc == RT_OK && planes[i].host)
+                chk(hipMemcpy(dptr(planes[i]), planes[i].host, n * planes[i].channels * 4u, hipMemcpyHostToDevice), "hipMemcpy");
+        rt_denoise_buffers d{static_cast<uint32_t>(sizeof(rt_denoise_buffers)), dptr(planes[0]), dptr(planes[1]),
+                             dptr(planes[2]), dptr(planes[3]), dptr(planes[4]), dptr(planes[5])};
+        if (rc == RT_OK) chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
+        if (rc == RT_OK) rc = denoise_levels(P, d, terms, 0, P.levels - 1u, kDenoiseTiledMaxStep, nullptr);
+        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
+        // the copy on the null stream follows the kernels
+        if (rc == RT_OK) chk(hipMemcpy(buffers->out, d.out, n * 12u, hipMemcpyDeviceToHost), "hipMemcpy");
+        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_denoise");
+        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
+    }
+    if (rc != RT_OK) {
+        // a failed call leaves no state behind: the next one starts from a new context
+        const std::string msg = g_error;
+        sync_release(dev, cx);
+        g_error = msg;
+    }
+    if (rc == RT_OK && stats) {
+        *stats = rt_stats{};
+        stats->kernel_ms = ms;
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
+
+int rt_denoise_params_default(uint32_t width, uint32_t height, rt_denoise_params *out)
+{
+    if (!out) return fail(RT_ERR_INVALID, "rt_denoise_params_default: null argument");
+    if (!width || !height) return fail(RT_ERR_INVALID, "rt_denoise_params_default: zero width or height");
+    // chosen by the CPU sweep of DESIGN.md §4.9
+    *out = rt_denoise_params{static_cast<uint32_t>(sizeof(rt_denoise_params)), width, height, 2u, 4.0f, 2.0f, 1.0f, 1.0f, 0u};
+    return RT_OK;
+}
+
+int rt_denoise_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers, void *stream)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise(params, buffers, true, "rt_denoise_device", &terms); rc != RT_OK) return rc;
+    return denoise_levels(*params, *buffers, terms, 0, params->levels - 1u, kDenoiseTiledMaxStep,
+                          static_cast<hipStream_t>(stream));
+}
+
+int rt_denoise_level_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers, uint32_t level,
+                            void *stream)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise(params, buffers, false, "rt_denoise_level_device", &terms); rc != RT_OK) return rc;
+    if (level >= params->levels) return fail(RT_ERR_INVALID, "rt_denoise_level_device: level is not below levels");
+    return denoise_levels(*params, *buffers, terms, level, level, kDenoiseTiledFits, static_cast<hipStream_t>(stream));
+}
+
+int rt_denoise(const rt_denoise_params *params, const rt_denoise_buffers *buffers, rt_stats *stats)
+{
+    return denoise_host(params, buffers, stats);
+}
 
 int rt_render_aov(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
                   const rt_camera *camera, const rt_params *params, const rt_aov_buffers *aov, rt_stats *stats)

@@ -5,6 +5,8 @@ DeviceScene.render         async on a caller stream into a device buffer (rt_ren
                            the path bench.py times with inputs resident in HBM
 render_aov / DeviceScene.render_aov   first-hit feature buffers for a denoiser or compositor
                            (rt_render_aov / rt_render_aov_device)
+denoise / denoise_device   the edge-avoiding à-trous denoiser over those buffers (rt_denoise /
+                           rt_denoise_device)
 MultiContext               row tiles over ranks (devices), gathered to rank 0 (rt_multi_*)
 save_ppm                   app::save_to_file (src/main.cxx:87-101), rt_write_ppm
 """
@@ -140,6 +142,69 @@ def render_aov(scene, params, camera=None, samples=0, planes=tuple(abi.AOV_PLANE
     check(lib().rt_render_aov(abi.ptr(s, C.POINTER(abi.RtSphere)), len(s), abi.ptr(m, C.POINTER(abi.RtMaterial)),
                               len(m), C.byref(_cam(camera, params)), C.byref(params), C.byref(rec), None))
     return out
+
+
+def denoise_params(width, height, base=None, demodulate=None, direct=None, **fields):
+    """An rt_denoise_params record: the library defaults for the image (or a copy of `base`) with
+    `fields` set (levels, sigma_color, sigma_normal, sigma_depth, sigma_albedo, flags);
+    demodulate / direct set or clear RT_DENOISE_DEMODULATE / RT_DENOISE_DIRECT."""
+    p = abi.RtDenoiseParams()
+    if base is None:
+        check(lib().rt_denoise_params_default(width, height, C.byref(p)))
+    else:
+        C.memmove(C.byref(p), C.byref(base), C.sizeof(p))
+        p.width, p.height = width, height
+    names = dict(abi.RtDenoiseParams._fields_)
+    for k, v in fields.items():
+        if k not in names or k in ("size", "width", "height"):
+            raise KeyError(f"rt_denoise_params has no field {k!r}")
+        setattr(p, k, v)
+    for bit, on in ((abi.RT_DENOISE_DEMODULATE, demodulate), (abi.RT_DENOISE_DIRECT, direct)):
+        if on is not None:
+            p.flags = (p.flags | bit) if on else (p.flags & ~bit)
+    return p
+
+
+def denoise_buffers(pointers):
+    """An rt_denoise_buffers record from a dict plane name (beauty, albedo, normal, depth, out,
+    scratch) -> address (absent or 0: not given)."""
+    unknown = set(pointers) - set(abi.DENOISE_PLANES)
+    if unknown:
+        raise KeyError(f"rt_denoise_buffers has no plane {sorted(unknown)!r}")
+    return abi.RtDenoiseBuffers(C.sizeof(abi.RtDenoiseBuffers), *(pointers.get(n) or None for n in abi.DENOISE_PLANES))
+
+
+def denoise(beauty, albedo=None, normal=None, depth=None, params=None, stats=None, **fields):
+    """rt_denoise: the à-trous filter of a float32 (h, w, 3) beauty image guided by
+    the planes of render_aov that are given (albedo and normal (h, w, 3), depth (h, w)); returns
+    float32 (h, w, 3). params: an rt_denoise_params record (default: the library's for this size);
+    `fields` as denoise_params takes them. stats: an optional RtStats to fill."""
+    planes = {"beauty": beauty, "albedo": albedo, "normal": normal, "depth": depth}
+    if beauty is None or np.ndim(beauty) != 3 or np.shape(beauty)[2] != 3:
+        raise ValueError(f"beauty must be float32 (h, w, 3), not {np.shape(beauty)}")
+    h, w = np.shape(beauty)[:2]
+    host = {}
+    for n, a in planes.items():
+        if a is None:
+            continue
+        want = (h, w, 3) if abi.DENOISE_PLANES[n] == 3 else (h, w)
+        a = np.asarray(a)
+        if a.dtype != np.float32 or a.shape != want:
+            raise ValueError(f"{n} must be float32 {want}, not {a.dtype} {a.shape}")
+        host[n] = np.ascontiguousarray(a)
+    p = denoise_params(w, h, base=params, **fields)
+    out = np.zeros((h, w, 3), dtype=np.float32)
+    rec = denoise_buffers({**{n: a.ctypes.data for n, a in host.items()}, "out": out.ctypes.data})
+    check(lib().rt_denoise(C.byref(p), C.byref(rec), C.byref(stats) if stats is not None else None))
+    return out
+
+
+def denoise_device(pointers, params, stream=None):
+    """Enqueue rt_denoise_device on `stream`: `pointers` is a dict plane name (beauty, albedo,
+    normal, depth, out, scratch) -> device address on the current device, `params` an
+    rt_denoise_params record (denoise_params). One launch per level, no host synchronisation."""
+    rec = denoise_buffers(pointers)
+    check(lib().rt_denoise_device(C.byref(params), C.byref(rec), C.c_void_p(stream or 0)))
 
 
 def tile_order(scene, params, camera=None):
