@@ -196,8 +196,11 @@ enum rt_diag {
                                           the main launch (traced) instead of the sky kernel   */
     RT_DIAG_LONE_UNSPLIT = 1u << 16,    /* a lone pass dealt by tile classes is not split (its
                                           trapped paths start in its first items)              */
-    RT_DIAG_SKY_SERIAL = 1u << 17       /* a lone pass's sky kernel after its main and deep
+    RT_DIAG_SKY_SERIAL = 1u << 17,      /* a lone pass's sky kernel after its main and deep
                                           launches on their stream (not beside them)           */
+    /* (bit 18 is unassigned and rejected)                                                      */
+    RT_DIAG_NO_TRAP_END = 1u << 19      /* every trap window empty: paths trapped in isolated
+                                          glass balls are traced to max_depth (same bits)      */
 };
 int rt_options_default(rt_options *out);
 /* Applies "key=value[,key=value...]" (fields above; diag bits as ieee_roots, no_shortcut,
@@ -241,6 +244,13 @@ int rt_scene_huge(uint32_t seed, rt_sphere *spheres, uint32_t sphere_cap, uint32
 int rt_tile_order(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
                   uint32_t n_materials, const rt_camera *camera, const rt_params *params,
                   uint32_t *perm, uint32_t cap, uint32_t *n_blocks, uint32_t *n_lead, uint32_t *n_sky);
+
+/* The trap windows of a scene's spheres: out[2 i], out[2 i + 1] = sphere i's
+ * {cos_lo, cos_hi}. A path that reflects totally inside sphere i with its cosine in the window
+ * is proven to stay in that ball until max_depth (<= 64) and is ended there with colour 0; {1, 0}
+ * = no window (not an isolated glass ball, or the margins leave none). Host-only.              */
+int rt_trap_windows(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
+                    uint32_t n_materials, float *out);
 
 /* ---- synchronous host-buffer renders (the cuda_impl replacement) ------------------- */
 /* These keep one device context per device between calls (the scene on the device, its

@@ -45,6 +45,7 @@ def _declare(L):
         "rt_tile_order": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, P(abi.RtCamera),
                                     P(abi.RtParams), P(C.c_uint32), C.c_uint32, P(C.c_uint32), P(C.c_uint32),
                                     P(C.c_uint32)]),
+        "rt_trap_windows": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, P(C.c_float)]),
         "rt_render_f32": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32,
                                     P(abi.RtCamera), P(abi.RtParams), P(C.c_float), P(abi.RtStats)]),
         "rt_render_rgb8": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32,

@@ -19,6 +19,14 @@ constexpr float kIsoR2Grow = 1.0201f;
 // a dielectric sphere's shortcut word (rt_host.cpp shortcut_words): this bit, then the geo slots
 // (+ 1, 0 = none) of its at most two neighbours in bits [0, 15) and [15, 30)
 constexpr uint32_t kShortcut = 0x80000000u;
+// Trap windows (rt_host_build.cpp trap_windows): a path that reflects totally
+// inside an isolated glass ball with its cosine in the ball's window stays there until max_depth
+// and returns 0, so the kernels end it at once. The windows hold for renders of at most
+// kTrapDepth segments per path; the drift margin is kTrapDriftK kTrapDepth 2^-23 (|C|_inf + r) / kMIN,
+// kTrapDriftK at least 8 x the largest drift tests/tools/trap_census.cpp measures in those units
+// (0.114 on config 3's frames; tests/test_trap_cpu.py asserts it).
+constexpr uint32_t kTrapDepth = 64;
+constexpr double kTrapDriftK = 1.0;
 // clusters under one level-2 box (the walk tests a passing box's clusters in pairs). 8: config 3
 // frame period 2.548-2.562 vs 2.578-2.596 ms with 4, 6 alike with 4, 12 and 16 slower, 2 +5%
 // (profiles/r05/ab/super_clusters.txt)

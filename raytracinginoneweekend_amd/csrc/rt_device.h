@@ -118,6 +118,9 @@ struct KParams {
     uint32_t shade_offset;
     uint32_t lds_units;      // blob units staged in LDS: all of it, or the part before shade_offset
     uint32_t shade_lds;      // 1: shading records read from LDS, 0: from the global blob
+    // trap windows {cos_lo, cos_hi} by original sphere index (rt_host_build.cpp trap_windows;
+    // global memory: read on the total-reflection branch only), {1, 0} = none
+    const float2 *trap;
     // outputs / workspace
     float *slots;            // [sample_end - sample_begin][n_pixels][3]
     uint32_t *queue_ctr;     // [8 x kQueueStride]: one counter per 256-B line

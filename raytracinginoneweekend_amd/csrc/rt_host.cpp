@@ -147,6 +147,9 @@ struct rt_scene {
     float clus_pad[2] = {0.f, 0.f};
     uint32_t n_supers[2] = {0, 0}, supers_offset[2] = {0, 0};
     uint32_t shade_offset[2] = {0, 0};
+    // trap windows (rt_host_build.cpp trap_windows): {cos_lo, cos_hi} per sphere, then as many
+    // empty windows (for renders deeper than rt::kTrapDepth); all empty under RT_DIAG_NO_TRAP_END
+    float *trap = nullptr;
     bool in_fast_range = false;  // every sphere within 2^19 of the origin, radii >= 2^-40 (short exact forms)
     // workspaces: consecutive render passes (of one frame or of consecutive frames) rotate over
     // internal streams xs[b] and workspaces slots[b], so a pass renders while the caller stream
@@ -445,7 +448,7 @@ int rt_scene_destroy(rt_scene *sc)
     }
     if (sc->ev_tail) (void)hipEventDestroy(sc->ev_tail);
     if (sc->ev_sky) (void)hipEventDestroy(sc->ev_sky);
-    for (void *p : {(void *)sc->blob[0], (void *)sc->blob[1], (void *)sc->dbg, (void *)sc->acc, (void *)sc->queue_ctr, sc->wq})
+    for (void *p : {(void *)sc->blob[0], (void *)sc->blob[1], (void *)sc->dbg, (void *)sc->acc, (void *)sc->queue_ctr, sc->wq, (void *)sc->trap})
         if (p) (void)hipFree(p);
     for (float *p : sc->slots)
         if (p) (void)hipFree(p);
@@ -565,6 +568,18 @@ int rt_scene_create_ex(const rt_sphere *spheres, uint32_t n_spheres, const rt_ma
         sc->n_supers[b] = blobs[b].n_supers;
         sc->supers_offset[b] = blobs[b].supers_offset;
         sc->shade_offset[b] = blobs[b].shade_offset;
+    }
+    if (rc == RT_OK) {
+        // the windows, then the empty set; a scene without spheres keeps one empty window
+        std::vector<float> trap = trap_windows(spheres, n_spheres, materials);
+        const size_t nw = std::max<size_t>(n_spheres, 1u);
+        trap.resize(4 * nw);
+        for (size_t i = (opt.diag & RT_DIAG_NO_TRAP_END) ? 0 : nw; i < 2 * nw; ++i) {
+            trap[2 * i] = 1.f;
+            trap[2 * i + 1] = 0.f;
+        }
+        if (n_spheres == 0) { trap[0] = 1.f; trap[1] = 0.f; }
+        rc = up((void **)&sc->trap, trap.data(), trap.size() * sizeof(float));
     }
     if (rc == RT_OK) {
         hipError_t e = hipMalloc((void **)&sc->queue_ctr, kCtrWords * sizeof(uint32_t));
@@ -810,6 +825,9 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     k.diag_unbounded_nb = (O.diag & RT_DIAG_UNBOUNDED_NB) ? 1u : 0u;
     k.fast_roots = sc->in_fast_range && camera_in_fast_range(*camera) && !(O.diag & RT_DIAG_IEEE_ROOTS) ? 1u : 0u;
     k.shade_offset = sc->shade_offset[b];
+    // the windows hold for paths of at most rt::kTrapDepth segments: deeper renders get the empty set
+    k.trap = reinterpret_cast<const float2 *>(sc->trap) +
+             (P.max_depth > rt::kTrapDepth ? std::max<size_t>(sc->n_spheres, 1u) : 0u);
     // the shading records (the blob's tail) join the geometry in LDS unless that costs
     // workgroups per CU; RT_DIAG_SHADE_LDS / RT_DIAG_SHADE_GLOBAL force the choice (same bits)
     auto occ_for = [&](int in_lds, int *out) -> int {
@@ -1546,6 +1564,7 @@ int rt_scene_usage_get(const rt_scene *sc, rt_scene_usage *out)
     for (uint32_t w = 0; w < kMaxWs; ++w) ws += sc->slots_bytes[w] + sc->deep_bytes[w];
     uint64_t fixed = kCtrWords * sizeof(uint32_t) + (sc->dbg ? rt::kDbgWords * sizeof(unsigned long long) : 0u);
     for (int b = 0; b < 2; ++b) fixed += static_cast<uint64_t>(sc->blob_units[b]) * 16u;
+    fixed += static_cast<uint64_t>(std::max(sc->n_spheres, 1u)) * 16u;  // the trap windows
     u.device_bytes = ws + fixed;
     u.workspace_bytes = ws;
     u.render_streams = sc->used_streams;

@@ -90,7 +90,8 @@ int check_options(const rt_options &o)
     if (o.cluster_size < 4 || o.cluster_size > 64 || o.cluster_size % 4) return bad("cluster_size (4..64, multiple of 4)");
     if (o.transpose_max > 16) return bad("transpose_max (0..16)");
     if (o.wave_queue_rays < 64) return bad("wave_queue_rays (>= 64)");
-    if (o.diag & ~((RT_DIAG_SKY_SERIAL << 1) - 1u)) return bad("diag (unknown bit)");
+    // (bit 18 is unassigned: it stays the unknown bit the option tests reject)
+    if (o.diag & ~(((RT_DIAG_SKY_SERIAL << 1) - 1u) | RT_DIAG_NO_TRAP_END)) return bad("diag (unknown bit)");
     if ((o.diag & RT_DIAG_SHADE_LDS) && (o.diag & RT_DIAG_SHADE_GLOBAL)) return bad("diag (shade_lds with shade_global)");
     return RT_OK;
 }
@@ -105,7 +106,7 @@ int parse_options(const char *text, rt_options &o)
         {"standin_transport", RT_DIAG_STANDIN_TRANSPORT}, {"unbounded_nb", RT_DIAG_UNBOUNDED_NB},
         {"no_pairs", RT_DIAG_NO_PAIRS}, {"pairs", RT_DIAG_PAIRS}, {"in_flight", RT_DIAG_IN_FLIGHT},
         {"natural_order", RT_DIAG_NATURAL_ORDER}, {"no_sky", RT_DIAG_NO_SKY}, {"lone_unsplit", RT_DIAG_LONE_UNSPLIT},
-        {"sky_serial", RT_DIAG_SKY_SERIAL}};
+        {"sky_serial", RT_DIAG_SKY_SERIAL}, {"no_trap_end", RT_DIAG_NO_TRAP_END}};
     rt_options n = o;
     std::string all(text ? text : "");
     for (char &c : all)
@@ -633,6 +634,71 @@ std::vector<uint32_t> shortcut_words(const rt_sphere *s, uint32_t n, const rt_ma
     return word;
 }
 
+// Trap windows (rt_kernel.hip's dielectric shading). A path that hits a glass
+// ball S from inside on the total-reflection branch with cosine c is reflected with probability 1
+// (raytracer.hxx:187-189: length(NaN) > 0 is false), and in exact arithmetic every later hit is
+// again S's far root from inside at the same cosine. S gets a window [cos_lo, cos_hi] such that a
+// path whose cosine lies in it provably repeats that until its depth runs out, where it returns 0
+// (main.cxx:74): the kernels end it at once. Per sphere:
+//   material dielectric with ior > 1, radius positive and finite, centre finite;
+//   isolation: the closed ball B(C, R), R^2 = r^2 kIsoR2Grow, meets no other sphere's surface
+//     (| |C_T - C| - |r_T| | > R for every other sphere T, the always-tested ones included): a
+//     chord of S lies in S (convex), so no other sphere has a root on it; spheres that contain S
+//     whole have their far root beyond S's; duplicates, bubbles and cutting shells disqualify S;
+//   the drift margin m = kTrapDriftK kTrapDepth 2^-23 (|C|_inf + r) / kMIN: per bounce the hit
+//     point is off by a few ulp of |C|_inf + r, which turns the cosine by that over the chord's
+//     length (>= kMIN); at least 8 x the largest drift of the cosine measured along trapped runs
+//     (tests/tools/trap_census.cpp);
+//   cos_hi = sqrt(1 - 1 / ior^2) - m: k = 1 - ior^2 (1 - d^2) < 0 (math.hxx:300-309) for every
+//     cosine within m above it;
+//   cos_lo = kMIN (1 + 1e-3) / (2 r) + m: the far root 2 r cos / |d| of a near-unit direction stays
+//     above kMIN = 0.008 (raytracer.hxx:98) for every cosine within m below it; the near root
+//     (the hit point itself, |t| ~ 1e-5) stays far below kMIN.
+// Both ends are rounded inward to binary32. An empty window is {1, 0}.
+std::vector<float> trap_windows(const rt_sphere *s, uint32_t n, const rt_material *m)
+{
+    std::vector<float> win(2 * static_cast<size_t>(n));
+    for (uint32_t i = 0; i < n; ++i) {
+        win[2 * i] = 1.f;
+        win[2 * i + 1] = 0.f;
+    }
+    size_t n_diel = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (m[s[i].material].kind == RT_DIELECTRIC) ++n_diel;
+    if (static_cast<double>(n_diel) * static_cast<double>(n) > 4e8) return win;  // leave huge scenes alone
+    for (uint32_t S = 0; S < n; ++S) {
+        const rt_material &mt = m[s[S].material];
+        if (mt.kind != RT_DIELECTRIC) continue;
+        const double ior = mt.param, r = s[S].radius;
+        const double C[3] = {s[S].center[0], s[S].center[1], s[S].center[2]};
+        if (!(ior > 1.0) || !std::isfinite(ior) || !(r > 0.0) || !std::isfinite(r)) continue;
+        if (!std::isfinite(C[0]) || !std::isfinite(C[1]) || !std::isfinite(C[2])) continue;
+        const double R = r * std::sqrt(static_cast<double>(rt::kIsoR2Grow));
+        bool isolated = true;
+        for (uint32_t T = 0; T < n && isolated; ++T) {
+            if (T == S) continue;
+            const double rT = std::fabs(static_cast<double>(s[T].radius));
+            const double dx = s[T].center[0] - C[0], dy = s[T].center[1] - C[1], dz = s[T].center[2] - C[2];
+            const double dist = std::sqrt(dx * dx + dy * dy + dz * dz);
+            // (NaN compares false: a sphere with a non-finite record disqualifies S)
+            if (!(std::fabs(dist - rT) > R * (1.0 + 1e-9))) isolated = false;
+        }
+        if (!isolated) continue;
+        const double cinf = std::max(std::fabs(C[0]), std::max(std::fabs(C[1]), std::fabs(C[2])));
+        const double margin = rt::kTrapDriftK * rt::kTrapDepth * 0x1p-23 * (cinf + r) / static_cast<double>(0.008f);
+        const double lo = static_cast<double>(0.008f) * (1.0 + 1e-3) / (2.0 * r) + margin;
+        const double hi = std::sqrt(1.0 - 1.0 / (ior * ior)) - margin;
+        if (!(lo <= hi) || !(lo > 0.0) || !(hi < 1.0)) continue;
+        float flo = static_cast<float>(lo), fhi = static_cast<float>(hi);
+        if (static_cast<double>(flo) < lo) flo = std::nextafter(flo, 2.f);
+        if (static_cast<double>(fhi) > hi) fhi = std::nextafter(fhi, -1.f);
+        if (!(flo <= fhi)) continue;
+        win[2 * S] = flo;
+        win[2 * S + 1] = fhi;
+    }
+    return win;
+}
+
 // ---- tile classes --------------------------------------------------------
 scene_geom scene_geometry(const rt_sphere *s, const blob_t &b)
 {
@@ -912,6 +978,20 @@ int rt_tile_order(const rt_sphere *spheres, uint32_t n_spheres, const rt_materia
     *n_sky = t.n_sky;
     if (t.perm.size() > cap) return cap ? fail(RT_ERR_CAPACITY, "rt_tile_order: perm buffer too small") : RT_OK;
     std::copy(t.perm.begin(), t.perm.end(), perm);
+    return RT_OK;
+}
+
+// The trap windows a scene of these spheres gets (trap_windows): out[2 i], out[2 i + 1] = sphere
+// i's {cos_lo, cos_hi}, {1, 0} when it has none.
+int rt_trap_windows(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
+                    float *out)
+{
+    if ((n_spheres && (!spheres || !out)) || !materials || !n_materials)
+        return fail(RT_ERR_INVALID, "rt_trap_windows: null argument or no materials");
+    for (uint32_t i = 0; i < n_spheres; ++i)
+        if (spheres[i].material >= n_materials) return fail(RT_ERR_INVALID, "rt_trap_windows: bad material index");
+    const std::vector<float> w = trap_windows(spheres, n_spheres, materials);
+    std::copy(w.begin(), w.end(), out);
     return RT_OK;
 }
 

@@ -39,6 +39,8 @@ struct blob_t {
 blob_t build_blob(const rt_sphere *s, uint32_t n, bool clustered, uint32_t cluster_max);
 std::vector<uint32_t> shortcut_words(const rt_sphere *s, uint32_t n, const rt_material *m, const blob_t &b,
                                      bool nb_off);
+// per sphere {cos_lo, cos_hi}, the trap window of an isolated glass ball (empty: {1, 0})
+std::vector<float> trap_windows(const rt_sphere *s, uint32_t n, const rt_material *m);
 
 // ---- tile classes of a pass ---------------------------------------------
 // What the classifier needs of a culled scene: the always-tested spheres, the box of every

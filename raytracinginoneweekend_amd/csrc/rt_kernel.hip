@@ -1527,6 +1527,7 @@ __device__ __forceinline__ void render_body(const KParams &p)
         // ---- shading: the hit of every live lane -----------------------------------------
         bool done = absorbed;
         f3 col = mk(0.f, 0.f, 0.f);
+        uint32_t trap_rem = 0;  // COUNT: the segments a path ended by its trap window would still trace
         if (alive && !defer) {
             if (!seg) {
                 done = true;  // main.cxx:74 (only reachable with max_depth == 0)
@@ -1624,6 +1625,7 @@ __device__ __forceinline__ void render_body(const KParams &p)
                             f3 outward = mk(-hn.x, -hn.y, -hn.z);
                             float ri = md.w, xs = dcs.y;
                             float cosv = dot(ud, hn);
+                            const bool inside = cosv > 0.f;
                             if (cosv <= 0.f) {
                                 outward = outward * -1.f;
                                 ri = dcs.x;                     // 1.f / ri
@@ -1633,13 +1635,35 @@ __device__ __forceinline__ void render_body(const KParams &p)
                             const f3 refr = refract(ud, outward, ri);
                             float prob = 1.f;
                             // length(refr) > 0 <=> norm > 0 (correctly rounded sqrt; NaN -> false)
-                            if (refr.x * refr.x + refr.y * refr.y + refr.z * refr.z > 0.f) prob = schlick_x(xs, cosv);
+                            const float rn = refr.x * refr.x + refr.y * refr.y + refr.z * refr.z;
+                            if (rn > 0.f) {
+                                prob = schlick_x(xs, cosv);
+                            } else if (inside && rn != rn) {
+                                // Total reflection inside the ball (refract gave NaN: reflected with
+                                // probability 1). With the cosine in the ball's trap window (rt_host_build.cpp
+                                // trap_windows) every later hit is proven to be this
+                                // ball's far root on this branch until max_depth, where the path returns 0
+                                // (main.cxx:74): it ends here with that colour. Ordered compares: a NaN
+                                // cosine never triggers. The skipped draws are this sample's own.
+                                const __attribute__((address_space(1))) float *win =
+                                    (const __attribute__((address_space(1))) float *)(P.trap + ib);
+                                if (cosv >= win[0] && cosv <= win[1]) {
+                                    done = true;
+                                    if (COUNT) trap_rem = P.max_depth - depth;
+                                }
+                            }
                             d = canonical(rng, inc_data) < prob ? rf : refr;
                         }
                     }
                 }
             }
             stamp(3);
+        }
+        if constexpr (COUNT) {
+            // the tally stays the reference's hit_world count: the segments the ended paths skip
+            uint32_t r = trap_rem;
+            for (int off = 32; off >= 1; off >>= 1) r += (uint32_t)__shfl_xor((int)r, off);
+            wt.add_seg(r);
         }
         if (done) {
             RT_EV(EV_STORE);

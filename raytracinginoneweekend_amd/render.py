@@ -222,6 +222,16 @@ def tile_order(scene, params, camera=None):
     return perm, nl.value, ns.value
 
 
+def trap_windows(scene):
+    """rt_trap_windows: per sphere (cos_lo, cos_hi), the trap window of an isolated glass ball
+    (DESIGN.md §4.1a); (1, 0) for a sphere without one."""
+    s, m = _scene_arrays(scene)
+    out = np.zeros((len(s), 2), dtype=np.float32)
+    check(lib().rt_trap_windows(abi.ptr(s, C.POINTER(abi.RtSphere)), len(s), abi.ptr(m, C.POINTER(abi.RtMaterial)),
+                                len(m), abi.ptr(out, C.POINTER(C.c_float))))
+    return out
+
+
 def release_cached():
     """rt_release_cached: free the device context the synchronous renders keep between calls."""
     check(lib().rt_release_cached())
