@@ -322,6 +322,34 @@ int rt_scene_destroy(rt_scene *scene);
  * enqueued on `stream`, so results appear in stream order.                                   */
 int rt_render_device(rt_scene *scene, const rt_camera *camera, const rt_params *params,
                      float *d_rgb, void *stream, uint64_t *d_segments);
+/* ---- the render with the variance of each pixel's mean luminance ----
+ * d_rgb receives the bits rt_render_device writes for the same arguments; d_var receives one float
+ * per pixel, laid out as the one-channel feature planes below (row * width + x; packed rows or
+ * RT_FLAG_FULL_FRAME, with row_offset / row_stride / num_rows). With c_s the colour of the
+ * beauty's sample s = 0..spp-1, every operation binary32 and rounded on its own (no contraction):
+ *   L_s  = (0.2126f * c_s.r + 0.7152f * c_s.g) + 0.0722f * c_s.b
+ *   d_s  = L_s - L_0                          (shifted data: d_0 = 0)
+ *   m1   = (((0 + d_0) + d_1) + ...)          sequential, in sample order, across passes
+ *   m2   = (((0 + d_0*d_0) + d_1*d_1) + ...)  likewise
+ *   n    = float(spp);  mean = m1 / n;  ex2 = m2 / n            (IEEE divisions)
+ *   var  = fmaxf(0.0f, ex2 - mean * mean) / float(spp - 1)
+ * the unbiased sample variance of L divided by spp: the variance of the pixel's mean luminance. The
+ * shift by L_0 keeps the subtraction from cancelling on nearly constant pixels (the sky).
+ * spp < 2 is RT_ERR_INVALID. RT_FLAG_BRUTE_FORCE is honoured (same bits); RT_FLAG_FAST_MATH,
+ * RT_FLAG_SCALAR_SCENE, RT_FLAG_WAVEFRONT and RT_FLAG_CUDA_COMPAT return RT_ERR_UNSUPPORTED. Every
+ * argument is checked before any HIP call. The frame is planned with one sample per slot and its
+ * proven-sky tiles traced by the main launch (as under RT_DIAG_NO_PAIRS | RT_DIAG_NO_SKY), whatever
+ * the scene's options say: the per-sample colours must reach the accumulation. A frame of several
+ * passes carries {L_0, m1, m2} per pixel in a workspace accounted like the multi-pass sums
+ * (rt_scene_usage, max_workspace_bytes), allocated by the first such frame. d_segments, stream
+ * order and frames in flight are rt_render_device's.                                           */
+int rt_render_var_device(rt_scene *scene, const rt_camera *camera, const rt_params *params,
+                         float *d_rgb, float *d_var, void *stream, uint64_t *d_segments);
+/* Host pointers, synchronous, through the cached per-device context of rt_render_f32. With
+ * RT_FLAG_FULL_FRAME only the rendered rows of rgb_out and var_out are written.                */
+int rt_render_var(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
+                  const rt_camera *camera, const rt_params *params,
+                  float *rgb_out, float *var_out, rt_stats *stats);
 /* ---- first-hit feature buffers --------------------------------------
  * The guide buffers a denoiser or compositor takes, for the pass rt_params describes. Sample s
  * of a pixel is the beauty render's sample s (same key with the frame's spp, same streams, same
@@ -442,6 +470,42 @@ int rt_denoise_level_device(const rt_denoise_params *params, const rt_denoise_bu
  * the counters are 0.                                                                           */
 int rt_denoise(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
                rt_stats *stats);
+
+/* ---- the variance-guided à-trous filter --------------------------------
+ * rt_denoise_device with the colour term steered per pixel by the variance rt_render_var writes
+ * (SVGF, Schied et al. 2017, §4.2-4.4). Everything above holds except: V_0 = variance; at level l
+ * (step s = 1 << l, colour input C_l, variance input V_l), for pixel p = (x, y):
+ *   prefilter  g = 0; for j = -1..1 (outer), i = -1..1 (inner): g = g + k * V_l(q), q = (clamp(x + i,
+ *              0, w - 1), clamp(y + j, 0, h - 1)) (spacing 1, not s), k = 0.25f at the centre, 0.125f
+ *              when exactly one of i, j is 0, 0.0625f at the corners
+ *   colour     r_c(p) = 1.0f / (sc2 * g + var_floor), sc2 = sigma_color * sigma_color formed once on
+ *              the host: one IEEE division per pixel and level and no 2^-l factor (V itself
+ *              shrinks); the term is edge(d2, r_c(p)) with the RGB d2 above; sigma_color = 0: off
+ *   variance   in the same tap loop, from sumv = 0: sumv = sumv + (w * w) * V_l(q) with the tap's
+ *              final w; V_{l+1}(p) = sumv / (sumw * sumw)
+ * The normal, depth and albedo terms, the tap order, the skipped taps and sumw / sum[c] are
+ * unchanged. The levels' V alternate between the two halves of var_scratch; variance_out, if
+ * given, receives V_levels. RT_DENOISE_DEMODULATE is RT_ERR_UNSUPPORTED (the variance would have to
+ * be demodulated too); RT_DENOISE_DIRECT is accepted and means nothing new (every level is a
+ * direct-load launch). RT_ERR_INVALID names the field: every check of rt_denoise_device, a wrong
+ * size, a null variance, a null var_scratch (device call), a var_floor that is not positive and
+ * finite, variance_out or var_scratch equal to any other plane.                                 */
+typedef struct rt_denoise_var_buffers {
+    uint32_t size;          /* sizeof(rt_denoise_var_buffers)                                   */
+    float var_floor;        /* > 0, finite                                                       */
+    const float *variance;  /* [h][w], as rt_render_var writes it; never written                 */
+    float *variance_out;    /* optional [h][w]: V after the last level                           */
+    float *var_scratch;     /* 2*w*h floats (device call; ignored by the host call)              */
+} rt_denoise_var_buffers;
+/* The defaults (DESIGN.md §4.10 records the sweep that chose them); either record may be NULL. */
+int rt_denoise_var_params_default(uint32_t width, uint32_t height, rt_denoise_params *params,
+                                  rt_denoise_var_buffers *var);
+/* Device pointers; one launch per level on `stream`, no host synchronisation, no allocation.    */
+int rt_denoise_var_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
+                          const rt_denoise_var_buffers *var, void *stream);
+/* Host pointers, synchronous, device planes in the cached per-device context (as rt_denoise).   */
+int rt_denoise_var(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
+                   const rt_denoise_var_buffers *var, rt_stats *stats);
 
 /* Device memory a scene holds and how its renders are cut (after the last render call).  */
 typedef struct rt_scene_usage {

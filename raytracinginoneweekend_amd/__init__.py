@@ -6,7 +6,7 @@ from . import _abi as abi  # noqa: F401
 from ._lib import RtError, lib  # noqa: F401
 from .camera import CORRECTED, REFERENCE, Camera  # noqa: F401
 from .render import (DeviceScene, MultiContext, default_options, default_options_set, denoise,  # noqa: F401
-                     denoise_device, denoise_params,
+                     denoise_device, denoise_params, denoise_var, denoise_var_device, denoise_var_params, render_var,
                      epilogue_rgb8_device, make_params, options, parse_options, render_aov, render_cuda_impl, render_f32,
                      release_cached, render_multi_f32, render_multi_rgb8, render_rgb8, save_ppm,
                      set_default_options, tile_order, trap_windows)

@@ -123,8 +123,19 @@ class RtDenoiseBuffers(C.Structure):
     ]
 
 
+class RtDenoiseVarBuffers(C.Structure):
+    """rt_denoise_var_buffers (include/rt_api.h): the variance planes of a variance-guided denoise."""
+    _fields_ = [
+        ("size", C.c_uint32), ("var_floor", C.c_float),
+        ("variance", C.c_void_p), ("variance_out", C.c_void_p), ("var_scratch", C.c_void_p),
+    ]
+
+
 # the planes of rt_denoise_buffers: name -> channels
 DENOISE_PLANES = {"beauty": 3, "albedo": 3, "normal": 3, "depth": 1, "out": 3, "scratch": 3}
+
+# the planes of rt_denoise_var_buffers: name -> floats per pixel (var_scratch holds two planes)
+DENOISE_VAR_PLANES = {"variance": 1, "variance_out": 1, "var_scratch": 2}
 
 # the planes of rt_aov_buffers: name -> (channels, numpy dtype, value of a pixel no call wrote)
 AOV_PLANES = {"albedo": (3, np.float32, 0), "normal": (3, np.float32, 0), "depth": (1, np.float32, 0),
@@ -138,6 +149,7 @@ assert C.sizeof(RtParams) == 40
 assert C.sizeof(RtOptions) == 64 and C.sizeof(RtSceneUsage) == 56
 assert C.sizeof(RtAovBuffers) == 48
 assert C.sizeof(RtDenoiseParams) == 36 and C.sizeof(RtDenoiseBuffers) == 56
+assert C.sizeof(RtDenoiseVarBuffers) == 32
 
 
 def ptr(arr, ctype=C.c_void_p):

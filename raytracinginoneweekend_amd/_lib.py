@@ -81,6 +81,16 @@ def _declare(L):
         "rt_denoise_level_device": (C.c_int, [P(abi.RtDenoiseParams), P(abi.RtDenoiseBuffers), C.c_uint32,
                                               C.c_void_p]),
         "rt_denoise": (C.c_int, [P(abi.RtDenoiseParams), P(abi.RtDenoiseBuffers), P(abi.RtStats)]),
+        "rt_render_var_device": (C.c_int, [C.c_void_p, P(abi.RtCamera), P(abi.RtParams), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+        "rt_render_var": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, P(abi.RtCamera),
+                                    P(abi.RtParams), P(C.c_float), P(C.c_float), P(abi.RtStats)]),
+        "rt_denoise_var_params_default": (C.c_int, [C.c_uint32, C.c_uint32, P(abi.RtDenoiseParams),
+                                                    P(abi.RtDenoiseVarBuffers)]),
+        "rt_denoise_var_device": (C.c_int, [P(abi.RtDenoiseParams), P(abi.RtDenoiseBuffers),
+                                            P(abi.RtDenoiseVarBuffers), C.c_void_p]),
+        "rt_denoise_var": (C.c_int, [P(abi.RtDenoiseParams), P(abi.RtDenoiseBuffers), P(abi.RtDenoiseVarBuffers),
+                                     P(abi.RtStats)]),
         "rt_scene_kernel_times": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float), P(C.c_uint32)]),
         "rt_scene_debug_counters": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_int]),
         "rt_scene_debug_timeline": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_uint32, P(C.c_uint32)]),

@@ -247,4 +247,86 @@ hipError_t launch_denoise(const KDenoise &k, uint32_t terms, bool demod_in, bool
     return hipLaunchKernel(direct_ptr(v, std::make_index_sequence<32>{}), grid, dim3(64, 4), args, 0, stream);
 }
 
+// ---- the variance-guided level (rt_denoise_var_device) -------------------------
+// denoise_direct's tap loop with two differences: the colour term's r_c is formed per pixel from the
+// 3x3 prefiltered variance (clamped coordinates, spacing 1), and every tap also adds w^2 V(q) to the
+// variance carried to the next level. One lane per pixel, 64 consecutive x per wave row (every plane
+// is read with unit stride over the lanes); the terms are compiled out as above.
+template <int TERMS>
+__global__ __launch_bounds__(256) void denoise_var_direct(const KDenoiseVar kv)
+{
+    const KDenoise &k = kv.d;
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    const int W = k.W, H = k.H, s = k.step;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    float r_c = 0.f;
+    if (TERMS & kDnColor) {
+        float g = 0.f;
+#pragma unroll
+        for (int j = -1; j <= 1; ++j) {
+            const int qy = min(max(y + j, 0), H - 1);
+#pragma unroll
+            for (int i = -1; i <= 1; ++i) {
+                const int qx = min(max(x + i, 0), W - 1);
+                const float kk = (i == 0 && j == 0) ? 0.25f : (i == 0 || j == 0) ? 0.125f : 0.0625f;
+                g = g + kk * kv.vin[(size_t)qy * W + qx];
+            }
+        }
+        r_c = 1.0f / (kv.sc2 * g + kv.var_floor);
+    }
+    const float cr = k.in[3u * p], cg = k.in[3u * p + 1u], cb = k.in[3u * p + 2u];
+    float nx = 0.f, ny = 0.f, nz = 0.f, pz = 0.f, ar = 0.f, ag = 0.f, ab = 0.f;
+    if (TERMS & kDnNormal) nx = k.normal[3u * p], ny = k.normal[3u * p + 1u], nz = k.normal[3u * p + 2u];
+    if (TERMS & kDnDepth) pz = k.depth[p];
+    if (TERMS & kDnAlbedo) ar = k.albedo[3u * p], ag = k.albedo[3u * p + 1u], ab = k.albedo[3u * p + 2u];
+    float sumw = 0.f, sumv = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
+#pragma unroll
+    for (int j = -2; j <= 2; ++j) {
+        const int qy = y + j * s;
+#pragma unroll
+        for (int i = -2; i <= 2; ++i) {
+            const int qx = x + i * s;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;  // skipped: nothing is added
+            const size_t q = (size_t)qy * W + qx;
+            float w = dn_h(i) * dn_h(j);
+            const float qr = k.in[3u * q], qg = k.in[3u * q + 1u], qb = k.in[3u * q + 2u];
+            if (TERMS & kDnColor) w = w * dn_edge(dn_dist2(qr, qg, qb, cr, cg, cb), r_c);
+            if (TERMS & kDnNormal)
+                w = w * dn_edge(dn_dist2(k.normal[3u * q], k.normal[3u * q + 1u], k.normal[3u * q + 2u], nx, ny, nz),
+                                k.r_n);
+            if (TERMS & kDnDepth) {
+                const float dz = k.depth[q] - pz;
+                w = w * dn_edge(dz * dz, k.r_z);
+            }
+            if (TERMS & kDnAlbedo)
+                w = w * dn_edge(dn_dist2(k.albedo[3u * q], k.albedo[3u * q + 1u], k.albedo[3u * q + 2u], ar, ag, ab),
+                                k.r_a);
+            sumw = sumw + w;
+            sumv = sumv + (w * w) * kv.vin[q];
+            sr = sr + w * qr;
+            sg = sg + w * qg;
+            sb = sb + w * qb;
+        }
+    }
+    k.out[3u * p] = sr / sumw;
+    k.out[3u * p + 1u] = sg / sumw;
+    k.out[3u * p + 2u] = sb / sumw;
+    if (kv.vout) kv.vout[p] = sumv / (sumw * sumw);
+}
+
+template <size_t... V>
+static const void *var_ptr(uint32_t v, std::index_sequence<V...>)
+{
+    static const void *const t[] = {reinterpret_cast<const void *>(&denoise_var_direct<int(V)>)...};
+    return t[v];
+}
+
+hipError_t launch_denoise_var(const KDenoiseVar &k, uint32_t terms, hipStream_t stream)
+{
+    void *args[] = {const_cast<KDenoiseVar *>(&k)};
+    const dim3 grid((k.d.W + 63) / 64, (k.d.H + 3) / 4);
+    return hipLaunchKernel(var_ptr(terms & 15u, std::make_index_sequence<16>{}), grid, dim3(64, 4), args, 0, stream);
+}
+
 } // namespace rt

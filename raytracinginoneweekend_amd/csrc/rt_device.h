@@ -197,6 +197,11 @@ struct KAccum {
     // flags; part 0 (unsplit pass): every pixel
     uint8_t *deep_px;
     uint32_t part;
+    // rt_render_var_device: var non-null selects the moments instantiation; mom =
+    // [n_pixels][3] {L_0, m1, m2} between passes, indexed like acc; var = the last pass's output
+    // plane, one float per pixel at the position of out's pixel
+    float *mom;
+    float *var;
 };
 
 // RT_FLAG_CUDA_COMPAT: the semantics of the reference's CUDA variant (src/CUDA/cuda_impl.cu),
@@ -256,6 +261,15 @@ struct KDenoise {
     uint32_t W, H, step;        // step = 1 << level
     float r_c, r_n, r_z, r_a;   // 1 / sigma^2 of each term, computed on the host
     uint32_t demod_out;         // the run's last level: the result times A'(p)
+};
+
+// One level of the variance-guided filter (rt_denoise_var_device): d as above
+// (d.r_c unused, no demodulation), vin = V_l, vout = V_{l+1} (null: not stored).
+struct KDenoiseVar {
+    KDenoise d;
+    const float *vin;
+    float *vout;
+    float sc2, var_floor;       // sigma_color^2 (formed on the host) and the floor of the colour term
 };
 
 // The wavefront variant's ray queue (structure of arrays, capacity cap rays): f = [9][cap]

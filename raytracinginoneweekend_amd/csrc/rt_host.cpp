@@ -50,6 +50,7 @@ hipError_t occupancy_aov(int cull, int *blocks_per_cu, size_t lds);
 hipError_t static_lds_aov(int cull, size_t *bytes);
 // rt_denoise.hip
 hipError_t launch_denoise(const KDenoise &k, uint32_t terms, bool demod_in, bool tiled, hipStream_t stream);
+hipError_t launch_denoise_var(const KDenoiseVar &k, uint32_t terms, hipStream_t stream);
 size_t denoise_tiled_lds(uint32_t terms, uint32_t step);
 } // namespace rt
 
@@ -158,6 +159,10 @@ struct rt_scene {
     size_t slots_bytes[kMaxWs] = {};
     float *acc = nullptr;
     size_t acc_bytes = 0;
+    // rt_render_var_device: {L_0, m1, m2} per pixel between the passes of a frame, beside acc
+    // (allocated by the first multi-pass variance render)
+    float *mom = nullptr;
+    size_t mom_bytes = 0;
     // deep-path split: per workspace, the pixel flags (a byte per pixel, at the front) and then
     // the deep queue (rt::DeepQueue); deep_clean = leading bytes known to be zero (every pass's
     // accumulation clears the flags it set, so only a larger pixel count needs a memset)
@@ -448,7 +453,7 @@ int rt_scene_destroy(rt_scene *sc)
     }
     if (sc->ev_tail) (void)hipEventDestroy(sc->ev_tail);
     if (sc->ev_sky) (void)hipEventDestroy(sc->ev_sky);
-    for (void *p : {(void *)sc->blob[0], (void *)sc->blob[1], (void *)sc->dbg, (void *)sc->acc, (void *)sc->queue_ctr, sc->wq, (void *)sc->trap})
+    for (void *p : {(void *)sc->blob[0], (void *)sc->blob[1], (void *)sc->dbg, (void *)sc->acc, (void *)sc->mom, (void *)sc->queue_ctr, sc->wq, (void *)sc->trap})
         if (p) (void)hipFree(p);
     for (float *p : sc->slots)
         if (p) (void)hipFree(p);
@@ -698,6 +703,9 @@ int free_workspaces(rt_scene *sc)
     void *ap = sc->acc;
     RT_HIP(drop(ap, sc->acc_bytes));
     sc->acc = nullptr;
+    void *mp = sc->mom;
+    RT_HIP(drop(mp, sc->mom_bytes));
+    sc->mom = nullptr;
     RT_HIP(drop(sc->wq, sc->wq_bytes));
     return RT_OK;
 }
@@ -720,7 +728,7 @@ int stream_leave(rt_scene *sc, hipStream_t st)
     return RT_OK;
 }
 int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
-                       uint64_t *d_segments);
+                       uint64_t *d_segments, float *d_var = nullptr);
 } // namespace
 
 int rt_render_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, float *d_rgb, void *stream,
@@ -734,6 +742,38 @@ int rt_render_device(rt_scene *sc, const rt_camera *camera, const rt_params *par
     const int rc = (params->flags & RT_FLAG_CUDA_COMPAT) ? render_compat(sc, camera, *params, d_rgb, st, d_segments)
                                                          : render_device_impl(sc, camera, *params, d_rgb, st, d_segments);
     if (rc != RT_OK) return rc;
+    return stream_leave(sc, st);
+}
+
+namespace {
+// The params of a variance render (rt_render_var*), decided before any HIP call.
+int check_var_params(const rt_params *p, const char *who)
+{
+    if (int rc = check_params(p); rc != RT_OK) return rc;
+    const std::string w(who);
+    if (p->spp < 2u) return fail(RT_ERR_INVALID, w + ": spp must be at least 2 (a variance needs two samples)");
+    static const struct { uint32_t bit; const char *name; } unsupported[] = {
+        {RT_FLAG_FAST_MATH, "RT_FLAG_FAST_MATH"}, {RT_FLAG_SCALAR_SCENE, "RT_FLAG_SCALAR_SCENE"},
+        {RT_FLAG_WAVEFRONT, "RT_FLAG_WAVEFRONT"}, {RT_FLAG_CUDA_COMPAT, "RT_FLAG_CUDA_COMPAT"}};
+    for (const auto &u : unsupported)
+        if (p->flags & u.bit) return fail(RT_ERR_UNSUPPORTED, w + ": " + u.name + " is not supported (the exact kernel only)");
+    return RT_OK;
+}
+} // namespace
+
+int rt_render_var_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, float *d_rgb, float *d_var,
+                         void *stream, uint64_t *d_segments)
+{
+    if (!sc) return fail(RT_ERR_INVALID, "rt_render_var_device: null scene");
+    if (!camera) return fail(RT_ERR_INVALID, "rt_render_var_device: null camera");
+    if (!d_rgb) return fail(RT_ERR_INVALID, "rt_render_var_device: null d_rgb");
+    if (!d_var) return fail(RT_ERR_INVALID, "rt_render_var_device: null d_var");
+    if (d_var == d_rgb) return fail(RT_ERR_INVALID, "rt_render_var_device: d_var is also d_rgb");
+    if (int rc = check_var_params(params, "rt_render_var_device"); rc != RT_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RT_HIP(hipSetDevice(sc->device));
+    if (int rc = stream_enter(sc, st); rc != RT_OK) return rc;
+    if (int rc = render_device_impl(sc, camera, *params, d_rgb, st, d_segments, d_var); rc != RT_OK) return rc;
     return stream_leave(sc, st);
 }
 
@@ -776,9 +816,13 @@ int frame_params(const rt_scene *sc, const rt_camera *camera, const rt_params &P
     return RT_OK;
 }
 
+// d_var (rt_render_var_device): the frame also yields the variance of each pixel's
+// mean luminance. Its samples' colours must reach the accumulation one by one, so it is planned as
+// under RT_DIAG_NO_PAIRS | RT_DIAG_NO_SKY whatever the scene's options say.
 int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
-                       uint64_t *d_segments)
+                       uint64_t *d_segments, float *d_var)
 {
+    const bool moments = d_var != nullptr;
     rt::KParams k{};
     if (int rc = frame_params(sc, camera, P, k, "rt_render_device"); rc) return rc;
     const uint64_t n_pixels = k.n_pixels;
@@ -896,7 +940,7 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     // in a workspace of its own beside the ring. Culled LDS kernels only (the wavefront variant,
     // brute force and the scalar-cache variant store single samples).
     const bool pairs_ok = !wave && cull_mode == 7 && variant != rt::V_EXACT_SCALAR && !(O.diag & RT_DIAG_NO_PAIRS) &&
-                          lds + sc->static_lds_pairs <= sc->max_lds;
+                          !moments && lds + sc->static_lds_pairs <= sc->max_lds;
     // passes dealt by tile classes: the culled LDS kernels with a scene geometry to classify
     const bool order_ok = sc->has_geom && cull_mode == 7 && !wave && variant != rt::V_EXACT_SCALAR &&
                           !(O.diag & RT_DIAG_NATURAL_ORDER);
@@ -966,7 +1010,7 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
         uint64_t t = static_cast<uint64_t>(n_ws_of(streams, wsps)) * (ws_bytes(sr, ring_pairs) + dq_of(sr));
         if (whole) t += ws_bytes(sp, false) + dq_of(sp);
         else if (ring_pairs) t += ws_bytes(sr, false) + dq_of(sr);
-        if (sr < P.spp) t += per_sample;  // the multi-pass sums
+        if (sr < P.spp) t += moments ? 2u * per_sample : per_sample;  // the multi-pass sums (and moments)
         if (wave) t += 2ull * wave_cap(sp) * 52u + 512u;
         return t;
     };
@@ -1011,6 +1055,7 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
             after += used && may_split ? std::max<uint64_t>(sc->deep_bytes[w], dq_of(pass_of(w))) : sc->deep_bytes[w];
         }
         after += spr < P.spp ? std::max<uint64_t>(sc->acc_bytes, per_sample) : sc->acc_bytes;
+        after += spr < P.spp && moments ? std::max<uint64_t>(sc->mom_bytes, per_sample) : sc->mom_bytes;
         after += wave ? std::max<uint64_t>(sc->wq_bytes, 2ull * wave_cap(spp_pass) * 52u + 512u) : sc->wq_bytes;
         if (after > O.max_workspace_bytes)
             if (int rc = free_workspaces(sc); rc) return rc;
@@ -1022,6 +1067,8 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     sc->used_pairs = sc->used_split = sc->used_lead = sc->used_sky = 0;
     if (spr < P.spp)
         if (int rc = ensure((void **)&sc->acc, &sc->acc_bytes, per_sample); rc) return rc;
+    if (spr < P.spp && moments)
+        if (int rc = ensure((void **)&sc->mom, &sc->mom_bytes, per_sample); rc) return rc;
     for (uint32_t w = 0; w < n_ws; ++w)
         if (int rc = ensure((void **)&sc->slots[w], &sc->slots_bytes[w], ws_size(w)); rc) return rc;
     if (lone_ws < kMaxWs)
@@ -1060,7 +1107,7 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     if (order_ok && !pairs)
         if (int rc = pass_order(sc, *camera, k, &ord); rc) return rc;
     // (max_depth 0: every sample's colour is 0, main.cxx:74, not the sky's)
-    const bool sky_kernel = ord && ord->d_perm && ord->t.n_sky && P.max_depth > 0 && !(O.diag & RT_DIAG_NO_SKY);
+    const bool sky_kernel = ord && ord->d_perm && ord->t.n_sky && P.max_depth > 0 && !(O.diag & RT_DIAG_NO_SKY) && !moments;
     const uint32_t sky_pos0 = sky_kernel ? static_cast<uint32_t>(64u * (ord->t.perm.size() - ord->t.n_sky)) : k.n_pixels;
     const uint32_t ring = static_cast<uint32_t>(sc->calls % rt_scene::kRing);
     ++sc->calls;
@@ -1338,6 +1385,8 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
         a.acc = sc->acc;
         a.out = d_rgb;
         a.out_u8 = nullptr;
+        a.mom = sc->mom;
+        a.var = d_var;
         a.n_pixels = k.n_pixels;
         a.n_samples = s1 - s0;
         a.n_blocks = (std::min(s1, full_blocks_end) - std::min(s0, full_blocks_end)) / 4u;
@@ -1560,7 +1609,7 @@ int rt_scene_usage_get(const rt_scene *sc, rt_scene_usage *out)
 {
     if (!sc || !out) return fail(RT_ERR_INVALID, "rt_scene_usage_get: null argument");
     rt_scene_usage u{};
-    uint64_t ws = sc->acc_bytes + sc->wq_bytes;
+    uint64_t ws = sc->acc_bytes + sc->mom_bytes + sc->wq_bytes;
     for (uint32_t w = 0; w < kMaxWs; ++w) ws += sc->slots_bytes[w] + sc->deep_bytes[w];
     uint64_t fixed = kCtrWords * sizeof(uint32_t) + (sc->dbg ? rt::kDbgWords * sizeof(unsigned long long) : 0u);
     for (int b = 0; b < 2; ++b) fixed += static_cast<uint64_t>(sc->blob_units[b]) * 16u;
@@ -1661,6 +1710,8 @@ struct SyncContext {
     size_t aov_bytes = 0;
     void *d_dn = nullptr;   // rt_denoise: the inputs, out and scratch, one after the other
     size_t dn_bytes = 0;
+    float *d_var = nullptr;  // rt_render_var: the variance plane (the beauty goes to d_rgb)
+    size_t var_bytes = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 std::mutex g_sync_mu;  // one synchronous render at a time per process (the reference's entry is not re-entrant)
@@ -1672,7 +1723,7 @@ void sync_release(int dev, SyncContext &c)
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(dev);
     if (c.sc) rt_scene_destroy(c.sc);
-    for (void *p : {(void *)c.d_rgb, (void *)c.d_u8, (void *)c.d_seg, c.d_aov, c.d_dn})
+    for (void *p : {(void *)c.d_rgb, (void *)c.d_u8, (void *)c.d_seg, c.d_aov, c.d_dn, (void *)c.d_var})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : {c.e0, c.e1})
         if (e) (void)hipEventDestroy(e);
@@ -1855,6 +1906,87 @@ int render_aov_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_mater
     return rc;
 }
 
+// Synchronous render with the variance plane into host buffers, through the same cached context
+// (full frame: the rendered rows only, of both outputs).
+int render_var_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
+                    const rt_camera *camera, const rt_params *params, float *rgb_out, float *var_out, rt_stats *stats)
+{
+    if (!camera) return fail(RT_ERR_INVALID, "rt_render_var: null camera");
+    if (!rgb_out) return fail(RT_ERR_INVALID, "rt_render_var: null rgb_out");
+    if (!var_out) return fail(RT_ERR_INVALID, "rt_render_var: null var_out");
+    if (var_out == rgb_out) return fail(RT_ERR_INVALID, "rt_render_var: var_out is also rgb_out");
+    if (int rc = check_var_params(params, "rt_render_var"); rc != RT_OK) return rc;
+    if ((n_spheres && !spheres) || !materials || !n_materials) return fail(RT_ERR_INVALID, "rt_render_var: null scene");
+    const auto t0 = std::chrono::steady_clock::now();
+    int dev = 0;
+    RT_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_sync_mu);
+    SyncContext &cx = g_sync[dev];
+    if (int rc = sync_scene(dev, cx, spheres, n_spheres, materials, n_materials); rc) return rc;
+    const rt_params &P = *params;
+    const bool full = (P.flags & RT_FLAG_FULL_FRAME) != 0u;
+    const uint64_t rows = rows_of(P), rows_out = full ? P.height : rows;
+    const size_t n_px = static_cast<size_t>(rows_out) * P.width;
+    int rc = RT_OK;
+    auto chk = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+        return rc == RT_OK;
+    };
+    auto grow_buf = [&](void **p, size_t *have, size_t want) {
+        if (*have >= want && *p) return;
+        if (*p) chk(hipFree(*p), "hipFree");
+        *p = nullptr;
+        *have = 0;
+        if (chk(hipMalloc(p, std::max<size_t>(want, 256)), "hipMalloc")) *have = want;
+    };
+    grow_buf((void **)&cx.d_rgb, &cx.rgb_bytes, n_px * 12u);
+    grow_buf((void **)&cx.d_var, &cx.var_bytes, n_px * 4u);
+    if (rc == RT_OK && !cx.d_seg) chk(hipMalloc((void **)&cx.d_seg, 24), "hipMalloc");
+    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
+    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
+    uint64_t segs[3] = {0, 0, 0};
+    float ms = 0.f;
+    if (rc == RT_OK && rows) {
+        if (stats) chk(hipMemsetAsync(cx.d_seg, 0, 24, nullptr), "hipMemset");
+        if (rc == RT_OK) chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
+        if (rc == RT_OK) rc = rt_render_var_device(cx.sc, camera, params, cx.d_rgb, cx.d_var, nullptr, stats ? cx.d_seg : nullptr);
+        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
+        // the copies on the null stream follow the render
+        const struct { void *host; const void *dev; size_t row_bytes; } outs[2] = {
+            {rgb_out, cx.d_rgb, static_cast<size_t>(P.width) * 12u}, {var_out, cx.d_var, static_cast<size_t>(P.width) * 4u}};
+        for (const auto &o : outs) {
+            if (rc != RT_OK) break;
+            if (!full) {
+                chk(hipMemcpy(o.host, o.dev, rows * o.row_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+            } else {
+                const size_t st = P.row_stride ? P.row_stride : 1u, first = P.row_offset * o.row_bytes;
+                chk(hipMemcpy2D(static_cast<char *>(o.host) + first, st * o.row_bytes,
+                                static_cast<const char *>(o.dev) + first, st * o.row_bytes, o.row_bytes, rows,
+                                hipMemcpyDeviceToHost),
+                    "hipMemcpy2D");
+            }
+        }
+        if (rc == RT_OK && stats) chk(hipMemcpy(segs, cx.d_seg, 24, hipMemcpyDeviceToHost), "hipMemcpy");
+        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_render_var");
+        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
+    }
+    if (rc != RT_OK) {
+        // a failed call leaves no state behind: the next one starts from a new context
+        const std::string msg = g_error;
+        sync_release(dev, cx);
+        g_error = msg;
+    }
+    if (rc == RT_OK && stats) {
+        stats->primaries = static_cast<uint64_t>(P.width) * rows * P.spp;
+        stats->segments = segs[0];
+        stats->sphere_tests = segs[1];
+        stats->box_tests = segs[2];
+        stats->kernel_ms = ms;
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return rc;
+}
+
 
 // ---- the à-trous denoiser (include/rt_api.h; kernels in rt_denoise.hip) ----------------------
 // Levels with a step up to this take the tiled kernel: at 1280x720 with every guide it takes 0.77
@@ -1865,6 +1997,10 @@ constexpr uint32_t kDenoiseTiledMaxStep = 2;
 // with every guide is then 60 KiB, the most a launch gets without asking for more.
 constexpr uint32_t kDenoiseTiledFits = 4;
 constexpr uint32_t kDenoiseMaxSide = 65536;
+// rt_denoise_var_params_default: the values scripts/denoise_var_sweep.py chose
+constexpr uint32_t kDnVarLevels = 2;
+constexpr float kDnVarSigmaColor = 32.0f, kDnVarSigmaNormal = 1.0f, kDnVarSigmaDepth = 4.0f, kDnVarSigmaAlbedo = 1.0f;
+constexpr float kDnVarFloor = 1e-6f;
 
 // Every argument check of the denoiser, before any HIP call (use_scratch: the call uses
 // buffers.scratch). terms: the edge terms that are on.
@@ -2007,9 +2143,174 @@ int denoise_host(const rt_denoise_params *params, const rt_denoise_buffers *buff
     return rc;
 }
 
+// ---- the variance-guided filter (include/rt_api.h) ---------------------------
+// Its checks: rt_denoise_device's, then the variance record's (use_scratch: a device call).
+int check_denoise_var(const rt_denoise_params *p, const rt_denoise_buffers *b, const rt_denoise_var_buffers *v,
+                      bool use_scratch, const char *who, uint32_t *terms)
+{
+    if (int rc = check_denoise(p, b, use_scratch, who, terms); rc != RT_OK) return rc;
+    const std::string w = std::string(who) + ": ";
+    if (p->flags & RT_DENOISE_DEMODULATE)
+        return fail(RT_ERR_UNSUPPORTED, w + "RT_DENOISE_DEMODULATE is not supported (the variance is not demodulated)");
+    if (!v) return fail(RT_ERR_INVALID, w + "null variance record");
+    if (v->size != sizeof(rt_denoise_var_buffers))
+        return fail(RT_ERR_INVALID, w + "var.size is not sizeof(rt_denoise_var_buffers)");
+    if (!std::isfinite(v->var_floor) || !(v->var_floor > 0.f)) return fail(RT_ERR_INVALID, w + "var_floor must be finite and positive");
+    if (!v->variance) return fail(RT_ERR_INVALID, w + "variance is null");
+    const float *const var_scratch = use_scratch ? v->var_scratch : nullptr;
+    if (use_scratch && !var_scratch) return fail(RT_ERR_INVALID, w + "var_scratch is null");
+    const float *const scratch = use_scratch ? b->scratch : nullptr;
+    for (const float *o : {b->beauty, b->albedo, b->normal, b->depth, static_cast<const float *>(b->out), scratch,
+                           v->variance}) {
+        if (o && o == v->variance_out) return fail(RT_ERR_INVALID, w + "variance_out is also another plane");
+        if (o && o == var_scratch) return fail(RT_ERR_INVALID, w + "var_scratch is also another plane");
+    }
+    if (var_scratch && var_scratch == v->variance_out) return fail(RT_ERR_INVALID, w + "var_scratch is also variance_out");
+    return RT_OK;
+}
+
+// Enqueue every level: the colours alternate between b.scratch and b.out as in denoise_levels, the
+// variances between the halves of v.var_scratch; the last level's goes to v.variance_out, if given.
+int denoise_var_levels(const rt_denoise_params &p, const rt_denoise_buffers &b, const rt_denoise_var_buffers &v,
+                       uint32_t terms, hipStream_t stream)
+{
+    rt::KDenoiseVar kv{};
+    rt::KDenoise &k = kv.d;
+    k.albedo = (terms & 8u) ? b.albedo : nullptr;
+    k.normal = b.normal;
+    k.depth = b.depth;
+    k.W = p.width;
+    k.H = p.height;
+    k.r_n = (terms & 2u) ? denoise_r(p.sigma_normal) : 0.f;
+    k.r_z = (terms & 4u) ? denoise_r(p.sigma_depth) : 0.f;
+    k.r_a = (terms & 8u) ? denoise_r(p.sigma_albedo) : 0.f;
+    kv.sc2 = p.sigma_color * p.sigma_color;
+    kv.var_floor = v.var_floor;
+    const size_t n = static_cast<size_t>(p.width) * p.height;
+    const float *in = b.beauty, *vin = v.variance;
+    const uint32_t last = p.levels - 1u;
+    for (uint32_t l = 0; l <= last; ++l) {
+        k.in = in;
+        k.out = ((last - l) & 1u) ? b.scratch : b.out;
+        k.step = 1u << l;
+        kv.vin = vin;
+        kv.vout = l == last ? v.variance_out : v.var_scratch + (l & 1u) * n;
+        RT_HIP(rt::launch_denoise_var(kv, terms, stream));
+        in = k.out;
+        vin = kv.vout;
+    }
+    return RT_OK;
+}
+
+// Synchronous variance-guided denoise of host planes through the cached context's buffer.
+int denoise_var_host(const rt_denoise_params *params, const rt_denoise_buffers *buffers, const rt_denoise_var_buffers *var,
+                     rt_stats *stats)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise_var(params, buffers, var, false, "rt_denoise_var", &terms); rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    int dev = 0;
+    RT_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_sync_mu);
+    SyncContext &cx = g_sync[dev];
+    const rt_denoise_params &P = *params;
+    const size_t n = static_cast<size_t>(P.width) * P.height;
+    // beauty, albedo, normal, depth, variance (inputs), out, scratch, variance_out, var_scratch
+    struct Plane { const float *host; uint32_t channels; size_t at; };
+    Plane planes[9] = {{buffers->beauty, 3, 0}, {buffers->albedo, 3, 0}, {buffers->normal, 3, 0}, {buffers->depth, 1, 0},
+                       {var->variance, 1, 0},   {buffers->out, 3, 0},    {P.levels > 1u ? buffers->out : nullptr, 3, 0},
+                       {var->variance_out, 1, 0}, {P.levels > 1u ? buffers->out : nullptr, 2, 0}};
+    size_t total = 0;
+    for (Plane &pl : planes)
+        if (pl.host) {
+            pl.at = total;
+            total += (n * pl.channels * 4u + 255u) & ~static_cast<size_t>(255u);
+        }
+    int rc = RT_OK;
+    auto chk = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+        return rc == RT_OK;
+    };
+    if (cx.dn_bytes < total || !cx.d_dn) {
+        if (cx.d_dn) chk(hipFree(cx.d_dn), "hipFree");
+        cx.d_dn = nullptr;
+        cx.dn_bytes = 0;
+        if (chk(hipMalloc(&cx.d_dn, std::max<size_t>(total, 256)), "hipMalloc")) cx.dn_bytes = total;
+    }
+    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
+    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
+    float ms = 0.f;
+    if (rc == RT_OK) {
+        char *base = static_cast<char *>(cx.d_dn);
+        auto dptr = [&](const Plane &pl) { return pl.host ? reinterpret_cast<float *>(base + pl.at) : nullptr; };
+        for (int i = 0; i < 5; ++i)
+            if (rc == RT_OK && planes[i].host)
+                chk(hipMemcpy(dptr(planes[i]), planes[i].host, n * planes[i].channels * 4u, hipMemcpyHostToDevice), "hipMemcpy");
+        rt_denoise_buffers d{static_cast<uint32_t>(sizeof(rt_denoise_buffers)), dptr(planes[0]), dptr(planes[1]),
+                             dptr(planes[2]), dptr(planes[3]), dptr(planes[5]), dptr(planes[6])};
+        rt_denoise_var_buffers dv{static_cast<uint32_t>(sizeof(rt_denoise_var_buffers)), var->var_floor, dptr(planes[4]),
+                                  dptr(planes[7]), dptr(planes[8])};
+        if (rc == RT_OK) chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
+        if (rc == RT_OK) rc = denoise_var_levels(P, d, dv, terms, nullptr);
+        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
+        // the copies on the null stream follow the kernels
+        if (rc == RT_OK) chk(hipMemcpy(buffers->out, d.out, n * 12u, hipMemcpyDeviceToHost), "hipMemcpy");
+        if (rc == RT_OK && var->variance_out)
+            chk(hipMemcpy(var->variance_out, dv.variance_out, n * 4u, hipMemcpyDeviceToHost), "hipMemcpy");
+        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_denoise_var");
+        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
+    }
+    if (rc != RT_OK) {
+        // a failed call leaves no state behind: the next one starts from a new context
+        const std::string msg = g_error;
+        sync_release(dev, cx);
+        g_error = msg;
+    }
+    if (rc == RT_OK && stats) {
+        *stats = rt_stats{};
+        stats->kernel_ms = ms;
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
+
+int rt_denoise_var_params_default(uint32_t width, uint32_t height, rt_denoise_params *params, rt_denoise_var_buffers *var)
+{
+    if (!params && !var) return fail(RT_ERR_INVALID, "rt_denoise_var_params_default: null argument");
+    if (!width || !height) return fail(RT_ERR_INVALID, "rt_denoise_var_params_default: zero width or height");
+    // chosen by the CPU sweep of DESIGN.md §4.10 (scripts/denoise_var_sweep.py)
+    if (params)
+        *params = rt_denoise_params{static_cast<uint32_t>(sizeof(rt_denoise_params)), width, height, kDnVarLevels,
+                                    kDnVarSigmaColor, kDnVarSigmaNormal, kDnVarSigmaDepth, kDnVarSigmaAlbedo, 0u};
+    if (var)
+        *var = rt_denoise_var_buffers{static_cast<uint32_t>(sizeof(rt_denoise_var_buffers)), kDnVarFloor, nullptr, nullptr,
+                                      nullptr};
+    return RT_OK;
+}
+
+int rt_denoise_var_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
+                          const rt_denoise_var_buffers *var, void *stream)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise_var(params, buffers, var, true, "rt_denoise_var_device", &terms); rc != RT_OK) return rc;
+    return denoise_var_levels(*params, *buffers, *var, terms, static_cast<hipStream_t>(stream));
+}
+
+int rt_denoise_var(const rt_denoise_params *params, const rt_denoise_buffers *buffers, const rt_denoise_var_buffers *var,
+                   rt_stats *stats)
+{
+    return denoise_var_host(params, buffers, var, stats);
+}
+
+int rt_render_var(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
+                  const rt_camera *camera, const rt_params *params, float *rgb_out, float *var_out, rt_stats *stats)
+{
+    return render_var_host(spheres, n_spheres, materials, n_materials, camera, params, rgb_out, var_out, stats);
+}
 
 int rt_denoise_params_default(uint32_t width, uint32_t height, rt_denoise_params *out)
 {

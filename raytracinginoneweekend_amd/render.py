@@ -207,6 +207,91 @@ def denoise_device(pointers, params, stream=None):
     check(lib().rt_denoise_device(C.byref(params), C.byref(rec), C.c_void_p(stream or 0)))
 
 
+def render_var(scene, params, camera=None):
+    """rt_render_var: the beauty as render_f32 returns it, float32 (rows, width,
+    3), and the variance of each pixel's mean luminance, float32 (rows, width); returns (rgb, var,
+    stats). Full frame: rows the call does not render hold 0."""
+    s, m = _scene_arrays(scene)
+    rows, w = _out_rows(params), params.width
+    rgb = np.zeros((rows, w, 3), dtype=np.float32)
+    var = np.zeros((rows, w), dtype=np.float32)
+    st = abi.RtStats()
+    check(lib().rt_render_var(abi.ptr(s, C.POINTER(abi.RtSphere)), len(s), abi.ptr(m, C.POINTER(abi.RtMaterial)),
+                              len(m), C.byref(_cam(camera, params)), C.byref(params),
+                              abi.ptr(rgb, C.POINTER(C.c_float)), abi.ptr(var, C.POINTER(C.c_float)), C.byref(st)))
+    return rgb, var, st
+
+
+def denoise_var_params(width, height, base=None, var_floor=None, direct=None, **fields):
+    """The records of a variance-guided denoise: (rt_denoise_params, rt_denoise_var_buffers) with
+    the library defaults for the image (rt_denoise_var_params_default; the params a copy of `base`
+    if given), then `fields` set as denoise_params sets them and var_floor, if given."""
+    p, v = abi.RtDenoiseParams(), abi.RtDenoiseVarBuffers()
+    check(lib().rt_denoise_var_params_default(width, height, C.byref(p), C.byref(v)))
+    if base is not None:
+        C.memmove(C.byref(p), C.byref(base), C.sizeof(p))
+        p.width, p.height = width, height
+    names = dict(abi.RtDenoiseParams._fields_)
+    for k, val in fields.items():
+        if k not in names or k in ("size", "width", "height"):
+            raise KeyError(f"rt_denoise_params has no field {k!r}")
+        setattr(p, k, val)
+    if direct is not None:
+        p.flags = (p.flags | abi.RT_DENOISE_DIRECT) if direct else (p.flags & ~abi.RT_DENOISE_DIRECT)
+    if var_floor is not None:
+        v.var_floor = var_floor
+    return p, v
+
+
+def denoise_var_buffers(pointers, var_floor):
+    """An rt_denoise_var_buffers record from a dict plane name (variance, variance_out,
+    var_scratch) -> address (absent or 0: not given)."""
+    unknown = set(pointers) - set(abi.DENOISE_VAR_PLANES)
+    if unknown:
+        raise KeyError(f"rt_denoise_var_buffers has no plane {sorted(unknown)!r}")
+    return abi.RtDenoiseVarBuffers(C.sizeof(abi.RtDenoiseVarBuffers), var_floor,
+                                   *(pointers.get(n) or None for n in abi.DENOISE_VAR_PLANES))
+
+
+def denoise_var(beauty, variance, albedo=None, normal=None, depth=None, variance_out=False, params=None,
+                stats=None, **fields):
+    """rt_denoise_var: the à-trous filter of `beauty` with its colour term steered
+    per pixel by `variance` (float32 (h, w), as render_var returns it); the guides as denoise takes
+    them. Returns float32 (h, w, 3), or (image, variance after the last level) with variance_out.
+    `fields` as denoise_var_params takes them (var_floor among them)."""
+    planes = {"beauty": beauty, "albedo": albedo, "normal": normal, "depth": depth, "variance": variance}
+    if beauty is None or np.ndim(beauty) != 3 or np.shape(beauty)[2] != 3:
+        raise ValueError(f"beauty must be float32 (h, w, 3), not {np.shape(beauty)}")
+    if variance is None:
+        raise ValueError("variance must be float32 (h, w)")
+    h, w = np.shape(beauty)[:2]
+    host = {}
+    for n, a in planes.items():
+        if a is None:
+            continue
+        want = (h, w, 3) if n != "variance" and abi.DENOISE_PLANES[n] == 3 else (h, w)
+        a = np.asarray(a)
+        if a.dtype != np.float32 or a.shape != want:
+            raise ValueError(f"{n} must be float32 {want}, not {a.dtype} {a.shape}")
+        host[n] = np.ascontiguousarray(a)
+    p, v = denoise_var_params(w, h, base=params, **fields)
+    out = np.zeros((h, w, 3), dtype=np.float32)
+    vout = np.zeros((h, w), dtype=np.float32) if variance_out else None
+    rec = denoise_buffers({**{n: a.ctypes.data for n, a in host.items() if n != "variance"}, "out": out.ctypes.data})
+    vrec = denoise_var_buffers({"variance": host["variance"].ctypes.data,
+                                "variance_out": vout.ctypes.data if variance_out else 0}, v.var_floor)
+    check(lib().rt_denoise_var(C.byref(p), C.byref(rec), C.byref(vrec), C.byref(stats) if stats is not None else None))
+    return (out, vout) if variance_out else out
+
+
+def denoise_var_device(pointers, params, var_record, stream=None):
+    """Enqueue rt_denoise_var_device on `stream`: `pointers` as denoise_device takes them, `params`
+    an rt_denoise_params record, `var_record` an rt_denoise_var_buffers record of device addresses
+    (denoise_var_buffers). One launch per level, no host synchronisation."""
+    rec = denoise_buffers(pointers)
+    check(lib().rt_denoise_var_device(C.byref(params), C.byref(rec), C.byref(var_record), C.c_void_p(stream or 0)))
+
+
 def tile_order(scene, params, camera=None):
     """rt_tile_order: the pass's 64-pixel blocks in dealing order as
     (perm, n_lead, n_sky); perm is empty when the pass keeps the natural order."""
@@ -346,6 +431,14 @@ class DeviceScene:
         rec = aov_buffers(buffers, samples)
         check(lib().rt_render_aov_device(self.handle, C.byref(_cam(camera, params)), C.byref(params), C.byref(rec),
                                          C.c_void_p(stream or 0)))
+
+    def render_var(self, camera, params, rgb_ptr, var_ptr, stream=None, segments=None):
+        """Enqueue rt_render_var_device on `stream`: the beauty into device address rgb_ptr as
+        render() writes it, the variance of each pixel's mean luminance (one float per pixel,
+        laid out as `params` says) into var_ptr. segments: optional device int64[3], as render()."""
+        check(lib().rt_render_var_device(self.handle, C.byref(_cam(camera, params)), C.byref(params),
+                                         C.c_void_p(rgb_ptr), C.c_void_p(var_ptr), C.c_void_p(stream or 0),
+                                         C.c_void_p(segments) if segments else None))
 
     def usage(self):
         """rt_scene_usage_get: device bytes held and the last render's cut, as a dict."""
