@@ -507,6 +507,104 @@ int rt_denoise_var_device(const rt_denoise_params *params, const rt_denoise_buff
 int rt_denoise_var(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
                    const rt_denoise_var_buffers *var, rt_stats *stats);
 
+/* ---- temporal accumulation: the last frame's history reprojected ----------
+ * The stage between rt_render_var / rt_render_aov and rt_denoise_var (SVGF, Schied et al. 2017,
+ * §4.1): every pixel of the current frame reconstructs its first hit, projects it into the previous
+ * camera, resamples the previous frame's accumulated colour, variance and history length under
+ * consistency tests, and blends. The scene is static, so motion is camera motion and comes from the
+ * two rt_camera records. All arithmetic is binary32, every operation rounded on its own, in the order
+ * written; divisions are IEEE divisions.
+ *
+ * Planes are packed row-major, width x height, exactly as rt_render_var and rt_render_aov write them
+ * (the guides of the frame's samples). Current frame, all required: beauty[h][w][3], variance[h][w],
+ * normal[h][w][3], depth[h][w], alpha[h][w], sphere_id[h][w]. Previous frame, all given or all NULL
+ * (NULL: no history exists yet): prev_color[h][w][3], prev_variance[h][w], prev_history[h][w] (float),
+ * prev_normal, prev_depth, prev_sphere_id. Outputs, all required: out_color, out_variance,
+ * out_history. The caller ping-pongs; what it feeds back as prev_color is its choice: out_color, or,
+ * as SVGF does, the first filter level's output.
+ *
+ * Projection record (rt_reproject_basis, on the host). With h', v', llc', o' the previous camera's
+ * horizontal, vertical, lower_left_corner and origin:
+ *   a'          = llc' (RT_CAMERA_REFERENCE) or llc' - o' componentwise (RT_CAMERA_CORRECTED)
+ *   cross(x, y) = (x.y y.z - x.z y.y, x.z y.x - x.x y.z, x.x y.y - x.y y.x), each product rounded
+ *   dot(x, y)   = (x.x y.x + x.y y.y) + x.z y.z
+ *   D = dot(h', cross(v', a'));  A = cross(v', a') / D, B = cross(a', h') / D, G = cross(h', v') / D
+ *   out = {A, B, G, o'}
+ * D = 0 or a non-finite entry of out is RT_ERR_INVALID (prev_camera). For q = P - o' the Cramer
+ * solution of [h' v' a'] (al, be, ga) = q is al = dot(A, q), be = dot(B, q), ga = dot(G, q): ga is
+ * P's ray parameter in the previous camera (what its depth plane stores), and P projects to
+ * u' = al / ga, 1 - v' = be / ga. In REFERENCE mode too: that mode's rays have the image-plane point
+ * itself as their direction.
+ *
+ * Per pixel p = (x, y), with a formed from the current camera as a' above, o, hor, ver its origin,
+ * horizontal and vertical:
+ *   1 class   alpha(p) == 1.0f: surface; alpha(p) == 0.0f: sky; anything else: edge, no history
+ *   2 ray     u = ((float)x + 0.5f) / (float)w;  m = 1.0f - ((float)y + 0.5f) / (float)h
+ *             d = (a + hor * u) + ver * m, componentwise (the pinhole ray through the pixel centre)
+ *   3 q       surface: q = (o + depth(p) * d) - o';  sky: q = d (the point at infinity: the sky is
+ *             stable under rotation)
+ *   4 project al, be, ga as above; no history unless ga > 0.0f
+ *             px = (al / ga) * (float)w - 0.5f;  py = (1.0f - be / ga) * (float)h - 0.5f
+ *             no history unless px > -1.0f && px < (float)w && py > -1.0f && py < (float)h (false
+ *             for NaN)
+ *   5 taps    fx = floorf(px), tx = px - fx, ix = (int)fx; fy, ty, iy likewise. The taps
+ *             t = (ix + i, iy + j), j = 0, 1 (outer loop), i = 0, 1 (inner loop), with
+ *             wgt = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty). A tap is skipped (nothing is added)
+ *             when it lies outside the image, or prev_sphere_id(t) != sphere_id(p), or
+ *             d2 > normal_tol with dn = prev_normal(t) - normal(p) per component and
+ *             d2 = (dn.x dn.x + dn.y dn.y) + dn.z dn.z, or, for a surface pixel,
+ *             fabsf(prev_depth(t) - ga) > depth_tol * ga. (Sky pixels have id 0xffffffff, normal 0
+ *             and depth 0 on both sides and take no depth test.) From sumw = sum[3] = sumv = sumn = 0:
+ *             sumw = sumw + wgt;  sum[c] = sum[c] + wgt * prev_color(t)[c]
+ *             sumv = sumv + (wgt * wgt) * prev_variance(t);  sumn = sumn + wgt * prev_history(t)
+ *   6 blend   history exists iff sumw >= 0.01f. Then C_h[c] = sum[c] / sumw,
+ *             V_h = sumv / (sumw * sumw) (the variance of a weighted mean, as §4.10's levels),
+ *             N_h = sumn / sumw;  N = fminf(N_h + 1.0f, max_history);  k = fmaxf(1.0f / N, alpha_min)
+ *             out_color(p)[c] = k * beauty(p)[c] + (1.0f - k) * C_h[c]
+ *             out_variance(p) = (k * k) * variance(p) + ((1.0f - k) * (1.0f - k)) * V_h (the frames
+ *             taken as independent estimates);  out_history(p) = N
+ *   7 no history (any reason above, or prev NULL): out_color(p) = beauty(p), out_variance(p) =
+ *             variance(p), copies of the bits, and out_history(p) = 1.0f
+ * Ten divisions per pixel with history: two for the pixel centre, two for the projection, five for
+ * the resample, one for k. SVGF's 3x3 search when all four taps fail and its spatial variance
+ * estimate for short histories are left out. NaN or infinite plane values give
+ * unspecified output values; no tap is read outside the image whatever the values are.
+ *
+ * Every argument is checked before any HIP call; RT_ERR_INVALID names the field: a wrong size, zero
+ * width or height (or one above 65536), alpha_min outside (0, 1], max_history < 1, a negative
+ * normal_tol or depth_tol, a non-finite parameter, nonzero flags, a null camera, a null required
+ * plane, prev partly given, an output plane equal to an input plane or to another output plane, and,
+ * when prev is given, a null or degenerate prev_camera (ignored otherwise).                        */
+typedef struct rt_temporal_params {
+    uint32_t size;            /* sizeof(rt_temporal_params): the record's revision               */
+    uint32_t width, height;
+    float alpha_min;          /* 0 < alpha_min <= 1: the least weight of the current frame        */
+    float max_history;        /* >= 1: the cap of the history length                              */
+    float normal_tol;         /* >= 0: the largest squared normal distance of an accepted tap     */
+    float depth_tol;          /* >= 0: the largest relative depth difference of an accepted tap   */
+    uint32_t flags;           /* none defined: must be 0                                          */
+} rt_temporal_params;
+typedef struct rt_temporal_buffers {
+    uint32_t size;            /* sizeof(rt_temporal_buffers)                                      */
+    const float *beauty, *variance, *normal, *depth, *alpha;
+    const uint32_t *sphere_id;
+    const float *prev_color, *prev_variance, *prev_history, *prev_normal, *prev_depth;
+    const uint32_t *prev_sphere_id;
+    float *out_color, *out_variance, *out_history;
+} rt_temporal_buffers;
+/* The defaults (DESIGN.md §4.11 records the sweep that chose them) for a width x height image.   */
+int rt_temporal_params_default(uint32_t width, uint32_t height, rt_temporal_params *out);
+/* The projection record {A, B, G, o'} of a previous camera, as stated above. Host-only.          */
+int rt_reproject_basis(const rt_camera *prev, float out[12]);
+/* Device pointers on the current device; one launch on `stream` (a hipStream_t, or NULL), no host
+ * synchronisation, no allocation.                                                                 */
+int rt_temporal_device(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                       const rt_temporal_buffers *buffers, void *stream);
+/* Host pointers, synchronous; the device planes are the library's (kept in the cached per-device
+ * context rt_release_cached frees). stats (optional): kernel_ms, wall_ms; the counters are 0.     */
+int rt_temporal(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                const rt_temporal_buffers *buffers, rt_stats *stats);
+
 /* Device memory a scene holds and how its renders are cut (after the last render call).  */
 typedef struct rt_scene_usage {
     uint64_t device_bytes;     /* every device allocation of the scene                       */

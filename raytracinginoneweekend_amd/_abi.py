@@ -131,6 +131,31 @@ class RtDenoiseVarBuffers(C.Structure):
     ]
 
 
+class RtTemporalParams(C.Structure):
+    """rt_temporal_params (include/rt_api.h): the temporal accumulation's image size, blend and tests."""
+    _fields_ = [
+        ("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+        ("alpha_min", C.c_float), ("max_history", C.c_float), ("normal_tol", C.c_float), ("depth_tol", C.c_float),
+        ("flags", C.c_uint32),
+    ]
+
+
+# the planes of rt_temporal_buffers, in the record's order: name -> (channels, numpy dtype)
+TEMPORAL_PLANES = {
+    "beauty": (3, np.float32), "variance": (1, np.float32), "normal": (3, np.float32), "depth": (1, np.float32),
+    "alpha": (1, np.float32), "sphere_id": (1, np.uint32),
+    "prev_color": (3, np.float32), "prev_variance": (1, np.float32), "prev_history": (1, np.float32),
+    "prev_normal": (3, np.float32), "prev_depth": (1, np.float32), "prev_sphere_id": (1, np.uint32),
+    "out_color": (3, np.float32), "out_variance": (1, np.float32), "out_history": (1, np.float32),
+}
+
+
+class RtTemporalBuffers(C.Structure):
+    """rt_temporal_buffers (include/rt_api.h): the current frame's planes, the previous frame's (all
+    NULL: no history yet) and the outputs of a temporal accumulation."""
+    _fields_ = [("size", C.c_uint32)] + [(n, C.c_void_p) for n in TEMPORAL_PLANES]
+
+
 # the planes of rt_denoise_buffers: name -> channels
 DENOISE_PLANES = {"beauty": 3, "albedo": 3, "normal": 3, "depth": 1, "out": 3, "scratch": 3}
 
@@ -150,6 +175,7 @@ assert C.sizeof(RtOptions) == 64 and C.sizeof(RtSceneUsage) == 56
 assert C.sizeof(RtAovBuffers) == 48
 assert C.sizeof(RtDenoiseParams) == 36 and C.sizeof(RtDenoiseBuffers) == 56
 assert C.sizeof(RtDenoiseVarBuffers) == 32
+assert C.sizeof(RtTemporalParams) == 32 and C.sizeof(RtTemporalBuffers) == 128
 
 
 def ptr(arr, ctype=C.c_void_p):

@@ -91,6 +91,12 @@ def _declare(L):
                                             P(abi.RtDenoiseVarBuffers), C.c_void_p]),
         "rt_denoise_var": (C.c_int, [P(abi.RtDenoiseParams), P(abi.RtDenoiseBuffers), P(abi.RtDenoiseVarBuffers),
                                      P(abi.RtStats)]),
+        "rt_temporal_params_default": (C.c_int, [C.c_uint32, C.c_uint32, P(abi.RtTemporalParams)]),
+        "rt_reproject_basis": (C.c_int, [P(abi.RtCamera), P(C.c_float)]),
+        "rt_temporal_device": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera),
+                                         P(abi.RtTemporalBuffers), C.c_void_p]),
+        "rt_temporal": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera), P(abi.RtTemporalBuffers),
+                                  P(abi.RtStats)]),
         "rt_scene_kernel_times": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float), P(C.c_uint32)]),
         "rt_scene_debug_counters": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_int]),
         "rt_scene_debug_timeline": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_uint32, P(C.c_uint32)]),

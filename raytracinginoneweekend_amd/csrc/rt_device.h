@@ -272,6 +272,22 @@ struct KDenoiseVar {
     float sc2, var_floor;       // sigma_color^2 (formed on the host) and the floor of the colour term
 };
 
+// The temporal accumulation (rt_temporal.hip; rt_temporal_device): the current
+// frame's planes, the previous frame's (p_color null: no history, the launch copies), the outputs,
+// the current camera as the contract's {a, hor, ver, o} and the previous one as rt_reproject_basis's
+// record {A, B, G, o'}, both formed on the host.
+struct KTemporal {
+    const float *beauty, *variance, *normal, *depth, *alpha;
+    const uint32_t *id;
+    const float *p_color, *p_variance, *p_history, *p_normal, *p_depth;
+    const uint32_t *p_id;
+    float *o_color, *o_variance, *o_history;
+    uint32_t W, H;
+    float a[3], hor[3], ver[3], o[3];
+    float basis[12];
+    float alpha_min, max_history, normal_tol, depth_tol;
+};
+
 // The wavefront variant's ray queue (structure of arrays, capacity cap rays): f = [9][cap]
 // floats {o.xyz, d.xyz, attenuation.xyz}, then the data-stream state, the item index (slot) and
 // the segment count of each ray; count = rays in the queue.

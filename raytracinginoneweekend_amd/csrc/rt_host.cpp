@@ -52,6 +52,8 @@ hipError_t static_lds_aov(int cull, size_t *bytes);
 hipError_t launch_denoise(const KDenoise &k, uint32_t terms, bool demod_in, bool tiled, hipStream_t stream);
 hipError_t launch_denoise_var(const KDenoiseVar &k, uint32_t terms, hipStream_t stream);
 size_t denoise_tiled_lds(uint32_t terms, uint32_t step);
+// rt_temporal.hip
+hipError_t launch_temporal(const KTemporal &k, hipStream_t stream);
 } // namespace rt
 
 namespace {
@@ -2274,9 +2276,173 @@ int denoise_var_host(const rt_denoise_params *params, const rt_denoise_buffers *
     return rc;
 }
 
+// ---- temporal accumulation (include/rt_api.h; kernel in rt_temporal.hip) ------
+// rt_temporal_params_default: the values scripts/temporal_sweep.py chose
+constexpr float kTpAlphaMin = 0.4f, kTpMaxHistory = 32.0f, kTpNormalTol = 0.5f, kTpDepthTol = 0.1f;
+
+// Every argument check, before any HIP call; fills the kernel's record (the cameras as the
+// contract's {a, hor, ver, o} and {A, B, G, o'}) from the caller's pointers.
+int check_temporal(const rt_temporal_params *p, const rt_camera *cam, const rt_camera *prev_cam,
+                   const rt_temporal_buffers *b, const char *who, rt::KTemporal *k)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!p || !b) return fail(RT_ERR_INVALID, w + "null argument");
+    if (p->size != sizeof(rt_temporal_params)) return fail(RT_ERR_INVALID, w + "params.size is not sizeof(rt_temporal_params)");
+    if (b->size != sizeof(rt_temporal_buffers)) return fail(RT_ERR_INVALID, w + "buffers.size is not sizeof(rt_temporal_buffers)");
+    if (!p->width || p->width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
+    if (!p->height || p->height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    if (!std::isfinite(p->alpha_min) || !(p->alpha_min > 0.f) || p->alpha_min > 1.f)
+        return fail(RT_ERR_INVALID, w + "alpha_min must be above 0 and at most 1");
+    if (!std::isfinite(p->max_history) || p->max_history < 1.f) return fail(RT_ERR_INVALID, w + "max_history must be finite and at least 1");
+    if (!std::isfinite(p->normal_tol) || p->normal_tol < 0.f) return fail(RT_ERR_INVALID, w + "normal_tol must be finite and not negative");
+    if (!std::isfinite(p->depth_tol) || p->depth_tol < 0.f) return fail(RT_ERR_INVALID, w + "depth_tol must be finite and not negative");
+    if (p->flags) return fail(RT_ERR_INVALID, w + "flags must be 0 (none is defined)");
+    if (!cam) return fail(RT_ERR_INVALID, w + "camera is null");
+    if (cam->mode > RT_CAMERA_CORRECTED) return fail(RT_ERR_INVALID, w + "camera has a bad mode");
+    const struct { const char *name; const void *ptr; } cur[6] = {{"beauty", b->beauty}, {"variance", b->variance}, {"normal", b->normal},
+                                                                 {"depth", b->depth},   {"alpha", b->alpha},       {"sphere_id", b->sphere_id}},
+      prev[6] = {{"prev_color", b->prev_color},   {"prev_variance", b->prev_variance}, {"prev_history", b->prev_history},
+                 {"prev_normal", b->prev_normal}, {"prev_depth", b->prev_depth},       {"prev_sphere_id", b->prev_sphere_id}},
+      out[3] = {{"out_color", b->out_color}, {"out_variance", b->out_variance}, {"out_history", b->out_history}};
+    for (const auto &c : cur)
+        if (!c.ptr) return fail(RT_ERR_INVALID, w + c.name + " is null");
+    for (const auto &o : out)
+        if (!o.ptr) return fail(RT_ERR_INVALID, w + o.name + " is null");
+    int given = 0;
+    for (const auto &c : prev) given += c.ptr ? 1 : 0;
+    if (given != 0 && given != 6)
+        for (const auto &c : prev)
+            if (!c.ptr) return fail(RT_ERR_INVALID, w + c.name + " is null while other planes of prev are given");
+    for (int i = 0; i < 3; ++i) {
+        for (const auto &c : cur)
+            if (c.ptr == out[i].ptr) return fail(RT_ERR_INVALID, w + out[i].name + " is also the input plane " + c.name);
+        for (const auto &c : prev)
+            if (c.ptr == out[i].ptr) return fail(RT_ERR_INVALID, w + out[i].name + " is also the input plane " + c.name);
+        for (int j = 0; j < i; ++j)
+            if (out[j].ptr == out[i].ptr) return fail(RT_ERR_INVALID, w + out[i].name + " is also " + out[j].name);
+    }
+    rt::KTemporal t{};
+    if (given) {
+        if (!prev_cam) return fail(RT_ERR_INVALID, w + "prev_camera is null");
+        if (rt_reproject_basis(prev_cam, t.basis) != RT_OK) return fail(RT_ERR_INVALID, w + g_error.substr(g_error.find(": ") + 2));
+    }
+    t.beauty = b->beauty, t.variance = b->variance, t.normal = b->normal, t.depth = b->depth, t.alpha = b->alpha;
+    t.id = b->sphere_id;
+    t.p_color = b->prev_color, t.p_variance = b->prev_variance, t.p_history = b->prev_history;
+    t.p_normal = b->prev_normal, t.p_depth = b->prev_depth, t.p_id = b->prev_sphere_id;
+    t.o_color = b->out_color, t.o_variance = b->out_variance, t.o_history = b->out_history;
+    t.W = p->width, t.H = p->height;
+    for (int c = 0; c < 3; ++c) {
+        t.a[c] = cam->mode == RT_CAMERA_CORRECTED ? cam->lower_left_corner[c] - cam->origin[c] : cam->lower_left_corner[c];
+        t.hor[c] = cam->horizontal[c], t.ver[c] = cam->vertical[c], t.o[c] = cam->origin[c];
+    }
+    t.alpha_min = p->alpha_min, t.max_history = p->max_history, t.normal_tol = p->normal_tol, t.depth_tol = p->depth_tol;
+    *k = t;
+    return RT_OK;
+}
+
+// Synchronous temporal accumulation of host planes through the cached context's buffer.
+int temporal_host(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                  const rt_temporal_buffers *buffers, rt_stats *stats)
+{
+    rt::KTemporal k{};
+    if (int rc = check_temporal(params, camera, prev_camera, buffers, "rt_temporal", &k); rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    int dev = 0;
+    RT_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_sync_mu);
+    SyncContext &cx = g_sync[dev];
+    const size_t n = static_cast<size_t>(params->width) * params->height;
+    // the current planes, the previous ones (inputs), then the outputs, 256-byte aligned
+    struct Plane { const void *host; uint32_t channels; size_t at; };
+    Plane planes[15] = {{buffers->beauty, 3, 0},       {buffers->variance, 1, 0},      {buffers->normal, 3, 0},
+                        {buffers->depth, 1, 0},        {buffers->alpha, 1, 0},         {buffers->sphere_id, 1, 0},
+                        {buffers->prev_color, 3, 0},   {buffers->prev_variance, 1, 0}, {buffers->prev_history, 1, 0},
+                        {buffers->prev_normal, 3, 0},  {buffers->prev_depth, 1, 0},    {buffers->prev_sphere_id, 1, 0},
+                        {buffers->out_color, 3, 0},    {buffers->out_variance, 1, 0},  {buffers->out_history, 1, 0}};
+    size_t total = 0;
+    for (Plane &pl : planes)
+        if (pl.host) {
+            pl.at = total;
+            total += (n * pl.channels * 4u + 255u) & ~static_cast<size_t>(255u);
+        }
+    int rc = RT_OK;
+    auto chk = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+        return rc == RT_OK;
+    };
+    if (cx.dn_bytes < total || !cx.d_dn) {
+        if (cx.d_dn) chk(hipFree(cx.d_dn), "hipFree");
+        cx.d_dn = nullptr;
+        cx.dn_bytes = 0;
+        if (chk(hipMalloc(&cx.d_dn, std::max<size_t>(total, 256)), "hipMalloc")) cx.dn_bytes = total;
+    }
+    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
+    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
+    float ms = 0.f;
+    if (rc == RT_OK) {
+        char *base = static_cast<char *>(cx.d_dn);
+        auto fptr = [&](int i) { return planes[i].host ? reinterpret_cast<float *>(base + planes[i].at) : nullptr; };
+        auto uptr = [&](int i) { return planes[i].host ? reinterpret_cast<uint32_t *>(base + planes[i].at) : nullptr; };
+        for (int i = 0; i < 12; ++i)
+            if (rc == RT_OK && planes[i].host)
+                chk(hipMemcpy(base + planes[i].at, planes[i].host, n * planes[i].channels * 4u, hipMemcpyHostToDevice), "hipMemcpy");
+        k.beauty = fptr(0), k.variance = fptr(1), k.normal = fptr(2), k.depth = fptr(3), k.alpha = fptr(4), k.id = uptr(5);
+        k.p_color = fptr(6), k.p_variance = fptr(7), k.p_history = fptr(8), k.p_normal = fptr(9), k.p_depth = fptr(10);
+        k.p_id = uptr(11);
+        k.o_color = fptr(12), k.o_variance = fptr(13), k.o_history = fptr(14);
+        if (rc == RT_OK) chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
+        if (rc == RT_OK) chk(rt::launch_temporal(k, nullptr), "rt_temporal");
+        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
+        // the copies on the null stream follow the kernel
+        for (int i = 12; i < 15; ++i)
+            if (rc == RT_OK)
+                chk(hipMemcpy(const_cast<void *>(planes[i].host), base + planes[i].at, n * planes[i].channels * 4u, hipMemcpyDeviceToHost),
+                    "hipMemcpy");
+        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_temporal");
+        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
+    }
+    if (rc != RT_OK) {
+        // a failed call leaves no state behind: the next one starts from a new context
+        const std::string msg = g_error;
+        sync_release(dev, cx);
+        g_error = msg;
+    }
+    if (rc == RT_OK && stats) {
+        *stats = rt_stats{};
+        stats->kernel_ms = ms;
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
+
+int rt_temporal_params_default(uint32_t width, uint32_t height, rt_temporal_params *out)
+{
+    if (!out) return fail(RT_ERR_INVALID, "rt_temporal_params_default: null argument");
+    if (!width || !height) return fail(RT_ERR_INVALID, "rt_temporal_params_default: zero width or height");
+    *out = rt_temporal_params{static_cast<uint32_t>(sizeof(rt_temporal_params)), width, height, kTpAlphaMin, kTpMaxHistory,
+                              kTpNormalTol, kTpDepthTol, 0u};
+    return RT_OK;
+}
+
+int rt_temporal_device(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                       const rt_temporal_buffers *buffers, void *stream)
+{
+    rt::KTemporal k{};
+    if (int rc = check_temporal(params, camera, prev_camera, buffers, "rt_temporal_device", &k); rc != RT_OK) return rc;
+    RT_HIP(rt::launch_temporal(k, static_cast<hipStream_t>(stream)));
+    return RT_OK;
+}
+
+int rt_temporal(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                const rt_temporal_buffers *buffers, rt_stats *stats)
+{
+    return temporal_host(params, camera, prev_camera, buffers, stats);
+}
 
 int rt_denoise_var_params_default(uint32_t width, uint32_t height, rt_denoise_params *params, rt_denoise_var_buffers *var)
 {

@@ -272,6 +272,30 @@ int rt_camera_default(uint32_t width, uint32_t height, uint32_t mode, rt_camera 
                           focus, mode, out);
 }
 
+// The temporal accumulation's projection record (include/rt_api.h): the Cramer
+// rows of [h' v' a'] and the previous origin.
+int rt_reproject_basis(const rt_camera *prev, float out[12])
+{
+    if (!prev || !out) return fail(RT_ERR_INVALID, "rt_reproject_basis: null argument");
+    if (prev->mode > RT_CAMERA_CORRECTED) return fail(RT_ERR_INVALID, "rt_reproject_basis: prev_camera has a bad mode");
+    const hv o{prev->origin[0], prev->origin[1], prev->origin[2]};
+    const hv llc{prev->lower_left_corner[0], prev->lower_left_corner[1], prev->lower_left_corner[2]};
+    const hv h{prev->horizontal[0], prev->horizontal[1], prev->horizontal[2]};
+    const hv v{prev->vertical[0], prev->vertical[1], prev->vertical[2]};
+    const hv a = prev->mode == RT_CAMERA_CORRECTED ? llc - o : llc;
+    const hv va = hcross(v, a), ah = hcross(a, h), hv_ = hcross(h, v);
+    const float D = (h.x * va.x + h.y * va.y) + h.z * va.z;
+    const float r[12] = {va.x / D, va.y / D, va.z / D, ah.x / D, ah.y / D, ah.z / D,
+                         hv_.x / D, hv_.y / D, hv_.z / D, o.x, o.y, o.z};
+    bool finite = D != 0.f;
+    for (float f : r) finite = finite && std::isfinite(f);
+    if (!finite)
+        return fail(RT_ERR_INVALID, "rt_reproject_basis: prev_camera is degenerate (horizontal, vertical and the "
+                                    "image-plane corner do not span space, or an entry is not finite)");
+    std::memcpy(out, r, sizeof(r));
+    return RT_OK;
+}
+
 } // extern "C"
 
 namespace {

@@ -292,6 +292,94 @@ def denoise_var_device(pointers, params, var_record, stream=None):
     check(lib().rt_denoise_var_device(C.byref(params), C.byref(rec), C.byref(var_record), C.c_void_p(stream or 0)))
 
 
+def temporal_params(width, height, base=None, **fields):
+    """An rt_temporal_params record: the library defaults for the image (or a copy of `base`) with
+    `fields` set (alpha_min, max_history, normal_tol, depth_tol, flags)."""
+    p = abi.RtTemporalParams()
+    if base is None:
+        check(lib().rt_temporal_params_default(width, height, C.byref(p)))
+    else:
+        C.memmove(C.byref(p), C.byref(base), C.sizeof(p))
+        p.width, p.height = width, height
+    names = dict(abi.RtTemporalParams._fields_)
+    for k, v in fields.items():
+        if k not in names or k in ("size", "width", "height"):
+            raise KeyError(f"rt_temporal_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def temporal_buffers(pointers):
+    """An rt_temporal_buffers record from a dict plane name (abi.TEMPORAL_PLANES: the current
+    frame's beauty, variance, normal, depth, alpha, sphere_id; prev_color, prev_variance,
+    prev_history, prev_normal, prev_depth, prev_sphere_id; out_color, out_variance, out_history)
+    -> address (absent or 0: not given)."""
+    unknown = set(pointers) - set(abi.TEMPORAL_PLANES)
+    if unknown:
+        raise KeyError(f"rt_temporal_buffers has no plane {sorted(unknown)!r}")
+    return abi.RtTemporalBuffers(C.sizeof(abi.RtTemporalBuffers), *(pointers.get(n) or None for n in abi.TEMPORAL_PLANES))
+
+
+def _cam_record(camera):
+    return camera.c if isinstance(camera, Camera) else camera
+
+
+def reproject_basis(camera):
+    """rt_reproject_basis: the projection record {A, B, G, o'} of a previous camera (DESIGN.md
+    §4.11) as float32 (12,). Host-only."""
+    out = np.zeros(12, dtype=np.float32)
+    check(lib().rt_reproject_basis(C.byref(_cam_record(camera)), abi.ptr(out, C.POINTER(C.c_float))))
+    return out
+
+
+def temporal_device(pointers, params, camera, prev_camera, stream=None):
+    """Enqueue rt_temporal_device on `stream`: `pointers` is a dict plane name -> device address on
+    the current device (temporal_buffers; the prev_ planes all absent: no history yet), `params` an
+    rt_temporal_params record, `camera` and `prev_camera` the two frames' cameras (prev_camera may be
+    None without history). One launch, no host synchronisation."""
+    rec = temporal_buffers(pointers)
+    check(lib().rt_temporal_device(C.byref(params), C.byref(_cam_record(camera)),
+                                   C.byref(_cam_record(prev_camera)) if prev_camera is not None else None,
+                                   C.byref(rec), C.c_void_p(stream or 0)))
+
+
+_TEMPORAL_CUR = ("beauty", "variance", "normal", "depth", "alpha", "sphere_id")
+_TEMPORAL_PREV = ("color", "variance", "history", "normal", "depth", "sphere_id")
+
+
+def temporal(cur, prev, camera, prev_camera, params=None, stats=None, **fields):
+    """rt_temporal: the previous frame's history reprojected into the current
+    frame and blended. cur: dict of the current frame's planes (beauty and variance as render_var
+    returns them; normal, depth, alpha, sphere_id as render_aov does); prev: dict of the previous
+    frame's (color, variance, history as this call returned them, or color after a filter level;
+    normal, depth, sphere_id of that frame), or None: no history yet. Returns (color float32 (h, w,
+    3), variance float32 (h, w), history float32 (h, w)). params: an rt_temporal_params record
+    (default: the library's for this size); `fields` as temporal_params takes them."""
+    if set(cur) != set(_TEMPORAL_CUR):
+        raise KeyError(f"cur must hold exactly the planes {_TEMPORAL_CUR}, not {sorted(cur)}")
+    if prev is not None and set(prev) != set(_TEMPORAL_PREV):
+        raise KeyError(f"prev must hold exactly the planes {_TEMPORAL_PREV}, not {sorted(prev)}")
+    if np.ndim(cur["beauty"]) != 3 or np.shape(cur["beauty"])[2] != 3:
+        raise ValueError(f"beauty must be float32 (h, w, 3), not {np.shape(cur['beauty'])}")
+    h, w = np.shape(cur["beauty"])[:2]
+    host = {}
+    for n, a in [(n, cur[n]) for n in _TEMPORAL_CUR] + [("prev_" + n, prev[n]) for n in _TEMPORAL_PREV if prev is not None]:
+        ch, dt = abi.TEMPORAL_PLANES[n]
+        want = (h, w, 3) if ch == 3 else (h, w)
+        a = np.asarray(a)
+        if a.dtype != dt or a.shape != want:
+            raise ValueError(f"{n} must be {np.dtype(dt).name} {want}, not {a.dtype} {a.shape}")
+        host[n] = np.ascontiguousarray(a)
+    p = temporal_params(w, h, base=params, **fields)
+    out = {n: np.zeros((h, w, 3) if abi.TEMPORAL_PLANES[n][0] == 3 else (h, w), dtype=np.float32)
+           for n in ("out_color", "out_variance", "out_history")}
+    rec = temporal_buffers({n: a.ctypes.data for n, a in {**host, **out}.items()})
+    check(lib().rt_temporal(C.byref(p), C.byref(_cam_record(camera)),
+                            C.byref(_cam_record(prev_camera)) if prev_camera is not None else None, C.byref(rec),
+                            C.byref(stats) if stats is not None else None))
+    return out["out_color"], out["out_variance"], out["out_history"]
+
+
 def tile_order(scene, params, camera=None):
     """rt_tile_order: the pass's 64-pixel blocks in dealing order as
     (perm, n_lead, n_sky); perm is empty when the pass keeps the natural order."""
