@@ -1,8 +1,10 @@
 // rt_host.cpp — the device half of the C-ABI's host side (include/rt_api.h): device scene upload,
 // pass planning under the scene's options, frames in flight, the render entry points that replace
-// `cuda_impl` (src/main.cxx:18, src/CUDA/cuda_impl.cu:384) and the multi-GPU context. The
-// host-only half (camera and scene constructors, cluster builder, options, PPM writer) is
-// rt_host_build.cpp.
+// `cuda_impl` (src/main.cxx:18, src/CUDA/cuda_impl.cu:384), the cached context of the synchronous
+// host-buffer calls with the one path they all take through it (rt_host_sync.h SyncCall), and the
+// multi-GPU context. The filters and temporal accumulation are rt_host_post.cpp; the host-only
+// half (camera and scene constructors, cluster builder, options, PPM writer, the synchronous
+// calls' plane layout) is rt_host_build.cpp.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -25,47 +27,15 @@
 #include "../../include/rt_api.h"
 #include "rt_device.h"
 #include "rt_host_build.h"
+#include "rt_host_sync.h"
 
 using namespace rthost;
 
-namespace rt {
-hipError_t launch_render(int variant, int cull, const KParams &p, uint32_t grid, hipStream_t stream, int wpb = 4);
 #ifndef RT_LONE_DEEP_TMAX
 #define RT_LONE_DEEP_TMAX 4u  // the lone deep launch's transposition threshold (below)
 #endif
-hipError_t deep_occupancy(int variant, int wpb, size_t lds, int *blocks_per_cu, size_t *static_lds);
-hipError_t occupancy_render(int variant, int cull, int *blocks_per_cu, size_t lds, bool pairs = false);
-hipError_t static_lds_render(int variant, int cull, size_t *bytes, bool pairs = false);
-hipError_t launch_accumulate(const KAccum &k, hipStream_t stream);
-hipError_t launch_compat(const KCompat &k, uint32_t grid, hipStream_t stream);
-hipError_t launch_wave_gen(const KWave &w, hipStream_t stream);
-hipError_t launch_wave_bounce(int cull, const KWave &w, uint32_t grid, hipStream_t stream);
-hipError_t occupancy_wave_bounce(int cull, int *blocks_per_cu, size_t lds);
-hipError_t occupancy_compat(int *blocks_per_cu);
-hipError_t launch_epilogue(const float *in, uint8_t *out, uint64_t n, hipStream_t stream);
-hipError_t launch_sky(const KSky &k, hipStream_t stream);
-// rt_aov.hip
-hipError_t launch_aov(int cull, const KAov &k, uint32_t grid, hipStream_t stream);
-hipError_t occupancy_aov(int cull, int *blocks_per_cu, size_t lds);
-hipError_t static_lds_aov(int cull, size_t *bytes);
-// rt_denoise.hip
-hipError_t launch_denoise(const KDenoise &k, uint32_t terms, bool demod_in, bool tiled, hipStream_t stream);
-hipError_t launch_denoise_var(const KDenoiseVar &k, uint32_t terms, hipStream_t stream);
-size_t denoise_tiled_lds(uint32_t terms, uint32_t step);
-// rt_temporal.hip
-hipError_t launch_temporal(const KTemporal &k, hipStream_t stream);
-} // namespace rt
 
 namespace {
-
-
-#define RT_HIP(call)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(RT_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 
 // counters: [kMaxWs][8 queues x kQueueStride], then [kMaxWs][4] u64 segment counters, then
 // the compat kernel's counter
@@ -1694,7 +1664,7 @@ int rt_epilogue_rgb8_device(const float *d_rgb, uint8_t *d_out, uint64_t n_pixel
 
 namespace {
 
-// The synchronous renders' per-device context, kept between calls: the reference's entry point
+// The synchronous calls' per-device context, kept between calls: the reference's entry point
 // (cuda_impl, src/CUDA/cuda_impl.cu:384-453) is called once per frame with the same scene, and
 // building the scene (clusters, shortcut words, streams, events), its workspaces and the frame
 // buffers on every call cost more than the frame itself. The context is keyed by the scene's
@@ -1703,20 +1673,18 @@ namespace {
 struct SyncContext {
     std::vector<unsigned char> key;
     rt_scene *sc = nullptr;
-    float *d_rgb = nullptr;
-    size_t rgb_bytes = 0;
-    uint8_t *d_u8 = nullptr;
-    size_t u8_bytes = 0;
-    uint64_t *d_seg = nullptr;
-    void *d_aov = nullptr;  // rt_render_aov: the requested planes, one after the other
-    size_t aov_bytes = 0;
-    void *d_dn = nullptr;   // rt_denoise: the inputs, out and scratch, one after the other
-    size_t dn_bytes = 0;
-    float *d_var = nullptr;  // rt_render_var: the variance plane (the beauty goes to d_rgb)
-    size_t var_bytes = 0;
+    // The device planes of every synchronous call, grow-only: each call lays its planes out from
+    // offset 0 (rthost::plane_layout), so the arena holds the largest call's need, not the sum.
+    // Nothing in it outlives a call: every input plane is uploaded by the call that reads it, and
+    // every plane a call copies back is first written in full by its kernels (the rendered rows,
+    // each filter level's output and scratch, the temporal outputs) or cleared (render_host's
+    // full frame); the full-frame feature and variance renders copy back only the rows they wrote.
+    void *arena = nullptr;
+    size_t arena_bytes = 0;
+    uint64_t *d_seg = nullptr;  // the work counters of a render with stats (24 bytes)
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
-std::mutex g_sync_mu;  // one synchronous render at a time per process (the reference's entry is not re-entrant)
+std::mutex g_sync_mu;  // one synchronous call at a time per process (the reference's entry is not re-entrant)
 std::map<int, SyncContext> g_sync;
 
 void sync_release(int dev, SyncContext &c)
@@ -1725,7 +1693,7 @@ void sync_release(int dev, SyncContext &c)
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(dev);
     if (c.sc) rt_scene_destroy(c.sc);
-    for (void *p : {(void *)c.d_rgb, (void *)c.d_u8, (void *)c.d_seg, c.d_aov, c.d_dn, (void *)c.d_var})
+    for (void *p : {c.arena, (void *)c.d_seg})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : {c.e0, c.e1})
         if (e) (void)hipEventDestroy(e);
@@ -1755,161 +1723,162 @@ int sync_scene(int dev, SyncContext &cx, const rt_sphere *spheres, uint32_t n_sp
     return RT_OK;
 }
 
-// Synchronous host-buffer render on the current device (the cuda_impl replacement).
+} // namespace
+
+namespace rthost {
+
+SyncCall::SyncCall() : t0_(std::chrono::steady_clock::now()), lock_(g_sync_mu) {}
+
+int SyncCall::run(const SyncSpec &s, const std::function<int()> &enqueue, const std::function<int()> &after)
+{
+    int dev = 0;
+    RT_HIP(hipGetDevice(&dev));
+    SyncContext &cx = g_sync[dev];
+    if (s.scene) {
+        if (int rc = sync_scene(dev, cx, s.scene->spheres, s.scene->n_spheres, s.scene->materials, s.scene->n_materials); rc)
+            return rc;
+        scene = cx.sc;
+    }
+    const size_t total = plane_layout(s.planes, s.n_planes, s.n_px);
+    int rc = RT_OK;
+    auto chk = [&](hipError_t e, const char *what) {
+        if (rc == RT_OK) rc = hip_rc(e, what);
+        return rc == RT_OK;
+    };
+    if (cx.arena_bytes < total || !cx.arena) {
+        if (cx.arena) chk(hipFree(cx.arena), "hipFree");
+        cx.arena = nullptr;
+        cx.arena_bytes = 0;
+        if (chk(hipMalloc(&cx.arena, std::max<size_t>(total, 256)), "hipMalloc")) cx.arena_bytes = total;
+    }
+    if (rc == RT_OK && s.counters && !cx.d_seg) chk(hipMalloc((void **)&cx.d_seg, 24), "hipMalloc");
+    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
+    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
+    if (rc == RT_OK && !s.skip) {
+        Plane *const end = s.planes + s.n_planes;
+        for (Plane *pl = s.planes; pl != end; ++pl) {
+            if (pl->kind == Plane::Absent) continue;
+            pl->dev = static_cast<char *>(cx.arena) + pl->at;
+            if (rc == RT_OK && pl->kind == Plane::In)
+                chk(hipMemcpy(pl->dev, pl->host, s.n_px * pl->px_bytes, hipMemcpyHostToDevice), "hipMemcpy");
+            if (rc == RT_OK && pl->clear) chk(hipMemsetAsync(pl->dev, 0, s.n_px * pl->px_bytes, nullptr), "hipMemset");
+        }
+        // the work counters (rt_stats) come from the counting instantiation of the kernels, slower than
+        // the product's: only when the caller asks for them (rt::render_impl does not, as cuda_impl)
+        if (rc == RT_OK && s.counters) {
+            chk(hipMemsetAsync(cx.d_seg, 0, 24, nullptr), "hipMemset");
+            d_counters = cx.d_seg;
+        }
+        if (rc == RT_OK) chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
+        if (rc == RT_OK) rc = enqueue();
+        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
+        if (rc == RT_OK && after) rc = after();
+        // the copies on the null stream follow the work; the last one returns when all is done
+        const SyncRows &r = s.rows;
+        for (const Plane *pl = s.planes; pl != end; ++pl) {
+            if (rc != RT_OK || pl->kind != Plane::Out) continue;
+            const size_t row_bytes = r.width * pl->px_bytes;
+            if (!r.stride) {
+                chk(hipMemcpy(pl->host, pl->dev, r.rows * row_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+            } else {
+                const size_t first = r.offset * row_bytes;
+                chk(hipMemcpy2D(static_cast<char *>(pl->host) + first, r.stride * row_bytes,
+                                static_cast<const char *>(pl->dev) + first, r.stride * row_bytes, row_bytes, r.rows,
+                                hipMemcpyDeviceToHost),
+                    "hipMemcpy2D");
+            }
+        }
+        if (rc == RT_OK && s.counters) chk(hipMemcpy(counters, cx.d_seg, 24, hipMemcpyDeviceToHost), "hipMemcpy");
+        if (rc == RT_OK) chk(hipDeviceSynchronize(), s.who);
+        if (rc == RT_OK) chk(hipEventElapsedTime(&kernel_ms, cx.e0, cx.e1), "hipEventElapsedTime");
+    }
+    if (rc != RT_OK) {
+        // a failed call leaves no state behind: the next one starts from a new context
+        const std::string msg = g_error;
+        sync_release(dev, cx);
+        g_error = msg;
+    }
+    return rc;
+}
+
+} // namespace rthost
+
+namespace {
+
+// The rows a render's outputs come back as: the rendered rows one after the other, or, of a full
+// frame, those rows only, each to its place in the caller's frame.
+SyncRows rendered_rows(const rt_params &P)
+{
+    if (!(P.flags & RT_FLAG_FULL_FRAME)) return {P.width, rows_of(P)};
+    return {P.width, rows_of(P), P.row_offset, P.row_stride ? P.row_stride : 1u};
+}
+
+// The six fields a counted render sets of the caller's record (the others stay as they are).
+void render_stats(rt_stats &st, const SyncCall &call, uint64_t primaries)
+{
+    st.primaries = primaries;
+    st.segments = call.counters[0];
+    st.sphere_tests = call.counters[1];
+    st.box_tests = call.counters[2];
+    st.kernel_ms = call.kernel_ms;
+    st.wall_ms = call.wall_ms();
+}
+
+// Synchronous host-buffer render on the current device (the cuda_impl replacement). The frame is
+// rendered as floats also where only the 8-bit image is wanted; a full frame comes back whole,
+// cleared where no row was rendered.
 int render_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
                 const rt_camera *camera, const rt_params *params, float *rgb_out, uint8_t *u8_out, rt_stats *stats)
 {
     if (!camera || (!rgb_out && !u8_out)) return fail(RT_ERR_INVALID, "render: null argument");
     if (int rc = check_params(params); rc != RT_OK) return rc;
     if ((n_spheres && !spheres) || !materials || !n_materials) return fail(RT_ERR_INVALID, "render: null scene");
-    const auto t0 = std::chrono::steady_clock::now();
-    int dev = 0;
-    RT_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_sync_mu);
-    SyncContext &cx = g_sync[dev];
-    if (int rc = sync_scene(dev, cx, spheres, n_spheres, materials, n_materials); rc) return rc;
-    rt_scene *sc = cx.sc;
     const rt_params &P = *params;
-    const uint64_t rows = (P.flags & RT_FLAG_FULL_FRAME) ? P.height : rows_of(P);
-    const uint64_t n_values = rows * P.width * 3u;
-    int rc = RT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-        return rc == RT_OK;
-    };
-    auto grow_buf = [&](void **p, size_t *have, size_t want) {
-        if (*have >= want && *p) return;
-        if (*p) chk(hipFree(*p), "hipFree");
-        *p = nullptr;
-        *have = 0;
-        if (chk(hipMalloc(p, std::max<size_t>(want, 256)), "hipMalloc")) *have = want;
-    };
-    grow_buf((void **)&cx.d_rgb, &cx.rgb_bytes, n_values * 4);
-    if (u8_out) grow_buf((void **)&cx.d_u8, &cx.u8_bytes, n_values);
-    if (rc == RT_OK && !cx.d_seg) chk(hipMalloc((void **)&cx.d_seg, 24), "hipMalloc");
-    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
-    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
-    float *d_rgb = cx.d_rgb;
-    uint8_t *d_u8 = cx.d_u8;
-    uint64_t *d_seg = cx.d_seg;
-    hipEvent_t e0 = cx.e0, e1 = cx.e1;
-    if (rc == RT_OK && (P.flags & RT_FLAG_FULL_FRAME)) chk(hipMemsetAsync(d_rgb, 0, n_values * 4, nullptr), "hipMemset");
-    // the work counters (rt_stats) come from the counting instantiation of the kernels, slower than
-    // the product's: only when the caller asks for them (rt::render_impl does not, as cuda_impl)
-    if (rc == RT_OK && stats) chk(hipMemsetAsync(d_seg, 0, 24, nullptr), "hipMemset");
-    if (rc == RT_OK) chk(hipEventRecord(e0, nullptr), "hipEventRecord");
-    if (rc == RT_OK) rc = rt_render_device(sc, camera, params, d_rgb, nullptr, stats ? d_seg : nullptr);
-    if (rc == RT_OK) chk(hipEventRecord(e1, nullptr), "hipEventRecord");
-    if (rc == RT_OK && u8_out) rc = rt_epilogue_rgb8_device(d_rgb, d_u8, n_values / 3, nullptr);
-    uint64_t segs[3] = {0, 0, 0};
-    float ms = 0.f;
-    // the copies on the null stream follow the render; the last one returns when all is done
-    if (rc == RT_OK && rgb_out) chk(hipMemcpy(rgb_out, d_rgb, n_values * 4, hipMemcpyDeviceToHost), "hipMemcpy");
-    if (rc == RT_OK && u8_out) chk(hipMemcpy(u8_out, d_u8, n_values, hipMemcpyDeviceToHost), "hipMemcpy");
-    if (rc == RT_OK && stats) chk(hipMemcpy(segs, d_seg, 24, hipMemcpyDeviceToHost), "hipMemcpy");
-    if (rc == RT_OK) chk(hipDeviceSynchronize(), "render");
-    if (rc == RT_OK) chk(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-    if (rc != RT_OK) {
-        // a failed call leaves no state behind: the next one starts from a new context
-        const std::string msg = g_error;
-        sync_release(dev, cx);
-        g_error = msg;
-    }
-    if (rc == RT_OK && stats) {
-        stats->primaries = static_cast<uint64_t>(P.width) * rows_of(P) * P.spp;
-        stats->segments = segs[0];
-        stats->sphere_tests = segs[1];
-        stats->box_tests = segs[2];
-        stats->kernel_ms = ms;
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
+    const bool full = (P.flags & RT_FLAG_FULL_FRAME) != 0u;
+    const size_t rows = full ? P.height : rows_of(P), n_px = rows * P.width;
+    Plane planes[2] = {rgb_out ? plane_out(rgb_out, 12) : plane_scratch(true, 12), plane_out(u8_out, 3)};
+    planes[0].clear = full;
+    const SyncScene scene{spheres, n_spheres, materials, n_materials};
+    SyncCall call;
+    const int rc = call.run(
+        {"render", planes, 2, n_px, {P.width, rows}, &scene, stats != nullptr},
+        [&] { return rt_render_device(call.scene, camera, params, planes[0].as<float>(), nullptr, call.d_counters); },
+        [&] { return u8_out ? rt_epilogue_rgb8_device(planes[0].as<float>(), planes[1].as<uint8_t>(), n_px, nullptr) : RT_OK; });
+    if (rc == RT_OK && stats) render_stats(*stats, call, static_cast<uint64_t>(P.width) * rows_of(P) * P.spp);
     return rc;
 }
 
-// Synchronous feature buffers into host planes, through the same cached context: the planes are
-// rendered into one device buffer and copied out (full frame: the rendered rows only).
+// Synchronous feature buffers into host planes (full frame: the rendered rows only).
 int render_aov_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
                     const rt_camera *camera, const rt_params *params, const rt_aov_buffers *aov, rt_stats *stats)
 {
     if (int rc = check_aov(params, aov, "rt_render_aov"); rc != RT_OK) return rc;
     if (!camera) return fail(RT_ERR_INVALID, "rt_render_aov: null camera");
     if ((n_spheres && !spheres) || !materials || !n_materials) return fail(RT_ERR_INVALID, "rt_render_aov: null scene");
-    const auto t0 = std::chrono::steady_clock::now();
-    int dev = 0;
-    RT_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_sync_mu);
-    SyncContext &cx = g_sync[dev];
-    if (int rc = sync_scene(dev, cx, spheres, n_spheres, materials, n_materials); rc) return rc;
     const rt_params &P = *params;
-    const bool full = (P.flags & RT_FLAG_FULL_FRAME) != 0u;
-    const uint64_t rows = rows_of(P), rows_out = full ? P.height : rows;
+    const SyncRows rows = rendered_rows(P);
+    const size_t rows_out = (P.flags & RT_FLAG_FULL_FRAME) ? P.height : rows.rows;
     const uint32_t samples = aov->samples ? aov->samples : P.spp;
-    // the planes asked for, packed into the context's buffer (256-byte aligned)
-    struct Plane { void *host; uint32_t channels; size_t at; };
-    Plane planes[5] = {{aov->albedo, 3, 0}, {aov->normal, 3, 0}, {aov->depth, 1, 0}, {aov->alpha, 1, 0}, {aov->sphere_id, 1, 0}};
-    size_t total = 0;
-    for (Plane &pl : planes)
-        if (pl.host) {
-            pl.at = total;
-            total += (static_cast<size_t>(rows_out) * P.width * pl.channels * 4u + 255u) & ~static_cast<size_t>(255u);
-        }
-    int rc = RT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-        return rc == RT_OK;
-    };
-    if (cx.aov_bytes < total || !cx.d_aov) {
-        if (cx.d_aov) chk(hipFree(cx.d_aov), "hipFree");
-        cx.d_aov = nullptr;
-        cx.aov_bytes = 0;
-        if (chk(hipMalloc(&cx.d_aov, std::max<size_t>(total, 256)), "hipMalloc")) cx.aov_bytes = total;
-    }
-    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
-    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
-    float ms = 0.f;
-    if (rc == RT_OK && rows) {
-        char *base = static_cast<char *>(cx.d_aov);
-        auto dptr = [&](const Plane &pl) -> void * { return pl.host ? base + pl.at : nullptr; };
-        rt_aov_buffers d{static_cast<uint32_t>(sizeof(rt_aov_buffers)), samples,
-                         static_cast<float *>(dptr(planes[0])), static_cast<float *>(dptr(planes[1])),
-                         static_cast<float *>(dptr(planes[2])), static_cast<float *>(dptr(planes[3])),
-                         static_cast<uint32_t *>(dptr(planes[4]))};
-        chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
-        if (rc == RT_OK) rc = rt_render_aov_device(cx.sc, camera, params, &d, nullptr);
-        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
-        // the copies on the null stream follow the kernel
-        for (const Plane &pl : planes) {
-            if (rc != RT_OK || !pl.host) continue;
-            const size_t row_bytes = static_cast<size_t>(P.width) * pl.channels * 4u;
-            if (!full) {
-                chk(hipMemcpy(pl.host, base + pl.at, rows * row_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
-            } else {
-                const size_t st = P.row_stride ? P.row_stride : 1u, first = P.row_offset * row_bytes;
-                chk(hipMemcpy2D(static_cast<char *>(pl.host) + first, st * row_bytes, base + pl.at + first, st * row_bytes,
-                                row_bytes, rows, hipMemcpyDeviceToHost),
-                    "hipMemcpy2D");
-            }
-        }
-        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_render_aov");
-        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
-    }
-    if (rc != RT_OK) {
-        // a failed call leaves no state behind: the next one starts from a new context
-        const std::string msg = g_error;
-        sync_release(dev, cx);
-        g_error = msg;
-    }
+    Plane planes[5] = {plane_out(aov->albedo, 12), plane_out(aov->normal, 12), plane_out(aov->depth, 4),
+                       plane_out(aov->alpha, 4), plane_out(aov->sphere_id, 4)};
+    const SyncScene scene{spheres, n_spheres, materials, n_materials};
+    SyncCall call;
+    const int rc = call.run({"rt_render_aov", planes, 5, rows_out * P.width, rows, &scene, false, rows.rows == 0}, [&] {
+        const rt_aov_buffers d{static_cast<uint32_t>(sizeof(rt_aov_buffers)), samples, planes[0].as<float>(),
+                               planes[1].as<float>(), planes[2].as<float>(), planes[3].as<float>(), planes[4].as<uint32_t>()};
+        return rt_render_aov_device(call.scene, camera, params, &d, nullptr);
+    });
     if (rc == RT_OK && stats) {
         *stats = rt_stats{};
-        stats->primaries = stats->segments = static_cast<uint64_t>(P.width) * rows * samples;
-        stats->kernel_ms = ms;
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->primaries = stats->segments = static_cast<uint64_t>(P.width) * rows.rows * samples;
+        stats->kernel_ms = call.kernel_ms;
+        stats->wall_ms = call.wall_ms();
     }
     return rc;
 }
 
-// Synchronous render with the variance plane into host buffers, through the same cached context
-// (full frame: the rendered rows only, of both outputs).
+// Synchronous render with the variance plane into host buffers (full frame: the rendered rows
+// only, of both outputs).
 int render_var_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
                     const rt_camera *camera, const rt_params *params, float *rgb_out, float *var_out, rt_stats *stats)
 {
@@ -1919,500 +1888,17 @@ int render_var_host(const rt_sphere *spheres, uint32_t n_spheres, const rt_mater
     if (var_out == rgb_out) return fail(RT_ERR_INVALID, "rt_render_var: var_out is also rgb_out");
     if (int rc = check_var_params(params, "rt_render_var"); rc != RT_OK) return rc;
     if ((n_spheres && !spheres) || !materials || !n_materials) return fail(RT_ERR_INVALID, "rt_render_var: null scene");
-    const auto t0 = std::chrono::steady_clock::now();
-    int dev = 0;
-    RT_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_sync_mu);
-    SyncContext &cx = g_sync[dev];
-    if (int rc = sync_scene(dev, cx, spheres, n_spheres, materials, n_materials); rc) return rc;
     const rt_params &P = *params;
-    const bool full = (P.flags & RT_FLAG_FULL_FRAME) != 0u;
-    const uint64_t rows = rows_of(P), rows_out = full ? P.height : rows;
-    const size_t n_px = static_cast<size_t>(rows_out) * P.width;
-    int rc = RT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-        return rc == RT_OK;
-    };
-    auto grow_buf = [&](void **p, size_t *have, size_t want) {
-        if (*have >= want && *p) return;
-        if (*p) chk(hipFree(*p), "hipFree");
-        *p = nullptr;
-        *have = 0;
-        if (chk(hipMalloc(p, std::max<size_t>(want, 256)), "hipMalloc")) *have = want;
-    };
-    grow_buf((void **)&cx.d_rgb, &cx.rgb_bytes, n_px * 12u);
-    grow_buf((void **)&cx.d_var, &cx.var_bytes, n_px * 4u);
-    if (rc == RT_OK && !cx.d_seg) chk(hipMalloc((void **)&cx.d_seg, 24), "hipMalloc");
-    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
-    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
-    uint64_t segs[3] = {0, 0, 0};
-    float ms = 0.f;
-    if (rc == RT_OK && rows) {
-        if (stats) chk(hipMemsetAsync(cx.d_seg, 0, 24, nullptr), "hipMemset");
-        if (rc == RT_OK) chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
-        if (rc == RT_OK) rc = rt_render_var_device(cx.sc, camera, params, cx.d_rgb, cx.d_var, nullptr, stats ? cx.d_seg : nullptr);
-        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
-        // the copies on the null stream follow the render
-        const struct { void *host; const void *dev; size_t row_bytes; } outs[2] = {
-            {rgb_out, cx.d_rgb, static_cast<size_t>(P.width) * 12u}, {var_out, cx.d_var, static_cast<size_t>(P.width) * 4u}};
-        for (const auto &o : outs) {
-            if (rc != RT_OK) break;
-            if (!full) {
-                chk(hipMemcpy(o.host, o.dev, rows * o.row_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
-            } else {
-                const size_t st = P.row_stride ? P.row_stride : 1u, first = P.row_offset * o.row_bytes;
-                chk(hipMemcpy2D(static_cast<char *>(o.host) + first, st * o.row_bytes,
-                                static_cast<const char *>(o.dev) + first, st * o.row_bytes, o.row_bytes, rows,
-                                hipMemcpyDeviceToHost),
-                    "hipMemcpy2D");
-            }
-        }
-        if (rc == RT_OK && stats) chk(hipMemcpy(segs, cx.d_seg, 24, hipMemcpyDeviceToHost), "hipMemcpy");
-        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_render_var");
-        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
-    }
-    if (rc != RT_OK) {
-        // a failed call leaves no state behind: the next one starts from a new context
-        const std::string msg = g_error;
-        sync_release(dev, cx);
-        g_error = msg;
-    }
-    if (rc == RT_OK && stats) {
-        stats->primaries = static_cast<uint64_t>(P.width) * rows * P.spp;
-        stats->segments = segs[0];
-        stats->sphere_tests = segs[1];
-        stats->box_tests = segs[2];
-        stats->kernel_ms = ms;
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return rc;
-}
-
-
-// ---- the à-trous denoiser (include/rt_api.h; kernels in rt_denoise.hip) ----------------------
-// Levels with a step up to this take the tiled kernel: at 1280x720 with every guide it takes 0.77
-// of the direct kernel's time at steps 1 and 2 and 1.03 at step 4, where its halo is as large as
-// its tile (profiles/denoise/time_c3.txt). Its LDS image at step 2 is 37.5 KiB.
-constexpr uint32_t kDenoiseTiledMaxStep = 2;
-// The largest step the tiled kernel can take at all (rt_denoise_level_device's A/B): its LDS image
-// with every guide is then 60 KiB, the most a launch gets without asking for more.
-constexpr uint32_t kDenoiseTiledFits = 4;
-constexpr uint32_t kDenoiseMaxSide = 65536;
-// rt_denoise_var_params_default: the values scripts/denoise_var_sweep.py chose
-constexpr uint32_t kDnVarLevels = 2;
-constexpr float kDnVarSigmaColor = 32.0f, kDnVarSigmaNormal = 1.0f, kDnVarSigmaDepth = 4.0f, kDnVarSigmaAlbedo = 1.0f;
-constexpr float kDnVarFloor = 1e-6f;
-
-// Every argument check of the denoiser, before any HIP call (use_scratch: the call uses
-// buffers.scratch). terms: the edge terms that are on.
-int check_denoise(const rt_denoise_params *p, const rt_denoise_buffers *b, bool use_scratch, const char *who,
-                  uint32_t *terms)
-{
-    const std::string w = std::string(who) + ": ";
-    if (!p || !b) return fail(RT_ERR_INVALID, w + "null argument");
-    if (p->size != sizeof(rt_denoise_params)) return fail(RT_ERR_INVALID, w + "params.size is not sizeof(rt_denoise_params)");
-    if (b->size != sizeof(rt_denoise_buffers)) return fail(RT_ERR_INVALID, w + "buffers.size is not sizeof(rt_denoise_buffers)");
-    if (!p->width || p->width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
-    if (!p->height || p->height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
-    if (p->levels < 1u || p->levels > 6u) return fail(RT_ERR_INVALID, w + "levels must be 1..6");
-    const struct { const char *name; float v; } sig[4] = {{"sigma_color", p->sigma_color}, {"sigma_normal", p->sigma_normal},
-                                                          {"sigma_depth", p->sigma_depth}, {"sigma_albedo", p->sigma_albedo}};
-    for (const auto &s : sig)
-        if (!std::isfinite(s.v) || s.v < 0.f) return fail(RT_ERR_INVALID, w + s.name + " must be finite and not negative");
-    if (p->flags & ~static_cast<uint32_t>(RT_DENOISE_DEMODULATE | RT_DENOISE_DIRECT))
-        return fail(RT_ERR_INVALID, w + "unknown bits in flags");
-    if (!b->beauty) return fail(RT_ERR_INVALID, w + "beauty is null");
-    if (!b->out) return fail(RT_ERR_INVALID, w + "out is null");
-    if (b->normal && p->sigma_normal == 0.f) return fail(RT_ERR_INVALID, w + "sigma_normal is 0 with a normal plane");
-    if (b->depth && p->sigma_depth == 0.f) return fail(RT_ERR_INVALID, w + "sigma_depth is 0 with a depth plane");
-    if ((p->flags & RT_DENOISE_DEMODULATE) && !b->albedo)
-        return fail(RT_ERR_INVALID, w + "RT_DENOISE_DEMODULATE needs the albedo plane");
-    if (p->sigma_color != 0.f) {
-        const float s = p->sigma_color * std::ldexp(1.f, -static_cast<int>(p->levels - 1u));
-        if (!std::isfinite(1.0f / (s * s))) return fail(RT_ERR_INVALID, w + "sigma_color is too small for this many levels");
-    }
-    for (const auto &s : {sig[1], sig[2], sig[3]})
-        if (s.v != 0.f && !std::isfinite(1.0f / (s.v * s.v))) return fail(RT_ERR_INVALID, w + s.name + " is too small");
-    const bool need_scratch = use_scratch && p->levels > 1u;
-    if (need_scratch && !b->scratch) return fail(RT_ERR_INVALID, w + "scratch is null with levels > 1");
-    const float *const scratch = use_scratch ? b->scratch : nullptr;
-    for (const float *in : {b->beauty, b->albedo, b->normal, b->depth}) {
-        if (in && in == b->out) return fail(RT_ERR_INVALID, w + "out is also an input plane");
-        if (in && in == scratch) return fail(RT_ERR_INVALID, w + "scratch is also an input plane");
-    }
-    if (scratch && scratch == b->out) return fail(RT_ERR_INVALID, w + "scratch is also out");
-    *terms = (p->sigma_color != 0.f ? 1u : 0u) | (b->normal ? 2u : 0u) | (b->depth ? 4u : 0u) |
-             (b->albedo && p->sigma_albedo != 0.f ? 8u : 0u);
-    return RT_OK;
-}
-
-float denoise_r(float sigma) { return 1.0f / (sigma * sigma); }
-
-// Enqueue levels [first, last] of the run `p` describes: level l reads `in` when l == first and
-// the previous level's output otherwise; the last one writes b.out, those before it alternate
-// between b.scratch and b.out so that it does. Steps up to tiled_max_step take the tiled kernel.
-int denoise_levels(const rt_denoise_params &p, const rt_denoise_buffers &b, uint32_t terms, uint32_t first,
-                   uint32_t last, uint32_t tiled_max_step, hipStream_t stream)
-{
-    const bool demod = (p.flags & RT_DENOISE_DEMODULATE) != 0u;
-    rt::KDenoise k{};
-    k.albedo = (terms & 8u) || demod ? b.albedo : nullptr;
-    k.normal = b.normal;
-    k.depth = b.depth;
-    k.W = p.width;
-    k.H = p.height;
-    k.r_n = (terms & 2u) ? denoise_r(p.sigma_normal) : 0.f;
-    k.r_z = (terms & 4u) ? denoise_r(p.sigma_depth) : 0.f;
-    k.r_a = (terms & 8u) ? denoise_r(p.sigma_albedo) : 0.f;
-    const float *in = b.beauty;
-    for (uint32_t l = first; l <= last; ++l) {
-        k.in = in;
-        k.out = ((last - l) & 1u) ? b.scratch : b.out;
-        k.step = 1u << l;
-        k.r_c = (terms & 1u) ? denoise_r(p.sigma_color * std::ldexp(1.f, -static_cast<int>(l))) : 0.f;
-        k.demod_out = demod && l + 1u == p.levels;
-        const bool tiled = !(p.flags & RT_DENOISE_DIRECT) && k.step <= tiled_max_step;
-        RT_HIP(rt::launch_denoise(k, terms, demod && l == 0u, tiled, stream));
-        in = k.out;
-    }
-    return RT_OK;
-}
-
-// Synchronous denoise of host planes through the cached per-device context's buffer.
-int denoise_host(const rt_denoise_params *params, const rt_denoise_buffers *buffers, rt_stats *stats)
-{
-    uint32_t terms = 0;
-    if (int rc = check_denoise(params, buffers, false, "rt_denoise", &terms); rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    int dev = 0;
-    RT_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_sync_mu);
-    SyncContext &cx = g_sync[dev];
-    const rt_denoise_params &P = *params;
-    const size_t n = static_cast<size_t>(P.width) * P.height;
-    // beauty, albedo, normal, depth, out, scratch packed into the context's buffer (256-byte aligned)
-    struct Plane { const float *host; uint32_t channels; size_t at; };
-    Plane planes[6] = {{buffers->beauty, 3, 0}, {buffers->albedo, 3, 0}, {buffers->normal, 3, 0},
-                       {buffers->depth, 1, 0},  {buffers->out, 3, 0},    {P.levels > 1u ? buffers->out : nullptr, 3, 0}};
-    size_t total = 0;
-    for (Plane &pl : planes)
-        if (pl.host) {
-            pl.at = total;
-            total += (n * pl.channels * 4u + 255u) & ~static_cast<size_t>(255u);
-        }
-    int rc = RT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-        return rc == RT_OK;
-    };
-    if (cx.dn_bytes < total || !cx.d_dn) {
-        if (cx.d_dn) chk(hipFree(cx.d_dn), "hipFree");
-        cx.d_dn = nullptr;
-        cx.dn_bytes = 0;
-        if (chk(hipMalloc(&cx.d_dn, std::max<size_t>(total, 256)), "hipMalloc")) cx.dn_bytes = total;
-    }
-    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
-    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
-    float ms = 0.f;
-    if (rc == RT_OK) {
-        char *base = static_cast<char *>(cx.d_dn);
-        auto dptr = [&](const Plane &pl) { return pl.host ? reinterpret_cast<float *>(base + pl.at) : nullptr; };
-        for (int i = 0; i < 4; ++i)
-            if (rc == RT_OK && planes[i].host)
-                chk(hipMemcpy(dptr(planes[i]), planes[i].host, n * planes[i].channels * 4u, hipMemcpyHostToDevice), "hipMemcpy");
-        rt_denoise_buffers d{static_cast<uint32_t>(sizeof(rt_denoise_buffers)), dptr(planes[0]), dptr(planes[1]),
-                             dptr(planes[2]), dptr(planes[3]), dptr(planes[4]), dptr(planes[5])};
-        if (rc == RT_OK) chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
-        if (rc == RT_OK) rc = denoise_levels(P, d, terms, 0, P.levels - 1u, kDenoiseTiledMaxStep, nullptr);
-        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
-        // the copy on the null stream follows the kernels
-        if (rc == RT_OK) chk(hipMemcpy(buffers->out, d.out, n * 12u, hipMemcpyDeviceToHost), "hipMemcpy");
-        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_denoise");
-        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
-    }
-    if (rc != RT_OK) {
-        // a failed call leaves no state behind: the next one starts from a new context
-        const std::string msg = g_error;
-        sync_release(dev, cx);
-        g_error = msg;
-    }
-    if (rc == RT_OK && stats) {
-        *stats = rt_stats{};
-        stats->kernel_ms = ms;
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return rc;
-}
-
-// ---- the variance-guided filter (include/rt_api.h) ---------------------------
-// Its checks: rt_denoise_device's, then the variance record's (use_scratch: a device call).
-int check_denoise_var(const rt_denoise_params *p, const rt_denoise_buffers *b, const rt_denoise_var_buffers *v,
-                      bool use_scratch, const char *who, uint32_t *terms)
-{
-    if (int rc = check_denoise(p, b, use_scratch, who, terms); rc != RT_OK) return rc;
-    const std::string w = std::string(who) + ": ";
-    if (p->flags & RT_DENOISE_DEMODULATE)
-        return fail(RT_ERR_UNSUPPORTED, w + "RT_DENOISE_DEMODULATE is not supported (the variance is not demodulated)");
-    if (!v) return fail(RT_ERR_INVALID, w + "null variance record");
-    if (v->size != sizeof(rt_denoise_var_buffers))
-        return fail(RT_ERR_INVALID, w + "var.size is not sizeof(rt_denoise_var_buffers)");
-    if (!std::isfinite(v->var_floor) || !(v->var_floor > 0.f)) return fail(RT_ERR_INVALID, w + "var_floor must be finite and positive");
-    if (!v->variance) return fail(RT_ERR_INVALID, w + "variance is null");
-    const float *const var_scratch = use_scratch ? v->var_scratch : nullptr;
-    if (use_scratch && !var_scratch) return fail(RT_ERR_INVALID, w + "var_scratch is null");
-    const float *const scratch = use_scratch ? b->scratch : nullptr;
-    for (const float *o : {b->beauty, b->albedo, b->normal, b->depth, static_cast<const float *>(b->out), scratch,
-                           v->variance}) {
-        if (o && o == v->variance_out) return fail(RT_ERR_INVALID, w + "variance_out is also another plane");
-        if (o && o == var_scratch) return fail(RT_ERR_INVALID, w + "var_scratch is also another plane");
-    }
-    if (var_scratch && var_scratch == v->variance_out) return fail(RT_ERR_INVALID, w + "var_scratch is also variance_out");
-    return RT_OK;
-}
-
-// Enqueue every level: the colours alternate between b.scratch and b.out as in denoise_levels, the
-// variances between the halves of v.var_scratch; the last level's goes to v.variance_out, if given.
-int denoise_var_levels(const rt_denoise_params &p, const rt_denoise_buffers &b, const rt_denoise_var_buffers &v,
-                       uint32_t terms, hipStream_t stream)
-{
-    rt::KDenoiseVar kv{};
-    rt::KDenoise &k = kv.d;
-    k.albedo = (terms & 8u) ? b.albedo : nullptr;
-    k.normal = b.normal;
-    k.depth = b.depth;
-    k.W = p.width;
-    k.H = p.height;
-    k.r_n = (terms & 2u) ? denoise_r(p.sigma_normal) : 0.f;
-    k.r_z = (terms & 4u) ? denoise_r(p.sigma_depth) : 0.f;
-    k.r_a = (terms & 8u) ? denoise_r(p.sigma_albedo) : 0.f;
-    kv.sc2 = p.sigma_color * p.sigma_color;
-    kv.var_floor = v.var_floor;
-    const size_t n = static_cast<size_t>(p.width) * p.height;
-    const float *in = b.beauty, *vin = v.variance;
-    const uint32_t last = p.levels - 1u;
-    for (uint32_t l = 0; l <= last; ++l) {
-        k.in = in;
-        k.out = ((last - l) & 1u) ? b.scratch : b.out;
-        k.step = 1u << l;
-        kv.vin = vin;
-        kv.vout = l == last ? v.variance_out : v.var_scratch + (l & 1u) * n;
-        RT_HIP(rt::launch_denoise_var(kv, terms, stream));
-        in = k.out;
-        vin = kv.vout;
-    }
-    return RT_OK;
-}
-
-// Synchronous variance-guided denoise of host planes through the cached context's buffer.
-int denoise_var_host(const rt_denoise_params *params, const rt_denoise_buffers *buffers, const rt_denoise_var_buffers *var,
-                     rt_stats *stats)
-{
-    uint32_t terms = 0;
-    if (int rc = check_denoise_var(params, buffers, var, false, "rt_denoise_var", &terms); rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    int dev = 0;
-    RT_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_sync_mu);
-    SyncContext &cx = g_sync[dev];
-    const rt_denoise_params &P = *params;
-    const size_t n = static_cast<size_t>(P.width) * P.height;
-    // beauty, albedo, normal, depth, variance (inputs), out, scratch, variance_out, var_scratch
-    struct Plane { const float *host; uint32_t channels; size_t at; };
-    Plane planes[9] = {{buffers->beauty, 3, 0}, {buffers->albedo, 3, 0}, {buffers->normal, 3, 0}, {buffers->depth, 1, 0},
-                       {var->variance, 1, 0},   {buffers->out, 3, 0},    {P.levels > 1u ? buffers->out : nullptr, 3, 0},
-                       {var->variance_out, 1, 0}, {P.levels > 1u ? buffers->out : nullptr, 2, 0}};
-    size_t total = 0;
-    for (Plane &pl : planes)
-        if (pl.host) {
-            pl.at = total;
-            total += (n * pl.channels * 4u + 255u) & ~static_cast<size_t>(255u);
-        }
-    int rc = RT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-        return rc == RT_OK;
-    };
-    if (cx.dn_bytes < total || !cx.d_dn) {
-        if (cx.d_dn) chk(hipFree(cx.d_dn), "hipFree");
-        cx.d_dn = nullptr;
-        cx.dn_bytes = 0;
-        if (chk(hipMalloc(&cx.d_dn, std::max<size_t>(total, 256)), "hipMalloc")) cx.dn_bytes = total;
-    }
-    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
-    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
-    float ms = 0.f;
-    if (rc == RT_OK) {
-        char *base = static_cast<char *>(cx.d_dn);
-        auto dptr = [&](const Plane &pl) { return pl.host ? reinterpret_cast<float *>(base + pl.at) : nullptr; };
-        for (int i = 0; i < 5; ++i)
-            if (rc == RT_OK && planes[i].host)
-                chk(hipMemcpy(dptr(planes[i]), planes[i].host, n * planes[i].channels * 4u, hipMemcpyHostToDevice), "hipMemcpy");
-        rt_denoise_buffers d{static_cast<uint32_t>(sizeof(rt_denoise_buffers)), dptr(planes[0]), dptr(planes[1]),
-                             dptr(planes[2]), dptr(planes[3]), dptr(planes[5]), dptr(planes[6])};
-        rt_denoise_var_buffers dv{static_cast<uint32_t>(sizeof(rt_denoise_var_buffers)), var->var_floor, dptr(planes[4]),
-                                  dptr(planes[7]), dptr(planes[8])};
-        if (rc == RT_OK) chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
-        if (rc == RT_OK) rc = denoise_var_levels(P, d, dv, terms, nullptr);
-        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
-        // the copies on the null stream follow the kernels
-        if (rc == RT_OK) chk(hipMemcpy(buffers->out, d.out, n * 12u, hipMemcpyDeviceToHost), "hipMemcpy");
-        if (rc == RT_OK && var->variance_out)
-            chk(hipMemcpy(var->variance_out, dv.variance_out, n * 4u, hipMemcpyDeviceToHost), "hipMemcpy");
-        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_denoise_var");
-        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
-    }
-    if (rc != RT_OK) {
-        // a failed call leaves no state behind: the next one starts from a new context
-        const std::string msg = g_error;
-        sync_release(dev, cx);
-        g_error = msg;
-    }
-    if (rc == RT_OK && stats) {
-        *stats = rt_stats{};
-        stats->kernel_ms = ms;
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return rc;
-}
-
-// ---- temporal accumulation (include/rt_api.h; kernel in rt_temporal.hip) ------
-// rt_temporal_params_default: the values scripts/temporal_sweep.py chose
-constexpr float kTpAlphaMin = 0.4f, kTpMaxHistory = 32.0f, kTpNormalTol = 0.5f, kTpDepthTol = 0.1f;
-
-// Every argument check, before any HIP call; fills the kernel's record (the cameras as the
-// contract's {a, hor, ver, o} and {A, B, G, o'}) from the caller's pointers.
-int check_temporal(const rt_temporal_params *p, const rt_camera *cam, const rt_camera *prev_cam,
-                   const rt_temporal_buffers *b, const char *who, rt::KTemporal *k)
-{
-    const std::string w = std::string(who) + ": ";
-    if (!p || !b) return fail(RT_ERR_INVALID, w + "null argument");
-    if (p->size != sizeof(rt_temporal_params)) return fail(RT_ERR_INVALID, w + "params.size is not sizeof(rt_temporal_params)");
-    if (b->size != sizeof(rt_temporal_buffers)) return fail(RT_ERR_INVALID, w + "buffers.size is not sizeof(rt_temporal_buffers)");
-    if (!p->width || p->width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
-    if (!p->height || p->height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
-    if (!std::isfinite(p->alpha_min) || !(p->alpha_min > 0.f) || p->alpha_min > 1.f)
-        return fail(RT_ERR_INVALID, w + "alpha_min must be above 0 and at most 1");
-    if (!std::isfinite(p->max_history) || p->max_history < 1.f) return fail(RT_ERR_INVALID, w + "max_history must be finite and at least 1");
-    if (!std::isfinite(p->normal_tol) || p->normal_tol < 0.f) return fail(RT_ERR_INVALID, w + "normal_tol must be finite and not negative");
-    if (!std::isfinite(p->depth_tol) || p->depth_tol < 0.f) return fail(RT_ERR_INVALID, w + "depth_tol must be finite and not negative");
-    if (p->flags) return fail(RT_ERR_INVALID, w + "flags must be 0 (none is defined)");
-    if (!cam) return fail(RT_ERR_INVALID, w + "camera is null");
-    if (cam->mode > RT_CAMERA_CORRECTED) return fail(RT_ERR_INVALID, w + "camera has a bad mode");
-    const struct { const char *name; const void *ptr; } cur[6] = {{"beauty", b->beauty}, {"variance", b->variance}, {"normal", b->normal},
-                                                                 {"depth", b->depth},   {"alpha", b->alpha},       {"sphere_id", b->sphere_id}},
-      prev[6] = {{"prev_color", b->prev_color},   {"prev_variance", b->prev_variance}, {"prev_history", b->prev_history},
-                 {"prev_normal", b->prev_normal}, {"prev_depth", b->prev_depth},       {"prev_sphere_id", b->prev_sphere_id}},
-      out[3] = {{"out_color", b->out_color}, {"out_variance", b->out_variance}, {"out_history", b->out_history}};
-    for (const auto &c : cur)
-        if (!c.ptr) return fail(RT_ERR_INVALID, w + c.name + " is null");
-    for (const auto &o : out)
-        if (!o.ptr) return fail(RT_ERR_INVALID, w + o.name + " is null");
-    int given = 0;
-    for (const auto &c : prev) given += c.ptr ? 1 : 0;
-    if (given != 0 && given != 6)
-        for (const auto &c : prev)
-            if (!c.ptr) return fail(RT_ERR_INVALID, w + c.name + " is null while other planes of prev are given");
-    for (int i = 0; i < 3; ++i) {
-        for (const auto &c : cur)
-            if (c.ptr == out[i].ptr) return fail(RT_ERR_INVALID, w + out[i].name + " is also the input plane " + c.name);
-        for (const auto &c : prev)
-            if (c.ptr == out[i].ptr) return fail(RT_ERR_INVALID, w + out[i].name + " is also the input plane " + c.name);
-        for (int j = 0; j < i; ++j)
-            if (out[j].ptr == out[i].ptr) return fail(RT_ERR_INVALID, w + out[i].name + " is also " + out[j].name);
-    }
-    rt::KTemporal t{};
-    if (given) {
-        if (!prev_cam) return fail(RT_ERR_INVALID, w + "prev_camera is null");
-        if (rt_reproject_basis(prev_cam, t.basis) != RT_OK) return fail(RT_ERR_INVALID, w + g_error.substr(g_error.find(": ") + 2));
-    }
-    t.beauty = b->beauty, t.variance = b->variance, t.normal = b->normal, t.depth = b->depth, t.alpha = b->alpha;
-    t.id = b->sphere_id;
-    t.p_color = b->prev_color, t.p_variance = b->prev_variance, t.p_history = b->prev_history;
-    t.p_normal = b->prev_normal, t.p_depth = b->prev_depth, t.p_id = b->prev_sphere_id;
-    t.o_color = b->out_color, t.o_variance = b->out_variance, t.o_history = b->out_history;
-    t.W = p->width, t.H = p->height;
-    for (int c = 0; c < 3; ++c) {
-        t.a[c] = cam->mode == RT_CAMERA_CORRECTED ? cam->lower_left_corner[c] - cam->origin[c] : cam->lower_left_corner[c];
-        t.hor[c] = cam->horizontal[c], t.ver[c] = cam->vertical[c], t.o[c] = cam->origin[c];
-    }
-    t.alpha_min = p->alpha_min, t.max_history = p->max_history, t.normal_tol = p->normal_tol, t.depth_tol = p->depth_tol;
-    *k = t;
-    return RT_OK;
-}
-
-// Synchronous temporal accumulation of host planes through the cached context's buffer.
-int temporal_host(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
-                  const rt_temporal_buffers *buffers, rt_stats *stats)
-{
-    rt::KTemporal k{};
-    if (int rc = check_temporal(params, camera, prev_camera, buffers, "rt_temporal", &k); rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    int dev = 0;
-    RT_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_sync_mu);
-    SyncContext &cx = g_sync[dev];
-    const size_t n = static_cast<size_t>(params->width) * params->height;
-    // the current planes, the previous ones (inputs), then the outputs, 256-byte aligned
-    struct Plane { const void *host; uint32_t channels; size_t at; };
-    Plane planes[15] = {{buffers->beauty, 3, 0},       {buffers->variance, 1, 0},      {buffers->normal, 3, 0},
-                        {buffers->depth, 1, 0},        {buffers->alpha, 1, 0},         {buffers->sphere_id, 1, 0},
-                        {buffers->prev_color, 3, 0},   {buffers->prev_variance, 1, 0}, {buffers->prev_history, 1, 0},
-                        {buffers->prev_normal, 3, 0},  {buffers->prev_depth, 1, 0},    {buffers->prev_sphere_id, 1, 0},
-                        {buffers->out_color, 3, 0},    {buffers->out_variance, 1, 0},  {buffers->out_history, 1, 0}};
-    size_t total = 0;
-    for (Plane &pl : planes)
-        if (pl.host) {
-            pl.at = total;
-            total += (n * pl.channels * 4u + 255u) & ~static_cast<size_t>(255u);
-        }
-    int rc = RT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-        return rc == RT_OK;
-    };
-    if (cx.dn_bytes < total || !cx.d_dn) {
-        if (cx.d_dn) chk(hipFree(cx.d_dn), "hipFree");
-        cx.d_dn = nullptr;
-        cx.dn_bytes = 0;
-        if (chk(hipMalloc(&cx.d_dn, std::max<size_t>(total, 256)), "hipMalloc")) cx.dn_bytes = total;
-    }
-    if (rc == RT_OK && !cx.e0) chk(hipEventCreate(&cx.e0), "hipEventCreate");
-    if (rc == RT_OK && !cx.e1) chk(hipEventCreate(&cx.e1), "hipEventCreate");
-    float ms = 0.f;
-    if (rc == RT_OK) {
-        char *base = static_cast<char *>(cx.d_dn);
-        auto fptr = [&](int i) { return planes[i].host ? reinterpret_cast<float *>(base + planes[i].at) : nullptr; };
-        auto uptr = [&](int i) { return planes[i].host ? reinterpret_cast<uint32_t *>(base + planes[i].at) : nullptr; };
-        for (int i = 0; i < 12; ++i)
-            if (rc == RT_OK && planes[i].host)
-                chk(hipMemcpy(base + planes[i].at, planes[i].host, n * planes[i].channels * 4u, hipMemcpyHostToDevice), "hipMemcpy");
-        k.beauty = fptr(0), k.variance = fptr(1), k.normal = fptr(2), k.depth = fptr(3), k.alpha = fptr(4), k.id = uptr(5);
-        k.p_color = fptr(6), k.p_variance = fptr(7), k.p_history = fptr(8), k.p_normal = fptr(9), k.p_depth = fptr(10);
-        k.p_id = uptr(11);
-        k.o_color = fptr(12), k.o_variance = fptr(13), k.o_history = fptr(14);
-        if (rc == RT_OK) chk(hipEventRecord(cx.e0, nullptr), "hipEventRecord");
-        if (rc == RT_OK) chk(rt::launch_temporal(k, nullptr), "rt_temporal");
-        if (rc == RT_OK) chk(hipEventRecord(cx.e1, nullptr), "hipEventRecord");
-        // the copies on the null stream follow the kernel
-        for (int i = 12; i < 15; ++i)
-            if (rc == RT_OK)
-                chk(hipMemcpy(const_cast<void *>(planes[i].host), base + planes[i].at, n * planes[i].channels * 4u, hipMemcpyDeviceToHost),
-                    "hipMemcpy");
-        if (rc == RT_OK) chk(hipDeviceSynchronize(), "rt_temporal");
-        if (rc == RT_OK) chk(hipEventElapsedTime(&ms, cx.e0, cx.e1), "hipEventElapsedTime");
-    }
-    if (rc != RT_OK) {
-        // a failed call leaves no state behind: the next one starts from a new context
-        const std::string msg = g_error;
-        sync_release(dev, cx);
-        g_error = msg;
-    }
-    if (rc == RT_OK && stats) {
-        *stats = rt_stats{};
-        stats->kernel_ms = ms;
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
+    const SyncRows rows = rendered_rows(P);
+    const size_t rows_out = (P.flags & RT_FLAG_FULL_FRAME) ? P.height : rows.rows;
+    Plane planes[2] = {plane_out(rgb_out, 12), plane_out(var_out, 4)};
+    const SyncScene scene{spheres, n_spheres, materials, n_materials};
+    SyncCall call;
+    const int rc = call.run({"rt_render_var", planes, 2, rows_out * P.width, rows, &scene, stats != nullptr, rows.rows == 0}, [&] {
+        return rt_render_var_device(call.scene, camera, params, planes[0].as<float>(), planes[1].as<float>(), nullptr,
+                                    call.d_counters);
+    });
+    if (rc == RT_OK && stats) render_stats(*stats, call, static_cast<uint64_t>(P.width) * rows.rows * P.spp);
     return rc;
 }
 
@@ -2420,93 +1906,10 @@ int temporal_host(const rt_temporal_params *params, const rt_camera *camera, con
 
 extern "C" {
 
-int rt_temporal_params_default(uint32_t width, uint32_t height, rt_temporal_params *out)
-{
-    if (!out) return fail(RT_ERR_INVALID, "rt_temporal_params_default: null argument");
-    if (!width || !height) return fail(RT_ERR_INVALID, "rt_temporal_params_default: zero width or height");
-    *out = rt_temporal_params{static_cast<uint32_t>(sizeof(rt_temporal_params)), width, height, kTpAlphaMin, kTpMaxHistory,
-                              kTpNormalTol, kTpDepthTol, 0u};
-    return RT_OK;
-}
-
-int rt_temporal_device(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
-                       const rt_temporal_buffers *buffers, void *stream)
-{
-    rt::KTemporal k{};
-    if (int rc = check_temporal(params, camera, prev_camera, buffers, "rt_temporal_device", &k); rc != RT_OK) return rc;
-    RT_HIP(rt::launch_temporal(k, static_cast<hipStream_t>(stream)));
-    return RT_OK;
-}
-
-int rt_temporal(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
-                const rt_temporal_buffers *buffers, rt_stats *stats)
-{
-    return temporal_host(params, camera, prev_camera, buffers, stats);
-}
-
-int rt_denoise_var_params_default(uint32_t width, uint32_t height, rt_denoise_params *params, rt_denoise_var_buffers *var)
-{
-    if (!params && !var) return fail(RT_ERR_INVALID, "rt_denoise_var_params_default: null argument");
-    if (!width || !height) return fail(RT_ERR_INVALID, "rt_denoise_var_params_default: zero width or height");
-    // chosen by the CPU sweep of DESIGN.md §4.10 (scripts/denoise_var_sweep.py)
-    if (params)
-        *params = rt_denoise_params{static_cast<uint32_t>(sizeof(rt_denoise_params)), width, height, kDnVarLevels,
-                                    kDnVarSigmaColor, kDnVarSigmaNormal, kDnVarSigmaDepth, kDnVarSigmaAlbedo, 0u};
-    if (var)
-        *var = rt_denoise_var_buffers{static_cast<uint32_t>(sizeof(rt_denoise_var_buffers)), kDnVarFloor, nullptr, nullptr,
-                                      nullptr};
-    return RT_OK;
-}
-
-int rt_denoise_var_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
-                          const rt_denoise_var_buffers *var, void *stream)
-{
-    uint32_t terms = 0;
-    if (int rc = check_denoise_var(params, buffers, var, true, "rt_denoise_var_device", &terms); rc != RT_OK) return rc;
-    return denoise_var_levels(*params, *buffers, *var, terms, static_cast<hipStream_t>(stream));
-}
-
-int rt_denoise_var(const rt_denoise_params *params, const rt_denoise_buffers *buffers, const rt_denoise_var_buffers *var,
-                   rt_stats *stats)
-{
-    return denoise_var_host(params, buffers, var, stats);
-}
-
 int rt_render_var(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
                   const rt_camera *camera, const rt_params *params, float *rgb_out, float *var_out, rt_stats *stats)
 {
     return render_var_host(spheres, n_spheres, materials, n_materials, camera, params, rgb_out, var_out, stats);
-}
-
-int rt_denoise_params_default(uint32_t width, uint32_t height, rt_denoise_params *out)
-{
-    if (!out) return fail(RT_ERR_INVALID, "rt_denoise_params_default: null argument");
-    if (!width || !height) return fail(RT_ERR_INVALID, "rt_denoise_params_default: zero width or height");
-    // chosen by the CPU sweep of DESIGN.md §4.9
-    *out = rt_denoise_params{static_cast<uint32_t>(sizeof(rt_denoise_params)), width, height, 2u, 4.0f, 2.0f, 1.0f, 1.0f, 0u};
-    return RT_OK;
-}
-
-int rt_denoise_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers, void *stream)
-{
-    uint32_t terms = 0;
-    if (int rc = check_denoise(params, buffers, true, "rt_denoise_device", &terms); rc != RT_OK) return rc;
-    return denoise_levels(*params, *buffers, terms, 0, params->levels - 1u, kDenoiseTiledMaxStep,
-                          static_cast<hipStream_t>(stream));
-}
-
-int rt_denoise_level_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers, uint32_t level,
-                            void *stream)
-{
-    uint32_t terms = 0;
-    if (int rc = check_denoise(params, buffers, false, "rt_denoise_level_device", &terms); rc != RT_OK) return rc;
-    if (level >= params->levels) return fail(RT_ERR_INVALID, "rt_denoise_level_device: level is not below levels");
-    return denoise_levels(*params, *buffers, terms, level, level, kDenoiseTiledFits, static_cast<hipStream_t>(stream));
-}
-
-int rt_denoise(const rt_denoise_params *params, const rt_denoise_buffers *buffers, rt_stats *stats)
-{
-    return denoise_host(params, buffers, stats);
 }
 
 int rt_render_aov(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,

@@ -950,6 +950,18 @@ bool exact_by_reciprocal(float b)
     return ok;
 }
 
+size_t plane_layout(Plane *planes, size_t n_planes, size_t n_px)
+{
+    size_t total = 0;
+    for (size_t i = 0; i < n_planes; ++i) {
+        Plane &pl = planes[i];
+        if (pl.kind == Plane::Absent) continue;
+        pl.at = total;
+        total += (n_px * pl.px_bytes + 255u) & ~static_cast<size_t>(255u);
+    }
+    return total;
+}
+
 } // namespace rthost
 
 extern "C" {

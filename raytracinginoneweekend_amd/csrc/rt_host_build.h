@@ -70,4 +70,27 @@ tile_order classify_tiles(const rt_camera &cam, uint32_t W, uint32_t H, uint32_t
 rt::UDiv make_udiv(uint32_t d);
 bool exact_by_reciprocal(float b);
 
+// ---- the plane table of a synchronous host-buffer call (rt_host_sync.h SyncCall) ----------
+// One plane of the call in the cached context's device arena: an input is uploaded from `host`
+// before the work, an output copied back to `host` after it, a scratch plane lives on the
+// device only. An absent plane takes no room and no copy; its `dev` stays null.
+struct Plane {
+    enum Kind : uint32_t { Absent, In, Out, Scratch } kind;
+    void *host;          // In (only read) / Out: the caller's plane
+    uint32_t px_bytes;   // bytes per pixel
+    bool clear = false;  // zeroed on the device before the work
+    size_t at = 0;       // plane_layout: its offset in the arena
+    void *dev = nullptr;  // SyncCall::run: its address on the device
+    template <class T> T *as() const { return static_cast<T *>(dev); }
+};
+inline Plane plane_in(const void *host, uint32_t px_bytes)
+{
+    return {host ? Plane::In : Plane::Absent, const_cast<void *>(host), px_bytes};
+}
+inline Plane plane_out(void *host, uint32_t px_bytes) { return {host ? Plane::Out : Plane::Absent, host, px_bytes}; }
+inline Plane plane_scratch(bool wanted, uint32_t px_bytes) { return {wanted ? Plane::Scratch : Plane::Absent, nullptr, px_bytes}; }
+// Packs the planes that are there, n_px pixels each, in table order from offset 0 with every
+// offset a multiple of 256 bytes (`at`); returns the bytes they take together.
+size_t plane_layout(Plane *planes, size_t n_planes, size_t n_px);
+
 } // namespace rthost

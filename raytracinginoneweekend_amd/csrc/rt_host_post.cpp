@@ -1,0 +1,411 @@
+// rt_host_post.cpp — the post-process stages of the C-ABI (include/rt_api.h), which use nothing of
+// a device scene: the à-trous denoiser, its variance-guided form and temporal accumulation, each
+// with its argument checks, defaults, level driver, stream-ordered *_device entry point and the
+// synchronous host-plane call through the cached context (rt_host_sync.h SyncCall). The kernels
+// are rt_denoise.hip and rt_temporal.hip.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/rt_api.h"
+#include "rt_device.h"
+#include "rt_host_build.h"
+#include "rt_host_sync.h"
+
+using namespace rthost;
+
+namespace {
+
+// ---- the à-trous denoiser (include/rt_api.h; kernels in rt_denoise.hip) ----------------------
+// Levels with a step up to this take the tiled kernel: at 1280x720 with every guide it takes 0.77
+// of the direct kernel's time at steps 1 and 2 and 1.03 at step 4, where its halo is as large as
+// its tile (profiles/denoise/time_c3.txt). Its LDS image at step 2 is 37.5 KiB.
+constexpr uint32_t kDenoiseTiledMaxStep = 2;
+// The largest step the tiled kernel can take at all (rt_denoise_level_device's A/B): its LDS image
+// with every guide is then 60 KiB, the most a launch gets without asking for more.
+constexpr uint32_t kDenoiseTiledFits = 4;
+constexpr uint32_t kDenoiseMaxSide = 65536;
+// rt_denoise_var_params_default: the values scripts/denoise_var_sweep.py chose
+constexpr uint32_t kDnVarLevels = 2;
+constexpr float kDnVarSigmaColor = 32.0f, kDnVarSigmaNormal = 1.0f, kDnVarSigmaDepth = 4.0f, kDnVarSigmaAlbedo = 1.0f;
+constexpr float kDnVarFloor = 1e-6f;
+
+// Every argument check of the denoiser, before any HIP call (use_scratch: the call uses
+// buffers.scratch). terms: the edge terms that are on.
+int check_denoise(const rt_denoise_params *p, const rt_denoise_buffers *b, bool use_scratch, const char *who,
+                  uint32_t *terms)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!p || !b) return fail(RT_ERR_INVALID, w + "null argument");
+    if (p->size != sizeof(rt_denoise_params)) return fail(RT_ERR_INVALID, w + "params.size is not sizeof(rt_denoise_params)");
+    if (b->size != sizeof(rt_denoise_buffers)) return fail(RT_ERR_INVALID, w + "buffers.size is not sizeof(rt_denoise_buffers)");
+    if (!p->width || p->width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
+    if (!p->height || p->height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    if (p->levels < 1u || p->levels > 6u) return fail(RT_ERR_INVALID, w + "levels must be 1..6");
+    const struct { const char *name; float v; } sig[4] = {{"sigma_color", p->sigma_color}, {"sigma_normal", p->sigma_normal},
+                                                          {"sigma_depth", p->sigma_depth}, {"sigma_albedo", p->sigma_albedo}};
+    for (const auto &s : sig)
+        if (!std::isfinite(s.v) || s.v < 0.f) return fail(RT_ERR_INVALID, w + s.name + " must be finite and not negative");
+    if (p->flags & ~static_cast<uint32_t>(RT_DENOISE_DEMODULATE | RT_DENOISE_DIRECT))
+        return fail(RT_ERR_INVALID, w + "unknown bits in flags");
+    if (!b->beauty) return fail(RT_ERR_INVALID, w + "beauty is null");
+    if (!b->out) return fail(RT_ERR_INVALID, w + "out is null");
+    if (b->normal && p->sigma_normal == 0.f) return fail(RT_ERR_INVALID, w + "sigma_normal is 0 with a normal plane");
+    if (b->depth && p->sigma_depth == 0.f) return fail(RT_ERR_INVALID, w + "sigma_depth is 0 with a depth plane");
+    if ((p->flags & RT_DENOISE_DEMODULATE) && !b->albedo)
+        return fail(RT_ERR_INVALID, w + "RT_DENOISE_DEMODULATE needs the albedo plane");
+    if (p->sigma_color != 0.f) {
+        const float s = p->sigma_color * std::ldexp(1.f, -static_cast<int>(p->levels - 1u));
+        if (!std::isfinite(1.0f / (s * s))) return fail(RT_ERR_INVALID, w + "sigma_color is too small for this many levels");
+    }
+    for (const auto &s : {sig[1], sig[2], sig[3]})
+        if (s.v != 0.f && !std::isfinite(1.0f / (s.v * s.v))) return fail(RT_ERR_INVALID, w + s.name + " is too small");
+    const bool need_scratch = use_scratch && p->levels > 1u;
+    if (need_scratch && !b->scratch) return fail(RT_ERR_INVALID, w + "scratch is null with levels > 1");
+    const float *const scratch = use_scratch ? b->scratch : nullptr;
+    for (const float *in : {b->beauty, b->albedo, b->normal, b->depth}) {
+        if (in && in == b->out) return fail(RT_ERR_INVALID, w + "out is also an input plane");
+        if (in && in == scratch) return fail(RT_ERR_INVALID, w + "scratch is also an input plane");
+    }
+    if (scratch && scratch == b->out) return fail(RT_ERR_INVALID, w + "scratch is also out");
+    *terms = (p->sigma_color != 0.f ? 1u : 0u) | (b->normal ? 2u : 0u) | (b->depth ? 4u : 0u) |
+             (b->albedo && p->sigma_albedo != 0.f ? 8u : 0u);
+    return RT_OK;
+}
+
+float denoise_r(float sigma) { return 1.0f / (sigma * sigma); }
+
+// The part of the kernel's record that is the same at every level of a run, of either filter: the
+// guides, the image and the guides' weights (the albedo plane also where only demodulation reads it).
+rt::KDenoise denoise_record(const rt_denoise_params &p, const rt_denoise_buffers &b, uint32_t terms)
+{
+    rt::KDenoise k{};
+    k.albedo = (terms & 8u) || (p.flags & RT_DENOISE_DEMODULATE) ? b.albedo : nullptr;
+    k.normal = b.normal;
+    k.depth = b.depth;
+    k.W = p.width;
+    k.H = p.height;
+    k.r_n = (terms & 2u) ? denoise_r(p.sigma_normal) : 0.f;
+    k.r_z = (terms & 4u) ? denoise_r(p.sigma_depth) : 0.f;
+    k.r_a = (terms & 8u) ? denoise_r(p.sigma_albedo) : 0.f;
+    return k;
+}
+
+// Where level l of a run ending with level `last` writes: the last one b.out, those before it
+// alternately b.scratch and b.out so that it does.
+float *denoise_level_out(const rt_denoise_buffers &b, uint32_t l, uint32_t last)
+{
+    return ((last - l) & 1u) ? b.scratch : b.out;
+}
+
+// Enqueue levels [first, last] of the run `p` describes: level l reads `in` when l == first and
+// the previous level's output otherwise (denoise_level_out). Steps up to tiled_max_step take the
+// tiled kernel.
+int denoise_levels(const rt_denoise_params &p, const rt_denoise_buffers &b, uint32_t terms, uint32_t first,
+                   uint32_t last, uint32_t tiled_max_step, hipStream_t stream)
+{
+    const bool demod = (p.flags & RT_DENOISE_DEMODULATE) != 0u;
+    rt::KDenoise k = denoise_record(p, b, terms);
+    const float *in = b.beauty;
+    for (uint32_t l = first; l <= last; ++l) {
+        k.in = in;
+        k.out = denoise_level_out(b, l, last);
+        k.step = 1u << l;
+        k.r_c = (terms & 1u) ? denoise_r(p.sigma_color * std::ldexp(1.f, -static_cast<int>(l))) : 0.f;
+        k.demod_out = demod && l + 1u == p.levels;
+        const bool tiled = !(p.flags & RT_DENOISE_DIRECT) && k.step <= tiled_max_step;
+        RT_HIP(rt::launch_denoise(k, terms, demod && l == 0u, tiled, stream));
+        in = k.out;
+    }
+    return RT_OK;
+}
+
+// The caller's record with the planes' addresses on the device: planes[0..3] the inputs, then out
+// and scratch.
+rt_denoise_buffers denoise_device_record(const Plane *planes, int out, int scratch)
+{
+    return {static_cast<uint32_t>(sizeof(rt_denoise_buffers)), planes[0].as<float>(), planes[1].as<float>(),
+            planes[2].as<float>(), planes[3].as<float>(), planes[out].as<float>(), planes[scratch].as<float>()};
+}
+
+// A filter's or the accumulation's record: zeroed but for the two times.
+void timed_stats(rt_stats &st, const SyncCall &call)
+{
+    st = rt_stats{};
+    st.kernel_ms = call.kernel_ms;
+    st.wall_ms = call.wall_ms();
+}
+
+// Synchronous denoise of host planes.
+int denoise_host(const rt_denoise_params *params, const rt_denoise_buffers *buffers, rt_stats *stats)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise(params, buffers, false, "rt_denoise", &terms); rc != RT_OK) return rc;
+    const rt_denoise_params &P = *params;
+    const size_t n = static_cast<size_t>(P.width) * P.height;
+    Plane planes[6] = {plane_in(buffers->beauty, 12), plane_in(buffers->albedo, 12), plane_in(buffers->normal, 12),
+                       plane_in(buffers->depth, 4),   plane_out(buffers->out, 12),   plane_scratch(P.levels > 1u, 12)};
+    SyncCall call;
+    const int rc = call.run({"rt_denoise", planes, 6, n, {n, 1}}, [&] {
+        return denoise_levels(P, denoise_device_record(planes, 4, 5), terms, 0, P.levels - 1u, kDenoiseTiledMaxStep, nullptr);
+    });
+    if (rc == RT_OK && stats) timed_stats(*stats, call);
+    return rc;
+}
+
+// ---- the variance-guided filter (include/rt_api.h) ---------------------------
+// Its checks: rt_denoise_device's, then the variance record's (use_scratch: a device call).
+int check_denoise_var(const rt_denoise_params *p, const rt_denoise_buffers *b, const rt_denoise_var_buffers *v,
+                      bool use_scratch, const char *who, uint32_t *terms)
+{
+    if (int rc = check_denoise(p, b, use_scratch, who, terms); rc != RT_OK) return rc;
+    const std::string w = std::string(who) + ": ";
+    if (p->flags & RT_DENOISE_DEMODULATE)
+        return fail(RT_ERR_UNSUPPORTED, w + "RT_DENOISE_DEMODULATE is not supported (the variance is not demodulated)");
+    if (!v) return fail(RT_ERR_INVALID, w + "null variance record");
+    if (v->size != sizeof(rt_denoise_var_buffers))
+        return fail(RT_ERR_INVALID, w + "var.size is not sizeof(rt_denoise_var_buffers)");
+    if (!std::isfinite(v->var_floor) || !(v->var_floor > 0.f)) return fail(RT_ERR_INVALID, w + "var_floor must be finite and positive");
+    if (!v->variance) return fail(RT_ERR_INVALID, w + "variance is null");
+    const float *const var_scratch = use_scratch ? v->var_scratch : nullptr;
+    if (use_scratch && !var_scratch) return fail(RT_ERR_INVALID, w + "var_scratch is null");
+    const float *const scratch = use_scratch ? b->scratch : nullptr;
+    for (const float *o : {b->beauty, b->albedo, b->normal, b->depth, static_cast<const float *>(b->out), scratch,
+                           v->variance}) {
+        if (o && o == v->variance_out) return fail(RT_ERR_INVALID, w + "variance_out is also another plane");
+        if (o && o == var_scratch) return fail(RT_ERR_INVALID, w + "var_scratch is also another plane");
+    }
+    if (var_scratch && var_scratch == v->variance_out) return fail(RT_ERR_INVALID, w + "var_scratch is also variance_out");
+    return RT_OK;
+}
+
+// Enqueue every level: the colours go where denoise_levels' do, the variances alternate between
+// the halves of v.var_scratch; the last level's goes to v.variance_out, if given.
+int denoise_var_levels(const rt_denoise_params &p, const rt_denoise_buffers &b, const rt_denoise_var_buffers &v,
+                       uint32_t terms, hipStream_t stream)
+{
+    rt::KDenoiseVar kv{};
+    rt::KDenoise &k = kv.d;
+    k = denoise_record(p, b, terms);
+    kv.sc2 = p.sigma_color * p.sigma_color;
+    kv.var_floor = v.var_floor;
+    const size_t n = static_cast<size_t>(p.width) * p.height;
+    const float *in = b.beauty, *vin = v.variance;
+    const uint32_t last = p.levels - 1u;
+    for (uint32_t l = 0; l <= last; ++l) {
+        k.in = in;
+        k.out = denoise_level_out(b, l, last);
+        k.step = 1u << l;
+        kv.vin = vin;
+        kv.vout = l == last ? v.variance_out : v.var_scratch + (l & 1u) * n;
+        RT_HIP(rt::launch_denoise_var(kv, terms, stream));
+        in = k.out;
+        vin = kv.vout;
+    }
+    return RT_OK;
+}
+
+// Synchronous variance-guided denoise of host planes.
+int denoise_var_host(const rt_denoise_params *params, const rt_denoise_buffers *buffers, const rt_denoise_var_buffers *var,
+                     rt_stats *stats)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise_var(params, buffers, var, false, "rt_denoise_var", &terms); rc != RT_OK) return rc;
+    const rt_denoise_params &P = *params;
+    const size_t n = static_cast<size_t>(P.width) * P.height;
+    const bool more = P.levels > 1u;  // the colour scratch, and the two halves of the variance's
+    Plane planes[9] = {plane_in(buffers->beauty, 12), plane_in(buffers->albedo, 12),   plane_in(buffers->normal, 12),
+                       plane_in(buffers->depth, 4),   plane_in(var->variance, 4),      plane_out(buffers->out, 12),
+                       plane_scratch(more, 12),       plane_out(var->variance_out, 4), plane_scratch(more, 8)};
+    SyncCall call;
+    const int rc = call.run({"rt_denoise_var", planes, 9, n, {n, 1}}, [&] {
+        const rt_denoise_var_buffers dv{static_cast<uint32_t>(sizeof(rt_denoise_var_buffers)), var->var_floor,
+                                        planes[4].as<float>(), planes[7].as<float>(), planes[8].as<float>()};
+        return denoise_var_levels(P, denoise_device_record(planes, 5, 6), dv, terms, nullptr);
+    });
+    if (rc == RT_OK && stats) timed_stats(*stats, call);
+    return rc;
+}
+
+// ---- temporal accumulation (include/rt_api.h; kernel in rt_temporal.hip) ------
+// rt_temporal_params_default: the values scripts/temporal_sweep.py chose
+constexpr float kTpAlphaMin = 0.4f, kTpMaxHistory = 32.0f, kTpNormalTol = 0.5f, kTpDepthTol = 0.1f;
+
+// Every argument check, before any HIP call; fills the kernel's record (the cameras as the
+// contract's {a, hor, ver, o} and {A, B, G, o'}) from the caller's pointers.
+int check_temporal(const rt_temporal_params *p, const rt_camera *cam, const rt_camera *prev_cam,
+                   const rt_temporal_buffers *b, const char *who, rt::KTemporal *k)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!p || !b) return fail(RT_ERR_INVALID, w + "null argument");
+    if (p->size != sizeof(rt_temporal_params)) return fail(RT_ERR_INVALID, w + "params.size is not sizeof(rt_temporal_params)");
+    if (b->size != sizeof(rt_temporal_buffers)) return fail(RT_ERR_INVALID, w + "buffers.size is not sizeof(rt_temporal_buffers)");
+    if (!p->width || p->width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
+    if (!p->height || p->height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    if (!std::isfinite(p->alpha_min) || !(p->alpha_min > 0.f) || p->alpha_min > 1.f)
+        return fail(RT_ERR_INVALID, w + "alpha_min must be above 0 and at most 1");
+    if (!std::isfinite(p->max_history) || p->max_history < 1.f) return fail(RT_ERR_INVALID, w + "max_history must be finite and at least 1");
+    if (!std::isfinite(p->normal_tol) || p->normal_tol < 0.f) return fail(RT_ERR_INVALID, w + "normal_tol must be finite and not negative");
+    if (!std::isfinite(p->depth_tol) || p->depth_tol < 0.f) return fail(RT_ERR_INVALID, w + "depth_tol must be finite and not negative");
+    if (p->flags) return fail(RT_ERR_INVALID, w + "flags must be 0 (none is defined)");
+    if (!cam) return fail(RT_ERR_INVALID, w + "camera is null");
+    if (cam->mode > RT_CAMERA_CORRECTED) return fail(RT_ERR_INVALID, w + "camera has a bad mode");
+    const struct { const char *name; const void *ptr; } cur[6] = {{"beauty", b->beauty}, {"variance", b->variance}, {"normal", b->normal},
+                                                                 {"depth", b->depth},   {"alpha", b->alpha},       {"sphere_id", b->sphere_id}},
+      prev[6] = {{"prev_color", b->prev_color},   {"prev_variance", b->prev_variance}, {"prev_history", b->prev_history},
+                 {"prev_normal", b->prev_normal}, {"prev_depth", b->prev_depth},       {"prev_sphere_id", b->prev_sphere_id}},
+      out[3] = {{"out_color", b->out_color}, {"out_variance", b->out_variance}, {"out_history", b->out_history}};
+    for (const auto &c : cur)
+        if (!c.ptr) return fail(RT_ERR_INVALID, w + c.name + " is null");
+    for (const auto &o : out)
+        if (!o.ptr) return fail(RT_ERR_INVALID, w + o.name + " is null");
+    int given = 0;
+    for (const auto &c : prev) given += c.ptr ? 1 : 0;
+    if (given != 0 && given != 6)
+        for (const auto &c : prev)
+            if (!c.ptr) return fail(RT_ERR_INVALID, w + c.name + " is null while other planes of prev are given");
+    for (int i = 0; i < 3; ++i) {
+        for (const auto &c : cur)
+            if (c.ptr == out[i].ptr) return fail(RT_ERR_INVALID, w + out[i].name + " is also the input plane " + c.name);
+        for (const auto &c : prev)
+            if (c.ptr == out[i].ptr) return fail(RT_ERR_INVALID, w + out[i].name + " is also the input plane " + c.name);
+        for (int j = 0; j < i; ++j)
+            if (out[j].ptr == out[i].ptr) return fail(RT_ERR_INVALID, w + out[i].name + " is also " + out[j].name);
+    }
+    rt::KTemporal t{};
+    if (given) {
+        if (!prev_cam) return fail(RT_ERR_INVALID, w + "prev_camera is null");
+        if (rt_reproject_basis(prev_cam, t.basis) != RT_OK) return fail(RT_ERR_INVALID, w + g_error.substr(g_error.find(": ") + 2));
+    }
+    t.beauty = b->beauty, t.variance = b->variance, t.normal = b->normal, t.depth = b->depth, t.alpha = b->alpha;
+    t.id = b->sphere_id;
+    t.p_color = b->prev_color, t.p_variance = b->prev_variance, t.p_history = b->prev_history;
+    t.p_normal = b->prev_normal, t.p_depth = b->prev_depth, t.p_id = b->prev_sphere_id;
+    t.o_color = b->out_color, t.o_variance = b->out_variance, t.o_history = b->out_history;
+    t.W = p->width, t.H = p->height;
+    for (int c = 0; c < 3; ++c) {
+        t.a[c] = cam->mode == RT_CAMERA_CORRECTED ? cam->lower_left_corner[c] - cam->origin[c] : cam->lower_left_corner[c];
+        t.hor[c] = cam->horizontal[c], t.ver[c] = cam->vertical[c], t.o[c] = cam->origin[c];
+    }
+    t.alpha_min = p->alpha_min, t.max_history = p->max_history, t.normal_tol = p->normal_tol, t.depth_tol = p->depth_tol;
+    *k = t;
+    return RT_OK;
+}
+
+// Synchronous temporal accumulation of host planes: the current planes, the previous ones, then
+// the outputs.
+int temporal_host(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                  const rt_temporal_buffers *buffers, rt_stats *stats)
+{
+    rt::KTemporal k{};
+    if (int rc = check_temporal(params, camera, prev_camera, buffers, "rt_temporal", &k); rc != RT_OK) return rc;
+    const size_t n = static_cast<size_t>(params->width) * params->height;
+    const rt_temporal_buffers &b = *buffers;
+    Plane planes[15] = {plane_in(b.beauty, 12),     plane_in(b.variance, 4),      plane_in(b.normal, 12),
+                        plane_in(b.depth, 4),       plane_in(b.alpha, 4),         plane_in(b.sphere_id, 4),
+                        plane_in(b.prev_color, 12), plane_in(b.prev_variance, 4), plane_in(b.prev_history, 4),
+                        plane_in(b.prev_normal, 12), plane_in(b.prev_depth, 4),   plane_in(b.prev_sphere_id, 4),
+                        plane_out(b.out_color, 12), plane_out(b.out_variance, 4), plane_out(b.out_history, 4)};
+    SyncCall call;
+    const int rc = call.run({"rt_temporal", planes, 15, n, {n, 1}}, [&] {
+        auto f = [&](int i) { return planes[i].as<float>(); };
+        k.beauty = f(0), k.variance = f(1), k.normal = f(2), k.depth = f(3), k.alpha = f(4), k.id = planes[5].as<uint32_t>();
+        k.p_color = f(6), k.p_variance = f(7), k.p_history = f(8), k.p_normal = f(9), k.p_depth = f(10);
+        k.p_id = planes[11].as<uint32_t>();
+        k.o_color = f(12), k.o_variance = f(13), k.o_history = f(14);
+        return hip_rc(rt::launch_temporal(k, nullptr), "rt_temporal");
+    });
+    if (rc == RT_OK && stats) timed_stats(*stats, call);
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_temporal_params_default(uint32_t width, uint32_t height, rt_temporal_params *out)
+{
+    if (!out) return fail(RT_ERR_INVALID, "rt_temporal_params_default: null argument");
+    if (!width || !height) return fail(RT_ERR_INVALID, "rt_temporal_params_default: zero width or height");
+    *out = rt_temporal_params{static_cast<uint32_t>(sizeof(rt_temporal_params)), width, height, kTpAlphaMin, kTpMaxHistory,
+                              kTpNormalTol, kTpDepthTol, 0u};
+    return RT_OK;
+}
+
+int rt_temporal_device(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                       const rt_temporal_buffers *buffers, void *stream)
+{
+    rt::KTemporal k{};
+    if (int rc = check_temporal(params, camera, prev_camera, buffers, "rt_temporal_device", &k); rc != RT_OK) return rc;
+    RT_HIP(rt::launch_temporal(k, static_cast<hipStream_t>(stream)));
+    return RT_OK;
+}
+
+int rt_temporal(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                const rt_temporal_buffers *buffers, rt_stats *stats)
+{
+    return temporal_host(params, camera, prev_camera, buffers, stats);
+}
+
+int rt_denoise_var_params_default(uint32_t width, uint32_t height, rt_denoise_params *params, rt_denoise_var_buffers *var)
+{
+    if (!params && !var) return fail(RT_ERR_INVALID, "rt_denoise_var_params_default: null argument");
+    if (!width || !height) return fail(RT_ERR_INVALID, "rt_denoise_var_params_default: zero width or height");
+    // chosen by the CPU sweep of DESIGN.md §4.10 (scripts/denoise_var_sweep.py)
+    if (params)
+        *params = rt_denoise_params{static_cast<uint32_t>(sizeof(rt_denoise_params)), width, height, kDnVarLevels,
+                                    kDnVarSigmaColor, kDnVarSigmaNormal, kDnVarSigmaDepth, kDnVarSigmaAlbedo, 0u};
+    if (var)
+        *var = rt_denoise_var_buffers{static_cast<uint32_t>(sizeof(rt_denoise_var_buffers)), kDnVarFloor, nullptr, nullptr,
+                                      nullptr};
+    return RT_OK;
+}
+
+int rt_denoise_var_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers,
+                          const rt_denoise_var_buffers *var, void *stream)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise_var(params, buffers, var, true, "rt_denoise_var_device", &terms); rc != RT_OK) return rc;
+    return denoise_var_levels(*params, *buffers, *var, terms, static_cast<hipStream_t>(stream));
+}
+
+int rt_denoise_var(const rt_denoise_params *params, const rt_denoise_buffers *buffers, const rt_denoise_var_buffers *var,
+                   rt_stats *stats)
+{
+    return denoise_var_host(params, buffers, var, stats);
+}
+
+int rt_denoise_params_default(uint32_t width, uint32_t height, rt_denoise_params *out)
+{
+    if (!out) return fail(RT_ERR_INVALID, "rt_denoise_params_default: null argument");
+    if (!width || !height) return fail(RT_ERR_INVALID, "rt_denoise_params_default: zero width or height");
+    // chosen by the CPU sweep of DESIGN.md §4.9
+    *out = rt_denoise_params{static_cast<uint32_t>(sizeof(rt_denoise_params)), width, height, 2u, 4.0f, 2.0f, 1.0f, 1.0f, 0u};
+    return RT_OK;
+}
+
+int rt_denoise_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers, void *stream)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise(params, buffers, true, "rt_denoise_device", &terms); rc != RT_OK) return rc;
+    return denoise_levels(*params, *buffers, terms, 0, params->levels - 1u, kDenoiseTiledMaxStep,
+                          static_cast<hipStream_t>(stream));
+}
+
+int rt_denoise_level_device(const rt_denoise_params *params, const rt_denoise_buffers *buffers, uint32_t level,
+                            void *stream)
+{
+    uint32_t terms = 0;
+    if (int rc = check_denoise(params, buffers, false, "rt_denoise_level_device", &terms); rc != RT_OK) return rc;
+    if (level >= params->levels) return fail(RT_ERR_INVALID, "rt_denoise_level_device: level is not below levels");
+    return denoise_levels(*params, *buffers, terms, level, level, kDenoiseTiledFits, static_cast<hipStream_t>(stream));
+}
+
+int rt_denoise(const rt_denoise_params *params, const rt_denoise_buffers *buffers, rt_stats *stats)
+{
+    return denoise_host(params, buffers, stats);
+}
+
+} // extern "C"

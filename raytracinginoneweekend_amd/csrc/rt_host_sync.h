@@ -1,0 +1,109 @@
+// rt_host_sync.h — what the device half's two files share (rt_host.cpp: scenes, renders, the
+// cached context; rt_host_post.cpp: the filters and temporal accumulation): the kernels'
+// launchers, the HIP error forms, and the one path every synchronous host-buffer entry point
+// takes through the cached per-device context (SyncCall, implemented in rt_host.cpp).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdint>
+#include <functional>
+#include <mutex>
+#include <string>
+
+#include "../../include/rt_api.h"
+#include "rt_device.h"
+#include "rt_host_build.h"
+
+namespace rt {
+hipError_t launch_render(int variant, int cull, const KParams &p, uint32_t grid, hipStream_t stream, int wpb = 4);
+hipError_t deep_occupancy(int variant, int wpb, size_t lds, int *blocks_per_cu, size_t *static_lds);
+hipError_t occupancy_render(int variant, int cull, int *blocks_per_cu, size_t lds, bool pairs = false);
+hipError_t static_lds_render(int variant, int cull, size_t *bytes, bool pairs = false);
+hipError_t launch_accumulate(const KAccum &k, hipStream_t stream);
+hipError_t launch_compat(const KCompat &k, uint32_t grid, hipStream_t stream);
+hipError_t launch_wave_gen(const KWave &w, hipStream_t stream);
+hipError_t launch_wave_bounce(int cull, const KWave &w, uint32_t grid, hipStream_t stream);
+hipError_t occupancy_wave_bounce(int cull, int *blocks_per_cu, size_t lds);
+hipError_t occupancy_compat(int *blocks_per_cu);
+hipError_t launch_epilogue(const float *in, uint8_t *out, uint64_t n, hipStream_t stream);
+hipError_t launch_sky(const KSky &k, hipStream_t stream);
+// rt_aov.hip
+hipError_t launch_aov(int cull, const KAov &k, uint32_t grid, hipStream_t stream);
+hipError_t occupancy_aov(int cull, int *blocks_per_cu, size_t lds);
+hipError_t static_lds_aov(int cull, size_t *bytes);
+// rt_denoise.hip
+hipError_t launch_denoise(const KDenoise &k, uint32_t terms, bool demod_in, bool tiled, hipStream_t stream);
+hipError_t launch_denoise_var(const KDenoiseVar &k, uint32_t terms, hipStream_t stream);
+size_t denoise_tiled_lds(uint32_t terms, uint32_t step);
+// rt_temporal.hip
+hipError_t launch_temporal(const KTemporal &k, hipStream_t stream);
+} // namespace rt
+
+#define RT_HIP(call)                                                                      \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess)                                                             \
+            return fail(RT_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+namespace rthost {
+
+// RT_OK, or the failure "<what>: <HIP's message>"
+inline int hip_rc(hipError_t e, const char *what)
+{
+    return e == hipSuccess ? RT_OK : fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The scene of a synchronous render: the context keeps its device scene between calls.
+struct SyncScene {
+    const rt_sphere *spheres;
+    uint32_t n_spheres;
+    const rt_material *materials;
+    uint32_t n_materials;
+};
+
+// What the Out planes are copied back as: `rows` rows of `width` pixels, from the plane's start
+// one after the other (stride 0), or rows offset, offset + stride, ... of a frame that wide, each
+// to the same place in the caller's frame (one hipMemcpy2D per plane).
+struct SyncRows {
+    size_t width, rows, offset = 0, stride = 0;
+};
+
+struct SyncSpec {
+    const char *who;  // names the call where its last synchronise fails
+    Plane *planes;    // in upload and download order
+    size_t n_planes;
+    size_t n_px;      // pixels of every plane on the device
+    SyncRows rows;
+    const SyncScene *scene = nullptr;  // a render: the context holds this scene before the work
+    bool counters = false;  // zero the device's work counters before the work, read them after it
+    bool skip = false;      // nothing to do on the device (no rows): the outputs stay as they are
+};
+
+// One synchronous host-buffer call on the current device's cached context, g_sync_mu held from
+// construction to destruction. run(): the context's scene (renders), the planes laid out in its
+// arena, the inputs uploaded, the cleared planes and the counters zeroed, then between the two
+// timing events `enqueue` (the one device entry, on the null stream), then `after` (more work
+// that is not timed), the outputs and counters copied back, and the device synchronised. Any
+// failure releases the device's whole context, its scene included; the first failure's message
+// stays. The wrapper's own argument checks come before the object, so before any HIP call.
+class SyncCall {
+public:
+    SyncCall();
+    int run(const SyncSpec &spec, const std::function<int()> &enqueue, const std::function<int()> &after = {});
+    double wall_ms() const
+    {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count();
+    }
+    rt_scene *scene = nullptr;       // spec.scene's device scene, for `enqueue`
+    uint64_t *d_counters = nullptr;  // spec.counters: the device's three counters, for `enqueue`
+    uint64_t counters[3] = {0, 0, 0};  // ... and their values: segments, sphere tests, box tests
+    float kernel_ms = 0.f;           // between the events around `enqueue`
+
+private:
+    std::chrono::steady_clock::time_point t0_;
+    std::unique_lock<std::mutex> lock_;
+};
+
+} // namespace rthost

@@ -7,7 +7,7 @@
 //   host_check host <golden dir>        scene generators vs the reference's scene dumps, camera
 //                                       vs the restatement, cluster/neighbour-list builder on the
 //                                       huge scene and adversarial scenes, exact-division checks,
-//                                       options parser (fixed and random strings), PPM writer
+//                                       the synchronous calls' plane layout, options parser (fixed and random strings), PPM writer
 //   host_check render <scene.bin> <golden.f32> W H spp depth seed row0 stride rows mode threads
 //                                       the restatement's render vs a golden frame, bit for bit
 //   host_check threads <scene.bin>      (TSan) the restatement on 1 and 4 threads, the exact-division
@@ -218,6 +218,58 @@ void check_divisions()
     CHECK(!rthost::exact_by_reciprocal(0.f) && !rthost::exact_by_reciprocal(-3.f) && !rthost::exact_by_reciprocal(NAN));
 }
 
+// the synchronous calls' device planes (rthost::plane_layout): the planes that are there packed in
+// table order from 0, every offset a multiple of 256, none overlapping, absent ones left alone
+void check_plane_layout()
+{
+    using rthost::Plane;
+    int host = 0;  // any address: a given plane
+    CHECK(rthost::plane_layout(nullptr, 0, 24u * 16u) == 0u);
+    {   // absent planes in the middle take no room and keep their offset
+        Plane t[5] = {rthost::plane_in(&host, 12), rthost::plane_in(nullptr, 12), rthost::plane_scratch(false, 12),
+                      rthost::plane_out(nullptr, 4), rthost::plane_out(&host, 4)};
+        t[1].at = t[2].at = t[3].at = 77u;
+        CHECK(t[0].kind == Plane::In && t[1].kind == Plane::Absent && t[2].kind == Plane::Absent &&
+              t[3].kind == Plane::Absent && t[4].kind == Plane::Out);
+        CHECK(rthost::plane_layout(t, 5, 100u) == 1280u + 512u);
+        CHECK(t[0].at == 0u && t[4].at == 1280u && t[1].at == 77u && t[2].at == 77u && t[3].at == 77u);
+        CHECK(!t[0].dev && !t[4].dev);
+    }
+    {   // one pixel: every plane is one 256-byte unit
+        Plane t[4] = {rthost::plane_in(&host, 12), rthost::plane_out(&host, 4), rthost::plane_scratch(true, 8),
+                      rthost::plane_out(&host, 3)};
+        CHECK(rthost::plane_layout(t, 4, 1u) == 1024u);
+        for (size_t i = 0; i < 4; ++i) CHECK(t[i].at == 256u * i);
+    }
+    {   // a 3-channel and a 1-channel float plane of a 5x3 image
+        Plane t[2] = {rthost::plane_out(&host, 12), rthost::plane_out(&host, 4)};
+        CHECK(rthost::plane_layout(t, 2, 5u * 3u) == 512u);
+        CHECK(t[0].at == 0u && t[1].at == 256u);
+    }
+    {   // an empty image: every plane at 0, nothing taken
+        Plane t[2] = {rthost::plane_out(&host, 12), rthost::plane_out(&host, 3)};
+        CHECK(rthost::plane_layout(t, 2, 0u) == 0u && t[0].at == 0u && t[1].at == 0u);
+    }
+    {   // the temporal call's fifteen planes at 24x16: increasing, aligned, not overlapping, the total their end
+        const uint32_t px[15] = {12, 4, 12, 4, 4, 4, 12, 4, 4, 12, 4, 4, 12, 4, 4};
+        const size_t n = 24u * 16u;
+        Plane t[15];
+        for (int i = 0; i < 15; ++i) t[i] = i < 12 ? rthost::plane_in(&host, px[i]) : rthost::plane_out(&host, px[i]);
+        const size_t total = rthost::plane_layout(t, 15, n);
+        CHECK(t[0].at == 0u);
+        for (int i = 0; i < 15; ++i) {
+            CHECK(t[i].at % 256u == 0u);
+            const size_t end = t[i].at + n * px[i], next = i + 1 < 15 ? t[i + 1].at : total;
+            CHECK(end <= next && next - end < 256u);
+        }
+        CHECK(total % 256u == 0u);
+        // without the previous frame the outputs follow the current planes directly
+        for (int i = 6; i < 12; ++i) t[i] = rthost::plane_in(nullptr, px[i]);
+        const size_t without = rthost::plane_layout(t, 15, n);
+        CHECK(t[12].at == t[5].at + 1536u && without < total);
+    }
+}
+
 void check_options()
 {
     rt_options o;
@@ -338,6 +390,7 @@ int main(int argc, char **argv)
         check_builders(golden);
         check_tiles(golden);
         check_divisions();
+        check_plane_layout();
         check_options();
         check_ppm(golden);
         std::printf("host_check host: %s (%d failed checks)\n", g_fail ? "FAIL" : "ok", g_fail);
