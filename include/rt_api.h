@@ -605,6 +605,105 @@ int rt_temporal_device(const rt_temporal_params *params, const rt_camera *camera
 int rt_temporal(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
                 const rt_temporal_buffers *buffers, rt_stats *stats);
 
+/* ---- the preview session: the whole denoised-preview loop, one call per frame ----
+ * A device-resident object beside the stage entry points above. It owns every plane of the loop
+ * rt_render_var -> rt_render_aov -> rt_temporal -> rt_denoise_var -> epilogue and the prev / cur
+ * bookkeeping of guides and cameras, and enqueues one whole frame on the caller's stream per call:
+ * no host synchronisation and no allocation after rt_preview_create beyond what rt_render_var_device
+ * itself does on a camera's first use. With flags 0 a frame's bits are those of the five stage calls
+ * made by hand. Two switches are capabilities the stage calls do not have:
+ *
+ * RT_PREVIEW_DEMODULATE  the temporal stage and the filter work on illumination, not on albedo x
+ *   illumination. Per pixel p, binary32, every operation rounded on its own (the kernel preview_split):
+ *     A'[c] = fmaxf(albedo(p)[c], 0.0078125f)            (RT_DENOISE_DEMODULATE's floor)
+ *     I[c]  = beauty(p)[c] / A'[c]                       (IEEE division)
+ *     LA    = (0.2126f * A'.r + 0.7152f * A'.g) + 0.0722f * A'.b
+ *     V'    = variance(p) / (LA * LA)
+ *   LA is exact for grey albedos and an approximation otherwise (the variance is that of the mean
+ *   luminance and only scales the colour term). The stages run over I and V'; the last step
+ *   multiplies back: out(p)[c] = F(p)[c] * A'[c] with F the filter's output.
+ * RT_PREVIEW_FEEDBACK    as SVGF does, the first filter level's output C_1, V_1 is what the next frame
+ *   reprojects (its prev_color, prev_variance), not the temporal stage's own output; levels 1..L-1
+ *   continue from C_1, V_1. With levels == 1 the fed-back image is the frame's output.
+ * RT_PREVIEW_NO_TEMPORAL the temporal stage is skipped: every frame is filtered on its own.
+ *
+ * One frame, all on `stream`, in this order:
+ *   1 render   rt_render_var_device and rt_render_aov_device with rt_params {width, height, spp,
+ *              max_depth, seed, every row, flags 0}, aov samples = 0, all five planes
+ *   2 split    under DEMODULATE only (otherwise I = beauty, V' = variance: the same planes)
+ *   3 temporal rt_temporal_device's launch over I, V', the frame's guides and the session's prev_
+ *              planes and previous camera; no prev_ planes on the first frame and after
+ *              rt_preview_reset; skipped under NO_TEMPORAL
+ *   4 filter   rt_denoise_var_device's levels over the temporal outputs, guided by albedo, normal and
+ *              depth. The next frame's prev_color and prev_variance are C_1, V_1 under FEEDBACK and
+ *              the temporal outputs otherwise; its prev_history is out_history; its prev_ guides are
+ *              this frame's guides; its previous camera is `camera`
+ *   5 merge    one pass (the kernel preview_merge): out as above under DEMODULATE, the filter's bits
+ *              otherwise, stored to d_rgb if given; the texel rt_epilogue_rgb8_device computes from
+ *              those f32 bits stored to d_rgb8 if given
+ *
+ * rt_preview_create checks `p` field by field before it looks at `scene` and before any HIP call;
+ * RT_ERR_INVALID names the field: a wrong size, width or height outside 1..65536, spp < 2, max_depth
+ * 0, unknown flags, FEEDBACK with NO_TEMPORAL, a var_floor that is not positive and finite, then
+ * every check rt_temporal makes on its params (named temporal.alpha_min ...; temporal.width and
+ * .height must be the session's) and every check rt_denoise_var makes on its (denoise.levels ...;
+ * denoise.flags may hold RT_DENOISE_DIRECT only: the session's flag is the way to demodulate); then
+ * a null scene. What the two render calls refuse (a scene that does not fit LDS ...) comes back from
+ * the frame call as they report it; a failing frame call leaves the session's history as it was.
+ * A session uses its scene: destroy it before the scene. One host thread per session; sessions on
+ * one scene are independent.                                                                      */
+enum rt_preview_flags {
+    RT_PREVIEW_DEMODULATE = 1u << 0,
+    RT_PREVIEW_FEEDBACK = 1u << 1,
+    RT_PREVIEW_NO_TEMPORAL = 1u << 2
+};
+typedef struct rt_preview_params {
+    uint32_t size;                /* sizeof(rt_preview_params): the record's revision              */
+    uint32_t width, height;
+    uint32_t spp, max_depth;      /* of every frame's render; spp >= 2                             */
+    uint32_t flags;               /* rt_preview_flags                                              */
+    float var_floor;              /* rt_denoise_var_buffers.var_floor                              */
+    rt_temporal_params temporal;  /* width / height must equal the session's                       */
+    rt_denoise_params denoise;    /* likewise; flags: 0 or RT_DENOISE_DIRECT                       */
+} rt_preview_params;
+/* What the last enqueued frame wrote (device pointers, valid until the next frame call; all NULL
+ * before the first one): the temporal stage's outputs, the frame's guides, and the planes the next
+ * frame will take as prev_. Under NO_TEMPORAL out_color and out_variance are I and V', out_history
+ * and the prev_ planes are NULL. After rt_preview_reset the next frame ignores the prev_ planes. */
+typedef struct rt_preview_planes_t {
+    uint32_t size;                /* sizeof(rt_preview_planes_t), filled by the call               */
+    uint32_t frames;              /* frames enqueued since creation or the last reset              */
+    const float *out_color, *out_variance, *out_history;
+    const float *albedo, *normal, *depth, *alpha;
+    const uint32_t *sphere_id;
+    const float *prev_color, *prev_variance, *prev_history, *prev_normal, *prev_depth;
+    const uint32_t *prev_sphere_id;
+} rt_preview_planes_t;
+typedef struct rt_preview rt_preview;
+/* The defaults: the sub-records from rt_temporal_params_default and rt_denoise_var_params_default,
+ * max_depth 64, the flags scripts/preview_sweep.py chose (RT_PREVIEW_DEMODULATE).
+ * A zero width or height or spp < 2 is RT_ERR_INVALID.                                           */
+int rt_preview_params_default(uint32_t width, uint32_t height, uint32_t spp, rt_preview_params *out);
+/* Allocates every plane of the session on the scene's device (one allocation).                  */
+int rt_preview_create(rt_scene *scene, const rt_preview_params *p, rt_preview **out);
+/* Enqueue one frame. d_rgb: [height][width][3] floats (linear) or NULL; d_rgb8: [height][width][3]
+ * bytes (gamma 1/2.2) or NULL; one of them must be given. A NULL camera is RT_ERR_INVALID.        */
+int rt_preview_frame_device(rt_preview *pv, const rt_camera *camera, uint64_t seed, float *d_rgb, uint8_t *d_rgb8,
+                            void *stream);
+/* The next frame has no history (as the first one). Nothing is enqueued.                          */
+int rt_preview_reset(rt_preview *pv);
+int rt_preview_planes(rt_preview *pv, rt_preview_planes_t *out);
+/* The bytes of the session's device allocation (the scene's own workspaces: rt_scene_usage_get). */
+int rt_preview_usage(const rt_preview *pv, uint64_t *bytes);
+void rt_preview_destroy(rt_preview *pv);
+/* The session's two kernels on planes of the caller's (device pointers, one launch on `stream`, no
+ * host synchronisation): step 2 above, and step 5 (albedo NULL: out = the bits of `filtered`; one of
+ * d_rgb, d_rgb8 must be given). RT_ERR_INVALID names a null plane or a side outside 1..65536.    */
+int rt_preview_split_device(uint32_t width, uint32_t height, const float *beauty, const float *variance,
+                            const float *albedo, float *illumination, float *variance_out, void *stream);
+int rt_preview_merge_device(uint32_t width, uint32_t height, const float *filtered, const float *albedo, float *d_rgb,
+                            uint8_t *d_rgb8, void *stream);
+
 /* Device memory a scene holds and how its renders are cut (after the last render call).  */
 typedef struct rt_scene_usage {
     uint64_t device_bytes;     /* every device allocation of the scene                       */

@@ -30,6 +30,10 @@ RT_FLAG_WAVEFRONT = 1 << 5  # A/B: per-segment launches with HBM ray queues (sam
 RT_DENOISE_DEMODULATE = 1 << 0  # filter beauty / albedo', multiply back at the end
 RT_DENOISE_DIRECT = 1 << 1  # A/B: every level by the direct-load kernel (same bits)
 
+RT_PREVIEW_DEMODULATE = 1 << 0  # the temporal stage and the filter work on beauty / albedo'
+RT_PREVIEW_FEEDBACK = 1 << 1  # the first filter level's output is what the next frame reprojects
+RT_PREVIEW_NO_TEMPORAL = 1 << 2  # every frame filtered on its own
+
 
 class RtSphere(C.Structure):
     _fields_ = [("center", C.c_float * 3), ("radius", C.c_float), ("material", C.c_uint32)]
@@ -156,6 +160,31 @@ class RtTemporalBuffers(C.Structure):
     _fields_ = [("size", C.c_uint32)] + [(n, C.c_void_p) for n in TEMPORAL_PLANES]
 
 
+class RtPreviewParams(C.Structure):
+    """rt_preview_params (include/rt_api.h): a preview session's frame size, render, switches and the
+    records of its temporal stage and its filter."""
+    _fields_ = [
+        ("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("spp", C.c_uint32),
+        ("max_depth", C.c_uint32), ("flags", C.c_uint32), ("var_floor", C.c_float),
+        ("temporal", RtTemporalParams), ("denoise", RtDenoiseParams),
+    ]
+
+
+# the planes of rt_preview_planes_t, in the record's order: name -> (channels, numpy dtype)
+PREVIEW_PLANES = {
+    "out_color": (3, np.float32), "out_variance": (1, np.float32), "out_history": (1, np.float32),
+    "albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "alpha": (1, np.float32),
+    "sphere_id": (1, np.uint32),
+    "prev_color": (3, np.float32), "prev_variance": (1, np.float32), "prev_history": (1, np.float32),
+    "prev_normal": (3, np.float32), "prev_depth": (1, np.float32), "prev_sphere_id": (1, np.uint32),
+}
+
+
+class RtPreviewPlanes(C.Structure):
+    """rt_preview_planes_t (include/rt_api.h): the device planes a session's last frame wrote."""
+    _fields_ = [("size", C.c_uint32), ("frames", C.c_uint32)] + [(n, C.c_void_p) for n in PREVIEW_PLANES]
+
+
 # the planes of rt_denoise_buffers: name -> channels
 DENOISE_PLANES = {"beauty": 3, "albedo": 3, "normal": 3, "depth": 1, "out": 3, "scratch": 3}
 
@@ -176,6 +205,7 @@ assert C.sizeof(RtAovBuffers) == 48
 assert C.sizeof(RtDenoiseParams) == 36 and C.sizeof(RtDenoiseBuffers) == 56
 assert C.sizeof(RtDenoiseVarBuffers) == 32
 assert C.sizeof(RtTemporalParams) == 32 and C.sizeof(RtTemporalBuffers) == 128
+assert C.sizeof(RtPreviewParams) == 96 and C.sizeof(RtPreviewPlanes) == 120
 
 
 def ptr(arr, ctype=C.c_void_p):

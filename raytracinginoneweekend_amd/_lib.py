@@ -97,6 +97,18 @@ def _declare(L):
                                          P(abi.RtTemporalBuffers), C.c_void_p]),
         "rt_temporal": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera), P(abi.RtTemporalBuffers),
                                   P(abi.RtStats)]),
+        "rt_preview_params_default": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, P(abi.RtPreviewParams)]),
+        "rt_preview_create": (C.c_int, [C.c_void_p, P(abi.RtPreviewParams), P(C.c_void_p)]),
+        "rt_preview_frame_device": (C.c_int, [C.c_void_p, P(abi.RtCamera), C.c_uint64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+        "rt_preview_reset": (C.c_int, [C.c_void_p]),
+        "rt_preview_planes": (C.c_int, [C.c_void_p, P(abi.RtPreviewPlanes)]),
+        "rt_preview_usage": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
+        "rt_preview_destroy": (None, [C.c_void_p]),
+        "rt_preview_split_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+        "rt_preview_merge_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
         "rt_scene_kernel_times": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float), P(C.c_uint32)]),
         "rt_scene_debug_counters": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_int]),
         "rt_scene_debug_timeline": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_uint32, P(C.c_uint32)]),

@@ -288,6 +288,22 @@ struct KTemporal {
     float alpha_min, max_history, normal_tol, depth_tol;
 };
 
+// The preview session's own kernels (rt_preview.hip; rt_preview_frame_device).
+// preview_split: illum = beauty / A', var_out = variance / LA^2 with A' the floored albedo.
+struct KPreviewSplit {
+    const float *beauty, *variance, *albedo;
+    float *illum, *var_out;
+    uint32_t W, H;
+};
+// preview_merge: the filter's output (times A' when albedo is given) as f32 and / or rgb8, the
+// outputs that are given.
+struct KPreviewMerge {
+    const float *filtered, *albedo;
+    float *out;
+    uint8_t *out_u8;
+    uint32_t W, H;
+};
+
 // The wavefront variant's ray queue (structure of arrays, capacity cap rays): f = [9][cap]
 // floats {o.xyz, d.xyz, attenuation.xyz}, then the data-stream state, the item index (slot) and
 // the segment count of each ray; count = rays in the queue.

@@ -1662,6 +1662,9 @@ int rt_epilogue_rgb8_device(const float *d_rgb, uint8_t *d_out, uint64_t n_pixel
 
 } // extern "C"
 
+// the preview session (rt_host_post.cpp) allocates its planes where its scene lives
+int rthost::scene_device(const rt_scene *sc) { return sc->device; }
+
 namespace {
 
 // The synchronous calls' per-device context, kept between calls: the reference's entry point

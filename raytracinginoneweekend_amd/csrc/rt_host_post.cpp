@@ -1,13 +1,15 @@
 // rt_host_post.cpp — the post-process stages of the C-ABI (include/rt_api.h), which use nothing of
 // a device scene: the à-trous denoiser, its variance-guided form and temporal accumulation, each
 // with its argument checks, defaults, level driver, stream-ordered *_device entry point and the
-// synchronous host-plane call through the cached context (rt_host_sync.h SyncCall). The kernels
-// are rt_denoise.hip and rt_temporal.hip.
+// synchronous host-plane call through the cached context (rt_host_sync.h SyncCall); and the preview
+// session, which runs those stages after a scene's two render calls, one frame per call. The
+// kernels are rt_denoise.hip, rt_temporal.hip and rt_preview.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 
 #include "../../include/rt_api.h"
 #include "rt_device.h"
@@ -32,6 +34,32 @@ constexpr uint32_t kDnVarLevels = 2;
 constexpr float kDnVarSigmaColor = 32.0f, kDnVarSigmaNormal = 1.0f, kDnVarSigmaDepth = 4.0f, kDnVarSigmaAlbedo = 1.0f;
 constexpr float kDnVarFloor = 1e-6f;
 
+// The checks of a filter's params that read nothing but the record's own values, in two parts (the
+// checks of the planes come between them). w: the message up to the field's name ("rt_denoise: ",
+// or "rt_preview_create: denoise." for the session's sub-record).
+struct Sigma { const char *name; float v; };
+int check_denoise_ranges(const rt_denoise_params &p, const std::string &w)
+{
+    if (!p.width || p.width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
+    if (!p.height || p.height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    if (p.levels < 1u || p.levels > 6u) return fail(RT_ERR_INVALID, w + "levels must be 1..6");
+    for (const Sigma &s : {Sigma{"sigma_color", p.sigma_color}, Sigma{"sigma_normal", p.sigma_normal},
+                           Sigma{"sigma_depth", p.sigma_depth}, Sigma{"sigma_albedo", p.sigma_albedo}})
+        if (!std::isfinite(s.v) || s.v < 0.f) return fail(RT_ERR_INVALID, w + s.name + " must be finite and not negative");
+    return RT_OK;
+}
+int check_denoise_small(const rt_denoise_params &p, const std::string &w)
+{
+    if (p.sigma_color != 0.f) {
+        const float s = p.sigma_color * std::ldexp(1.f, -static_cast<int>(p.levels - 1u));
+        if (!std::isfinite(1.0f / (s * s))) return fail(RT_ERR_INVALID, w + "sigma_color is too small for this many levels");
+    }
+    for (const Sigma &s : {Sigma{"sigma_normal", p.sigma_normal}, Sigma{"sigma_depth", p.sigma_depth},
+                           Sigma{"sigma_albedo", p.sigma_albedo}})
+        if (s.v != 0.f && !std::isfinite(1.0f / (s.v * s.v))) return fail(RT_ERR_INVALID, w + s.name + " is too small");
+    return RT_OK;
+}
+
 // Every argument check of the denoiser, before any HIP call (use_scratch: the call uses
 // buffers.scratch). terms: the edge terms that are on.
 int check_denoise(const rt_denoise_params *p, const rt_denoise_buffers *b, bool use_scratch, const char *who,
@@ -41,13 +69,7 @@ int check_denoise(const rt_denoise_params *p, const rt_denoise_buffers *b, bool 
     if (!p || !b) return fail(RT_ERR_INVALID, w + "null argument");
     if (p->size != sizeof(rt_denoise_params)) return fail(RT_ERR_INVALID, w + "params.size is not sizeof(rt_denoise_params)");
     if (b->size != sizeof(rt_denoise_buffers)) return fail(RT_ERR_INVALID, w + "buffers.size is not sizeof(rt_denoise_buffers)");
-    if (!p->width || p->width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
-    if (!p->height || p->height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
-    if (p->levels < 1u || p->levels > 6u) return fail(RT_ERR_INVALID, w + "levels must be 1..6");
-    const struct { const char *name; float v; } sig[4] = {{"sigma_color", p->sigma_color}, {"sigma_normal", p->sigma_normal},
-                                                          {"sigma_depth", p->sigma_depth}, {"sigma_albedo", p->sigma_albedo}};
-    for (const auto &s : sig)
-        if (!std::isfinite(s.v) || s.v < 0.f) return fail(RT_ERR_INVALID, w + s.name + " must be finite and not negative");
+    if (int rc = check_denoise_ranges(*p, w); rc != RT_OK) return rc;
     if (p->flags & ~static_cast<uint32_t>(RT_DENOISE_DEMODULATE | RT_DENOISE_DIRECT))
         return fail(RT_ERR_INVALID, w + "unknown bits in flags");
     if (!b->beauty) return fail(RT_ERR_INVALID, w + "beauty is null");
@@ -56,12 +78,7 @@ int check_denoise(const rt_denoise_params *p, const rt_denoise_buffers *b, bool 
     if (b->depth && p->sigma_depth == 0.f) return fail(RT_ERR_INVALID, w + "sigma_depth is 0 with a depth plane");
     if ((p->flags & RT_DENOISE_DEMODULATE) && !b->albedo)
         return fail(RT_ERR_INVALID, w + "RT_DENOISE_DEMODULATE needs the albedo plane");
-    if (p->sigma_color != 0.f) {
-        const float s = p->sigma_color * std::ldexp(1.f, -static_cast<int>(p->levels - 1u));
-        if (!std::isfinite(1.0f / (s * s))) return fail(RT_ERR_INVALID, w + "sigma_color is too small for this many levels");
-    }
-    for (const auto &s : {sig[1], sig[2], sig[3]})
-        if (s.v != 0.f && !std::isfinite(1.0f / (s.v * s.v))) return fail(RT_ERR_INVALID, w + s.name + " is too small");
+    if (int rc = check_denoise_small(*p, w); rc != RT_OK) return rc;
     const bool need_scratch = use_scratch && p->levels > 1u;
     if (need_scratch && !b->scratch) return fail(RT_ERR_INVALID, w + "scratch is null with levels > 1");
     const float *const scratch = use_scratch ? b->scratch : nullptr;
@@ -182,9 +199,11 @@ int check_denoise_var(const rt_denoise_params *p, const rt_denoise_buffers *b, c
 }
 
 // Enqueue every level: the colours go where denoise_levels' do, the variances alternate between
-// the halves of v.var_scratch; the last level's goes to v.variance_out, if given.
+// the halves of v.var_scratch; the last level's goes to v.variance_out, if given. c1, v1 (the
+// preview session's feedback; both or neither): level 0 writes C_1 and V_1 there instead, and
+// level 1 reads them there.
 int denoise_var_levels(const rt_denoise_params &p, const rt_denoise_buffers &b, const rt_denoise_var_buffers &v,
-                       uint32_t terms, hipStream_t stream)
+                       uint32_t terms, hipStream_t stream, float *c1 = nullptr, float *v1 = nullptr)
 {
     rt::KDenoiseVar kv{};
     rt::KDenoise &k = kv.d;
@@ -200,6 +219,7 @@ int denoise_var_levels(const rt_denoise_params &p, const rt_denoise_buffers &b, 
         k.step = 1u << l;
         kv.vin = vin;
         kv.vout = l == last ? v.variance_out : v.var_scratch + (l & 1u) * n;
+        if (l == 0u && c1) k.out = c1, kv.vout = v1;
         RT_HIP(rt::launch_denoise_var(kv, terms, stream));
         in = k.out;
         vin = kv.vout;
@@ -233,6 +253,21 @@ int denoise_var_host(const rt_denoise_params *params, const rt_denoise_buffers *
 // rt_temporal_params_default: the values scripts/temporal_sweep.py chose
 constexpr float kTpAlphaMin = 0.4f, kTpMaxHistory = 32.0f, kTpNormalTol = 0.5f, kTpDepthTol = 0.1f;
 
+// The checks of the params' own values (w: the message up to the field's name, as
+// check_denoise_ranges takes it).
+int check_temporal_ranges(const rt_temporal_params &p, const std::string &w)
+{
+    if (!p.width || p.width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
+    if (!p.height || p.height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    if (!std::isfinite(p.alpha_min) || !(p.alpha_min > 0.f) || p.alpha_min > 1.f)
+        return fail(RT_ERR_INVALID, w + "alpha_min must be above 0 and at most 1");
+    if (!std::isfinite(p.max_history) || p.max_history < 1.f) return fail(RT_ERR_INVALID, w + "max_history must be finite and at least 1");
+    if (!std::isfinite(p.normal_tol) || p.normal_tol < 0.f) return fail(RT_ERR_INVALID, w + "normal_tol must be finite and not negative");
+    if (!std::isfinite(p.depth_tol) || p.depth_tol < 0.f) return fail(RT_ERR_INVALID, w + "depth_tol must be finite and not negative");
+    if (p.flags) return fail(RT_ERR_INVALID, w + "flags must be 0 (none is defined)");
+    return RT_OK;
+}
+
 // Every argument check, before any HIP call; fills the kernel's record (the cameras as the
 // contract's {a, hor, ver, o} and {A, B, G, o'}) from the caller's pointers.
 int check_temporal(const rt_temporal_params *p, const rt_camera *cam, const rt_camera *prev_cam,
@@ -242,14 +277,7 @@ int check_temporal(const rt_temporal_params *p, const rt_camera *cam, const rt_c
     if (!p || !b) return fail(RT_ERR_INVALID, w + "null argument");
     if (p->size != sizeof(rt_temporal_params)) return fail(RT_ERR_INVALID, w + "params.size is not sizeof(rt_temporal_params)");
     if (b->size != sizeof(rt_temporal_buffers)) return fail(RT_ERR_INVALID, w + "buffers.size is not sizeof(rt_temporal_buffers)");
-    if (!p->width || p->width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
-    if (!p->height || p->height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
-    if (!std::isfinite(p->alpha_min) || !(p->alpha_min > 0.f) || p->alpha_min > 1.f)
-        return fail(RT_ERR_INVALID, w + "alpha_min must be above 0 and at most 1");
-    if (!std::isfinite(p->max_history) || p->max_history < 1.f) return fail(RT_ERR_INVALID, w + "max_history must be finite and at least 1");
-    if (!std::isfinite(p->normal_tol) || p->normal_tol < 0.f) return fail(RT_ERR_INVALID, w + "normal_tol must be finite and not negative");
-    if (!std::isfinite(p->depth_tol) || p->depth_tol < 0.f) return fail(RT_ERR_INVALID, w + "depth_tol must be finite and not negative");
-    if (p->flags) return fail(RT_ERR_INVALID, w + "flags must be 0 (none is defined)");
+    if (int rc = check_temporal_ranges(*p, w); rc != RT_OK) return rc;
     if (!cam) return fail(RT_ERR_INVALID, w + "camera is null");
     if (cam->mode > RT_CAMERA_CORRECTED) return fail(RT_ERR_INVALID, w + "camera has a bad mode");
     const struct { const char *name; const void *ptr; } cur[6] = {{"beauty", b->beauty}, {"variance", b->variance}, {"normal", b->normal},
@@ -323,7 +351,278 @@ int temporal_host(const rt_temporal_params *params, const rt_camera *camera, con
 
 } // namespace
 
+// ---- the preview session (include/rt_api.h; kernels in rt_preview.hip) ---------
+// Every plane is a piece of one device allocation, made by rt_preview_create; a plane that the
+// session's flags and levels never touch is not there (its pointer stays null).
+struct rt_preview {
+    rt_scene *scene = nullptr;
+    int device = 0;
+    rt_preview_params p{};
+    uint32_t terms = 0;            // the filter's edge terms (check_denoise)
+    void *arena = nullptr;
+    uint64_t bytes = 0;
+    // the frame's render, its guides that no later frame reads, and what DEMODULATE makes of it
+    float *beauty = nullptr, *variance = nullptr, *albedo = nullptr, *alpha = nullptr;
+    float *illum = nullptr, *illum_var = nullptr;
+    // the guides the temporal stage compares, and what it reprojects: set `cur` is written by the
+    // next frame, the other one is its prev_ (one set under NO_TEMPORAL, no history at all)
+    struct Guides { float *normal = nullptr, *depth = nullptr; uint32_t *id = nullptr; } g[2];
+    struct History { float *color = nullptr, *variance = nullptr, *history = nullptr; } h[2];
+    // FEEDBACK: the temporal stage's outputs (h[cur] takes the first filter level's)
+    float *acc_color = nullptr, *acc_variance = nullptr;
+    // the filter's output and the levels' intermediate planes
+    float *filtered = nullptr, *scratch = nullptr, *var_scratch = nullptr;
+    uint32_t cur = 0;
+    rt_camera prev_camera{};
+    rt_preview_planes_t last{};    // last.frames: frames since creation or the last reset
+};
+
+namespace {
+
+constexpr uint32_t kPreviewFlags = RT_PREVIEW_DEMODULATE | RT_PREVIEW_FEEDBACK | RT_PREVIEW_NO_TEMPORAL;
+// rt_preview_params_default: max_depth as the reference's bounces_number; the flags
+// scripts/preview_sweep.py chose
+constexpr uint32_t kPvMaxDepth = 64;
+constexpr uint32_t kPvFlags = RT_PREVIEW_DEMODULATE;
+
+// Every check of a session's params, before its scene is looked at and before any HIP call. terms:
+// the filter's edge terms (the session gives every guide).
+int check_preview(const rt_preview_params *p, uint32_t *terms)
+{
+    const std::string w = "rt_preview_create: ";
+    if (!p) return fail(RT_ERR_INVALID, w + "null params");
+    if (p->size != sizeof(rt_preview_params)) return fail(RT_ERR_INVALID, w + "size is not sizeof(rt_preview_params)");
+    if (!p->width || p->width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
+    if (!p->height || p->height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    if (static_cast<uint64_t>(p->width) * p->height >= (1ull << 31))
+        return fail(RT_ERR_INVALID, w + "width * height must be below 2^31 (one render call)");
+    if (p->spp < 2u) return fail(RT_ERR_INVALID, w + "spp must be at least 2 (a variance needs two samples)");
+    if (!p->max_depth) return fail(RT_ERR_INVALID, w + "max_depth must be at least 1");
+    if (p->flags & ~kPreviewFlags) return fail(RT_ERR_INVALID, w + "unknown bits in flags");
+    if ((p->flags & RT_PREVIEW_FEEDBACK) && (p->flags & RT_PREVIEW_NO_TEMPORAL))
+        return fail(RT_ERR_INVALID, w + "flags: RT_PREVIEW_FEEDBACK needs the temporal stage (RT_PREVIEW_NO_TEMPORAL is set)");
+    if (!std::isfinite(p->var_floor) || !(p->var_floor > 0.f)) return fail(RT_ERR_INVALID, w + "var_floor must be finite and positive");
+    const rt_temporal_params &t = p->temporal;
+    if (t.size != sizeof(rt_temporal_params)) return fail(RT_ERR_INVALID, w + "temporal.size is not sizeof(rt_temporal_params)");
+    if (t.width != p->width) return fail(RT_ERR_INVALID, w + "temporal.width is not the session's width");
+    if (t.height != p->height) return fail(RT_ERR_INVALID, w + "temporal.height is not the session's height");
+    if (int rc = check_temporal_ranges(t, w + "temporal."); rc != RT_OK) return rc;
+    const rt_denoise_params &d = p->denoise;
+    if (d.size != sizeof(rt_denoise_params)) return fail(RT_ERR_INVALID, w + "denoise.size is not sizeof(rt_denoise_params)");
+    if (d.width != p->width) return fail(RT_ERR_INVALID, w + "denoise.width is not the session's width");
+    if (d.height != p->height) return fail(RT_ERR_INVALID, w + "denoise.height is not the session's height");
+    if (int rc = check_denoise_ranges(d, w + "denoise."); rc != RT_OK) return rc;
+    if (d.flags & RT_DENOISE_DEMODULATE)
+        return fail(RT_ERR_INVALID, w + "denoise.flags holds RT_DENOISE_DEMODULATE (the session demodulates with RT_PREVIEW_DEMODULATE)");
+    if (d.flags & ~static_cast<uint32_t>(RT_DENOISE_DIRECT)) return fail(RT_ERR_INVALID, w + "unknown bits in denoise.flags");
+    if (d.sigma_normal == 0.f) return fail(RT_ERR_INVALID, w + "denoise.sigma_normal is 0 with a normal plane");
+    if (d.sigma_depth == 0.f) return fail(RT_ERR_INVALID, w + "denoise.sigma_depth is 0 with a depth plane");
+    if (int rc = check_denoise_small(d, w + "denoise."); rc != RT_OK) return rc;
+    *terms = (d.sigma_color != 0.f ? 1u : 0u) | 2u | 4u | (d.sigma_albedo != 0.f ? 8u : 0u);
+    return RT_OK;
+}
+
+// The session's planes, each a multiple of 256 bytes from the arena's start: the first pass
+// (base null) sizes the arena, the second hands the addresses out.
+size_t preview_carve(rt_preview &pv, char *base)
+{
+    const rt_preview_params &p = pv.p;
+    const size_t n = static_cast<size_t>(p.width) * p.height;
+    const bool temporal = !(p.flags & RT_PREVIEW_NO_TEMPORAL), feedback = (p.flags & RT_PREVIEW_FEEDBACK) != 0u;
+    const bool demod = (p.flags & RT_PREVIEW_DEMODULATE) != 0u;
+    // the levels between the first (whose output the feedback keeps) and the last use the scratch planes
+    const bool between = p.denoise.levels > (feedback ? 2u : 1u);
+    size_t at = 0;
+    auto take = [&](auto *&plane, size_t words, bool wanted = true) {
+        if (!wanted) return;
+        if (base) plane = reinterpret_cast<std::remove_reference_t<decltype(plane)>>(base + at);
+        at += (words * n * sizeof(float) + 255u) / 256u * 256u;
+    };
+    take(pv.beauty, 3), take(pv.variance, 1), take(pv.albedo, 3), take(pv.alpha, 1);
+    take(pv.illum, 3, demod), take(pv.illum_var, 1, demod);
+    for (int s = 0; s < (temporal ? 2 : 1); ++s) take(pv.g[s].normal, 3), take(pv.g[s].depth, 1), take(pv.g[s].id, 1);
+    for (int s = 0; s < 2; ++s)
+        take(pv.h[s].color, 3, temporal), take(pv.h[s].variance, 1, temporal), take(pv.h[s].history, 1, temporal);
+    take(pv.acc_color, 3, feedback), take(pv.acc_variance, 1, feedback);
+    take(pv.filtered, 3), take(pv.scratch, 3, between), take(pv.var_scratch, 2, between);
+    return at;
+}
+
+// One frame of the loop, enqueued on `st`. The session's history moves on only when every stage
+// was enqueued.
+int preview_frame(rt_preview &pv, const rt_camera *camera, uint64_t seed, float *d_rgb, uint8_t *d_rgb8, hipStream_t st)
+{
+    const char *const who = "rt_preview_frame_device";
+    const rt_preview_params &P = pv.p;
+    const bool temporal = !(P.flags & RT_PREVIEW_NO_TEMPORAL), feedback = (P.flags & RT_PREVIEW_FEEDBACK) != 0u;
+    const bool demod = (P.flags & RT_PREVIEW_DEMODULATE) != 0u;
+    const uint32_t c = pv.cur, o = c ^ 1u;
+    const rt_preview::Guides &g = pv.g[c];
+    // 1 render
+    const rt_params rp{P.width, P.height, P.spp, P.max_depth, seed, 0u, 1u, 0u, 0u};
+    if (int rc = rt_render_var_device(pv.scene, camera, &rp, pv.beauty, pv.variance, st, nullptr); rc != RT_OK) return rc;
+    const rt_aov_buffers aov{static_cast<uint32_t>(sizeof(rt_aov_buffers)), 0u, pv.albedo, g.normal, g.depth, pv.alpha, g.id};
+    if (int rc = rt_render_aov_device(pv.scene, camera, &rp, &aov, st); rc != RT_OK) return rc;
+    // 2 split
+    const float *color = pv.beauty, *variance = pv.variance;
+    if (demod) {
+        RT_HIP(rt::launch_preview_split({pv.beauty, pv.variance, pv.albedo, pv.illum, pv.illum_var, P.width, P.height}, st));
+        color = pv.illum, variance = pv.illum_var;
+    }
+    // 3 temporal
+    if (temporal) {
+        const bool prev = pv.last.frames != 0u;
+        const rt_preview::History &hp = pv.h[o];
+        const rt_preview::Guides &gp = pv.g[o];
+        float *const out_c = feedback ? pv.acc_color : pv.h[c].color, *const out_v = feedback ? pv.acc_variance : pv.h[c].variance;
+        const rt_temporal_buffers tb{static_cast<uint32_t>(sizeof(rt_temporal_buffers)),
+                                     color, variance, g.normal, g.depth, pv.alpha, g.id,
+                                     prev ? hp.color : nullptr, prev ? hp.variance : nullptr, prev ? hp.history : nullptr,
+                                     prev ? gp.normal : nullptr, prev ? gp.depth : nullptr, prev ? gp.id : nullptr,
+                                     out_c, out_v, pv.h[c].history};
+        rt::KTemporal k{};
+        if (int rc = check_temporal(&P.temporal, camera, prev ? &pv.prev_camera : nullptr, &tb, who, &k); rc != RT_OK) return rc;
+        RT_HIP(rt::launch_temporal(k, st));
+        color = out_c, variance = out_v;
+    }
+    // 4 filter
+    const rt_denoise_buffers db{static_cast<uint32_t>(sizeof(rt_denoise_buffers)), color, pv.albedo, g.normal, g.depth,
+                                pv.filtered, pv.scratch};
+    const rt_denoise_var_buffers vb{static_cast<uint32_t>(sizeof(rt_denoise_var_buffers)), P.var_floor, variance, nullptr,
+                                    pv.var_scratch};
+    float *const c1 = feedback ? pv.h[c].color : nullptr, *const v1 = feedback ? pv.h[c].variance : nullptr;
+    if (int rc = denoise_var_levels(P.denoise, db, vb, pv.terms, st, c1, v1); rc != RT_OK) return rc;
+    // 5 merge
+    const float *const filtered = feedback && P.denoise.levels == 1u ? c1 : pv.filtered;
+    RT_HIP(rt::launch_preview_merge({filtered, demod ? pv.albedo : nullptr, d_rgb, d_rgb8, P.width, P.height}, st));
+    // what the frame wrote, and what the next one reprojects
+    rt_preview_planes_t &l = pv.last;
+    l.frames += 1u;
+    l.out_color = color, l.out_variance = variance, l.out_history = temporal ? pv.h[c].history : nullptr;
+    l.albedo = pv.albedo, l.normal = g.normal, l.depth = g.depth, l.alpha = pv.alpha, l.sphere_id = g.id;
+    if (temporal) {
+        l.prev_color = pv.h[c].color, l.prev_variance = pv.h[c].variance, l.prev_history = pv.h[c].history;
+        l.prev_normal = g.normal, l.prev_depth = g.depth, l.prev_sphere_id = g.id;
+        pv.cur = o;
+        pv.prev_camera = *camera;
+    }
+    return RT_OK;
+}
+
+int check_preview_side(uint32_t width, uint32_t height, const std::string &w)
+{
+    if (!width || width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
+    if (!height || height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    return RT_OK;
+}
+
+} // namespace
+
 extern "C" {
+
+int rt_preview_params_default(uint32_t width, uint32_t height, uint32_t spp, rt_preview_params *out)
+{
+    if (!out) return fail(RT_ERR_INVALID, "rt_preview_params_default: null argument");
+    if (!width || !height) return fail(RT_ERR_INVALID, "rt_preview_params_default: zero width or height");
+    if (spp < 2u) return fail(RT_ERR_INVALID, "rt_preview_params_default: spp must be at least 2 (a variance needs two samples)");
+    rt_preview_params p{};
+    rt_denoise_var_buffers v{};
+    if (int rc = rt_temporal_params_default(width, height, &p.temporal); rc != RT_OK) return rc;
+    if (int rc = rt_denoise_var_params_default(width, height, &p.denoise, &v); rc != RT_OK) return rc;
+    p.size = static_cast<uint32_t>(sizeof(rt_preview_params));
+    p.width = width, p.height = height, p.spp = spp, p.max_depth = kPvMaxDepth;
+    p.flags = kPvFlags;
+    p.var_floor = v.var_floor;
+    *out = p;
+    return RT_OK;
+}
+
+int rt_preview_create(rt_scene *scene, const rt_preview_params *p, rt_preview **out)
+{
+    uint32_t terms = 0;
+    if (int rc = check_preview(p, &terms); rc != RT_OK) return rc;
+    if (!scene) return fail(RT_ERR_INVALID, "rt_preview_create: scene is null");
+    if (!out) return fail(RT_ERR_INVALID, "rt_preview_create: out is null");
+    rt_preview *pv = new rt_preview;
+    pv->scene = scene;
+    pv->device = scene_device(scene);
+    pv->p = *p;
+    pv->terms = terms;
+    pv->last.size = static_cast<uint32_t>(sizeof(rt_preview_planes_t));
+    pv->bytes = preview_carve(*pv, nullptr);
+    hipError_t e = hipSetDevice(pv->device);
+    if (e == hipSuccess) e = hipMalloc(&pv->arena, pv->bytes);
+    if (e != hipSuccess) {
+        delete pv;
+        return fail(RT_ERR_DEVICE, std::string("rt_preview_create: the session's planes: ") + hipGetErrorString(e));
+    }
+    preview_carve(*pv, static_cast<char *>(pv->arena));
+    *out = pv;
+    return RT_OK;
+}
+
+int rt_preview_frame_device(rt_preview *pv, const rt_camera *camera, uint64_t seed, float *d_rgb, uint8_t *d_rgb8,
+                            void *stream)
+{
+    if (!pv) return fail(RT_ERR_INVALID, "rt_preview_frame_device: null session");
+    if (!camera) return fail(RT_ERR_INVALID, "rt_preview_frame_device: camera is null");
+    if (!d_rgb && !d_rgb8) return fail(RT_ERR_INVALID, "rt_preview_frame_device: d_rgb and d_rgb8 are both null");
+    return preview_frame(*pv, camera, seed, d_rgb, d_rgb8, static_cast<hipStream_t>(stream));
+}
+
+int rt_preview_reset(rt_preview *pv)
+{
+    if (!pv) return fail(RT_ERR_INVALID, "rt_preview_reset: null session");
+    pv->last.frames = 0u;
+    return RT_OK;
+}
+
+int rt_preview_planes(rt_preview *pv, rt_preview_planes_t *out)
+{
+    if (!pv || !out) return fail(RT_ERR_INVALID, "rt_preview_planes: null argument");
+    *out = pv->last;
+    return RT_OK;
+}
+
+int rt_preview_usage(const rt_preview *pv, uint64_t *bytes)
+{
+    if (!pv || !bytes) return fail(RT_ERR_INVALID, "rt_preview_usage: null argument");
+    *bytes = pv->bytes;
+    return RT_OK;
+}
+
+void rt_preview_destroy(rt_preview *pv)
+{
+    if (!pv) return;
+    // (the frames enqueued may still run: hipFree waits for the device)
+    if (pv->arena && hipSetDevice(pv->device) == hipSuccess) (void)hipFree(pv->arena);
+    delete pv;
+}
+
+int rt_preview_split_device(uint32_t width, uint32_t height, const float *beauty, const float *variance,
+                            const float *albedo, float *illumination, float *variance_out, void *stream)
+{
+    const std::string w = "rt_preview_split_device: ";
+    if (int rc = check_preview_side(width, height, w); rc != RT_OK) return rc;
+    const struct { const char *name; const void *ptr; } planes[5] = {
+        {"beauty", beauty}, {"variance", variance}, {"albedo", albedo}, {"illumination", illumination}, {"variance_out", variance_out}};
+    for (const auto &pl : planes)
+        if (!pl.ptr) return fail(RT_ERR_INVALID, w + pl.name + " is null");
+    RT_HIP(rt::launch_preview_split({beauty, variance, albedo, illumination, variance_out, width, height},
+                                    static_cast<hipStream_t>(stream)));
+    return RT_OK;
+}
+
+int rt_preview_merge_device(uint32_t width, uint32_t height, const float *filtered, const float *albedo, float *d_rgb,
+                            uint8_t *d_rgb8, void *stream)
+{
+    const std::string w = "rt_preview_merge_device: ";
+    if (int rc = check_preview_side(width, height, w); rc != RT_OK) return rc;
+    if (!filtered) return fail(RT_ERR_INVALID, w + "filtered is null");
+    if (!d_rgb && !d_rgb8) return fail(RT_ERR_INVALID, w + "d_rgb and d_rgb8 are both null");
+    RT_HIP(rt::launch_preview_merge({filtered, albedo, d_rgb, d_rgb8, width, height}, static_cast<hipStream_t>(stream)));
+    return RT_OK;
+}
 
 int rt_temporal_params_default(uint32_t width, uint32_t height, rt_temporal_params *out)
 {

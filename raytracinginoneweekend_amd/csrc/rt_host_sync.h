@@ -38,6 +38,9 @@ hipError_t launch_denoise_var(const KDenoiseVar &k, uint32_t terms, hipStream_t 
 size_t denoise_tiled_lds(uint32_t terms, uint32_t step);
 // rt_temporal.hip
 hipError_t launch_temporal(const KTemporal &k, hipStream_t stream);
+// rt_preview.hip
+hipError_t launch_preview_split(const KPreviewSplit &k, hipStream_t stream);
+hipError_t launch_preview_merge(const KPreviewMerge &k, hipStream_t stream);
 } // namespace rt
 
 #define RT_HIP(call)                                                                      \
@@ -54,6 +57,9 @@ inline int hip_rc(hipError_t e, const char *what)
 {
     return e == hipSuccess ? RT_OK : fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
+
+// The device a scene was created on (rt_scene is rt_host.cpp's own record).
+int scene_device(const rt_scene *sc);
 
 // The scene of a synchronous render: the context keeps its device scene between calls.
 struct SyncScene {

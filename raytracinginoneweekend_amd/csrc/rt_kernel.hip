@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "rt_device.h"
+#include "rt_texel.h"
 
 namespace rt {
 
@@ -2211,8 +2212,7 @@ __global__ __launch_bounds__(256) void epilogue_rgb8_kernel(const float *in, uin
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double g = (double)(1.f / 2.2f);
-    out[i] = (uint8_t)(255.f * (float)pow((double)in[i], g));
+    out[i] = rgb8_texel(in[i]);
 }
 
 // ---- the wavefront variant (RT_FLAG_WAVEFRONT; SURVEY §8(f3), an A/B against the megakernel) ----

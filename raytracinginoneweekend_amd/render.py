@@ -7,6 +7,8 @@ render_aov / DeviceScene.render_aov   first-hit feature buffers for a denoiser o
                            (rt_render_aov / rt_render_aov_device)
 denoise / denoise_device   the edge-avoiding à-trous denoiser over those buffers (rt_denoise /
                            rt_denoise_device)
+Preview / DeviceScene.preview   the whole denoised-preview loop on the device, one call per frame
+                           (rt_preview_*)
 MultiContext               row tiles over ranks (devices), gathered to rank 0 (rt_multi_*)
 save_ppm                   app::save_to_file (src/main.cxx:87-101), rt_write_ppm
 """
@@ -380,6 +382,100 @@ def temporal(cur, prev, camera, prev_camera, params=None, stats=None, **fields):
     return out["out_color"], out["out_variance"], out["out_history"]
 
 
+def preview_params(width, height, spp, base=None, demodulate=None, feedback=None, temporal=None, denoise=None,
+                   **fields):
+    """An rt_preview_params record: the library defaults for the frame (or a copy
+    of `base`) with `fields` set (max_depth, flags, var_floor); demodulate / feedback / temporal set
+    or clear RT_PREVIEW_DEMODULATE / RT_PREVIEW_FEEDBACK / the temporal stage (temporal=False:
+    RT_PREVIEW_NO_TEMPORAL), or temporal is a dict of rt_temporal_params fields (temporal_params);
+    denoise: a dict of rt_denoise_params fields (denoise_var_params; direct among them)."""
+    p = abi.RtPreviewParams()
+    if base is None:
+        check(lib().rt_preview_params_default(width, height, spp, C.byref(p)))
+    else:
+        C.memmove(C.byref(p), C.byref(base), C.sizeof(p))
+        p.width = p.temporal.width = p.denoise.width = width
+        p.height = p.temporal.height = p.denoise.height = height
+        p.spp = spp
+    for k, v in fields.items():
+        if k not in ("max_depth", "flags", "var_floor"):
+            raise KeyError(f"rt_preview_params has no field {k!r} to set")
+        setattr(p, k, v)
+    if isinstance(temporal, dict):
+        p.temporal = temporal_params(width, height, base=p.temporal, **temporal)
+        temporal = True
+    if denoise is not None:
+        p.denoise = denoise_var_params(width, height, base=p.denoise, **denoise)[0]
+    for bit, on in ((abi.RT_PREVIEW_DEMODULATE, demodulate), (abi.RT_PREVIEW_FEEDBACK, feedback),
+                    (abi.RT_PREVIEW_NO_TEMPORAL, None if temporal is None else not temporal)):
+        if on is not None:
+            p.flags = (p.flags | bit) if on else (p.flags & ~bit)
+    return p
+
+
+class Preview:
+    """A preview session on a DeviceScene (rt_preview_create): the loop render ->
+    feature buffers -> temporal accumulation -> variance-guided filter -> epilogue with every plane
+    and the history kept on the device, one call per frame. Close it before its scene."""
+
+    def __init__(self, device_scene, params):
+        h = C.c_void_p()
+        check(lib().rt_preview_create(device_scene.handle if device_scene is not None else None, C.byref(params),
+                                      C.byref(h)))
+        self.handle = h
+        self.scene = device_scene  # (kept alive as long as the session)
+        self.width, self.height = params.width, params.height
+
+    def frame(self, camera, seed, rgb_ptr=None, rgb8_ptr=None, stream=None):
+        """Enqueue one frame on `stream`: the denoised linear image into device address rgb_ptr
+        (float32 (h, w, 3)) and / or its gamma-corrected texels into rgb8_ptr (uint8 (h, w, 3))."""
+        check(lib().rt_preview_frame_device(self.handle, C.byref(_cam_record(camera)) if camera is not None else None,
+                                            seed, C.c_void_p(rgb_ptr or 0), C.c_void_p(rgb8_ptr or 0),
+                                            C.c_void_p(stream or 0)))
+
+    def reset(self):
+        """The next frame has no history."""
+        check(lib().rt_preview_reset(self.handle))
+
+    def planes(self):
+        """rt_preview_planes: what the last enqueued frame wrote, as a dict plane name
+        (abi.PREVIEW_PLANES) -> device address (None: not there), and 'frames'."""
+        r = abi.RtPreviewPlanes()
+        check(lib().rt_preview_planes(self.handle, C.byref(r)))
+        return {"frames": r.frames, **{n: getattr(r, n) for n in abi.PREVIEW_PLANES}}
+
+    def usage(self):
+        """rt_preview_usage: the bytes of the session's device allocation."""
+        n = C.c_uint64(0)
+        check(lib().rt_preview_usage(self.handle, C.byref(n)))
+        return n.value
+
+    def close(self):
+        if self.handle:
+            lib().rt_preview_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def preview_split_device(width, height, beauty, variance, albedo, illumination, variance_out, stream=None):
+    """Enqueue rt_preview_split_device (device addresses): illumination = beauty / albedo',
+    variance_out = variance / luminance(albedo')^2."""
+    check(lib().rt_preview_split_device(width, height, C.c_void_p(beauty), C.c_void_p(variance), C.c_void_p(albedo),
+                                        C.c_void_p(illumination), C.c_void_p(variance_out), C.c_void_p(stream or 0)))
+
+
+def preview_merge_device(width, height, filtered, albedo=None, rgb_ptr=None, rgb8_ptr=None, stream=None):
+    """Enqueue rt_preview_merge_device (device addresses): filtered (x albedo' when albedo is given)
+    as float32 into rgb_ptr and / or as gamma-corrected texels into rgb8_ptr."""
+    check(lib().rt_preview_merge_device(width, height, C.c_void_p(filtered), C.c_void_p(albedo or 0),
+                                        C.c_void_p(rgb_ptr or 0), C.c_void_p(rgb8_ptr or 0), C.c_void_p(stream or 0)))
+
+
 def tile_order(scene, params, camera=None):
     """rt_tile_order: the pass's 64-pixel blocks in dealing order as
     (perm, n_lead, n_sky); perm is empty when the pass keeps the natural order."""
@@ -527,6 +623,10 @@ class DeviceScene:
         check(lib().rt_render_var_device(self.handle, C.byref(_cam(camera, params)), C.byref(params),
                                          C.c_void_p(rgb_ptr), C.c_void_p(var_ptr), C.c_void_p(stream or 0),
                                          C.c_void_p(segments) if segments else None))
+
+    def preview(self, params):
+        """A preview session on this scene (Preview; preview_params makes the record)."""
+        return Preview(self, params)
 
     def usage(self):
         """rt_scene_usage_get: device bytes held and the last render's cut, as a dict."""
