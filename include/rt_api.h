@@ -166,6 +166,10 @@ typedef struct rt_options {
                                        of 4 within it, if they hold 32 samples or more. A frame
                                        issued alone that fits max_pass_bytes runs in one pass in
                                        a workspace of its own. 0 = passes of max_pass_bytes     */
+    uint32_t tile_classes;          /* where a pass's dealing order is computed for a camera the
+                                       scene has not seen: 0 = on the host (0),
+                                       1 = by kernels on a stream of the scene's own, without a
+                                       device-wide synchronisation. Same order, same bits        */
 } rt_options;
 enum rt_diag {
     RT_DIAG_IEEE_ROOTS = 1u << 0,      /* the IEEE sqrt/division sequences for every root     */
@@ -319,9 +323,38 @@ int rt_scene_destroy(rt_scene *scene);
  * hardware queues - 1, i.e. 3 at HIP's default GPU_MAX_HW_QUEUES=4 and at most 7) with
  * rt_options.workspaces_per_stream slot workspaces each, so consecutive frames overlap; they
  * read only the scene and the by-value arguments, and the writes to d_rgb / d_segments are
- * enqueued on `stream`, so results appear in stream order.                                   */
+ * enqueued on `stream`, so results appear in stream order.
+ * A camera (with its rows) the scene has not rendered among its last 8 first gets its dealing
+ * order (rt_tile_order). With rt_options.tile_classes = 0 the call computes it on the host
+ * (0.5 to 1.2 ms for a 1280x720 frame), allocates and uploads it synchronously and, to drop
+ * the oldest of 8, waits for the device to go idle: a camera that moves every frame drains the
+ * frames in flight. With tile_classes = 1 two small kernels on a stream of the scene's own
+ * compute it and the call waits for that stream's event alone (one short event wait, 0.09 ms on
+ * an idle device: the host needs the class counts to size the launches), with no allocation and
+ * no device-wide wait once the scene's 8 permutation buffers exist. On a device that frames in
+ * flight fill, those kernels themselves wait for room, about as long as the host path's drain
+ * (DESIGN.md §4.13). Either way a repeated camera costs nothing, and the images are the same
+ * bits.                                                                                       */
 int rt_render_device(rt_scene *scene, const rt_camera *camera, const rt_params *params,
                      float *d_rgb, void *stream, uint64_t *d_segments);
+/* The device twin of rt_tile_order: the dealing order of the pass camera +
+ * params describe, computed by the kernels of rt_options.tile_classes = 1 (whatever the scene's
+ * own setting) from this scene's geometry, i.e. with its cluster_size. The kernels run on
+ * `stream` and write perm[0 .. n_blocks) to the device buffer d_perm (cap entries); the call
+ * returns the counts after synchronising `stream`. cap = 0 queries the counts; 0 < cap < n_blocks
+ * is RT_ERR_CAPACITY with the counts set and nothing written. A width that is no multiple of 8
+ * gives the identity and zero counts, a pixel count that is no multiple of 64 n_blocks = 0, as
+ * on the host. The classes equal rt_tile_order's exactly. Arguments are checked before any HIP
+ * call.                                                                                         */
+int rt_tile_order_device(rt_scene *scene, const rt_camera *camera, const rt_params *params,
+                         uint32_t *d_perm, uint32_t cap, uint32_t *n_blocks, uint32_t *n_lead,
+                         uint32_t *n_sky, void *stream);
+/* How many dealing orders the scene has computed on the host and on the device since it was
+ * created, and how many render / feature-buffer calls found theirs cached (each pointer may be
+ * NULL). A pass that needs no classification (pixels not in whole 64-blocks, a width that is no
+ * multiple of 8) counts as a host order under either setting.                                   */
+int rt_scene_order_counts(rt_scene *scene, uint64_t *host_orders, uint64_t *device_orders,
+                          uint64_t *hits);
 /* ---- the render with the variance of each pixel's mean luminance ----
  * d_rgb receives the bits rt_render_device writes for the same arguments; d_var receives one float
  * per pixel, laid out as the one-channel feature planes below (row * width + x; packed rows or

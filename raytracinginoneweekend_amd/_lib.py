@@ -121,6 +121,9 @@ def _declare(L):
         "rt_scene_create_ex": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, C.c_int,
                                          P(abi.RtOptions), P(C.c_void_p)]),
         "rt_scene_usage_get": (C.c_int, [C.c_void_p, P(abi.RtSceneUsage)]),
+        "rt_tile_order_device": (C.c_int, [C.c_void_p, P(abi.RtCamera), P(abi.RtParams), C.c_void_p, C.c_uint32,
+                                           P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), C.c_void_p]),
+        "rt_scene_order_counts": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)]),
         "rt_multi_create_ex": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, P(C.c_int),
                                          C.c_int, P(abi.RtOptions), P(C.c_void_p)]),
     }

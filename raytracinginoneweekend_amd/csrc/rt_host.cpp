@@ -200,12 +200,39 @@ struct rt_scene {
     bool has_geom = false;
     struct Order {
         std::vector<unsigned char> key;
-        rthost::tile_order t;
+        rthost::tile_order t;   // (an order computed on the device: the counts alone, perm stays empty)
+        uint32_t n_blocks = 0;  // blocks of the permutation (0: the pass keeps its natural order)
         uint32_t *d_perm = nullptr;
+        int slot = -1;  // >= 0: d_perm is perm_pool[slot]'s buffer, not the order's own
         uint64_t used = 0;
     };
     static constexpr size_t kOrders = 8;
     std::vector<Order> orders;
+    uint64_t order_tick = 0;  // the orders' LRU clock
+    uint64_t host_orders = 0, device_orders = 0, order_hits = 0;  // rt_scene_order_counts
+    // Dealing orders computed on the device (rt_options.tile_classes = 1, rt_tile_order_device;
+    // DESIGN.md §4.13). The geometry classify_tiles_kernel reads, uploaded at creation (KTiles::geom);
+    // then, made by the first such order: a stream of the scene's own for the two kernels (the
+    // caller's and the render streams hold the frames in flight) with the event the host waits
+    // on, the class bytes, the counts on the device and in pinned host memory. A cached order's
+    // permutation sits in a slot of perm_pool; a slot carries an event recorded after the last
+    // call that read it, which the classification stream waits on before the slot is written again.
+    float *d_geom = nullptr;
+    uint32_t geom_boxes = 0, geom_always = 0;
+    bool geom_root = false;
+    float geom_pad = 0.f;
+    hipStream_t tile_st = nullptr;
+    hipEvent_t ev_tiles = nullptr;
+    uint8_t *d_cls = nullptr;
+    uint32_t cls_cap = 0;
+    uint32_t *d_counts = nullptr, *h_counts = nullptr;
+    struct PermSlot {
+        uint32_t *d = nullptr;
+        uint32_t cap = 0;
+        hipEvent_t ev_read = nullptr;
+        bool read_valid = false;
+    };
+    PermSlot perm_pool[kOrders];
     // ring of (start, end) events bracketing the render kernels of each rt_render_device call
     static constexpr uint32_t kRing = 256;
     std::vector<hipEvent_t> ev_begin, ev_end;
@@ -433,7 +460,19 @@ int rt_scene_destroy(rt_scene *sc)
         if (p) (void)hipFree(p);
     if (sc->deep_over) (void)hipHostFree(sc->deep_over);
     for (auto &o : sc->orders)
-        if (o.d_perm) (void)hipFree(o.d_perm);
+        if (o.d_perm && o.slot < 0) (void)hipFree(o.d_perm);
+    if (sc->tile_st) {
+        (void)hipStreamSynchronize(sc->tile_st);
+        (void)hipStreamDestroy(sc->tile_st);
+    }
+    if (sc->ev_tiles) (void)hipEventDestroy(sc->ev_tiles);
+    for (auto &s : sc->perm_pool) {
+        if (s.ev_read) (void)hipEventDestroy(s.ev_read);
+        if (s.d) (void)hipFree(s.d);
+    }
+    for (void *p : {(void *)sc->d_geom, (void *)sc->d_cls, (void *)sc->d_counts})
+        if (p) (void)hipFree(p);
+    if (sc->h_counts) (void)hipHostFree(sc->h_counts);
     (void)hipSetDevice(prev);
     delete sc;
     return RT_OK;
@@ -559,6 +598,21 @@ int rt_scene_create_ex(const rt_sphere *spheres, uint32_t n_spheres, const rt_ma
         rc = up((void **)&sc->trap, trap.data(), trap.size() * sizeof(float));
     }
     if (rc == RT_OK) {
+        // the culled scene's geometry as classify_tiles_kernel reads it (rt_tiles.h KTiles::geom)
+        const scene_geom g = scene_geometry(spheres, blobs[1]);
+        std::vector<float> words(g.root, g.root + 6);
+        words.insert(words.end(), g.boxes.begin(), g.boxes.end());
+        static_assert(sizeof(rt_sphere) == 5 * sizeof(float), "rt_sphere records follow the boxes as words");
+        const size_t at = words.size();
+        words.resize(at + 5u * g.always.size());
+        if (!g.always.empty()) std::memcpy(words.data() + at, g.always.data(), g.always.size() * sizeof(rt_sphere));
+        sc->geom_boxes = static_cast<uint32_t>(g.boxes.size() / 6u);
+        sc->geom_always = static_cast<uint32_t>(g.always.size());
+        sc->geom_root = g.has_root;
+        sc->geom_pad = g.clus_pad;
+        rc = up((void **)&sc->d_geom, words.data(), words.size() * sizeof(float));
+    }
+    if (rc == RT_OK) {
         hipError_t e = hipMalloc((void **)&sc->queue_ctr, kCtrWords * sizeof(uint32_t));
         if (e != hipSuccess) rc = fail(RT_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
         if (rc == RT_OK &&
@@ -610,29 +664,168 @@ int rt_scene_create_ex(const rt_sphere *spheres, uint32_t n_spheres, const rt_ma
 }
 
 namespace {
+// ---- dealing orders computed on the device --------------------------------
+// order_blocks_kernel is one workgroup that walks the blocks 1024 at a time: passes above this
+// many blocks (a 8192 x 8192 frame) have their order computed on the host under tile_classes = 1
+constexpr uint32_t kDeviceOrderMaxBlocks = 1u << 20;
+
+// The classification's stream, event, class bytes and counts, made on first use and grown to
+// n_blocks class bytes (nothing of an earlier classification is in flight then: every one ends
+// with the host waiting for it).
+int tiles_ready(rt_scene *sc, uint32_t n_blocks)
+{
+    // (a stream of the default priority: one of the highest priority, and the kernels' waves at a
+    // raised issue priority, were measured and did not help)
+    if (!sc->tile_st) RT_HIP(hipStreamCreateWithFlags(&sc->tile_st, hipStreamNonBlocking));
+    if (!sc->ev_tiles) RT_HIP(hipEventCreateWithFlags(&sc->ev_tiles, hipEventDisableTiming));
+    if (!sc->d_counts) RT_HIP(hipMalloc((void **)&sc->d_counts, 2 * sizeof(uint32_t)));
+    if (!sc->h_counts) RT_HIP(hipHostMalloc((void **)&sc->h_counts, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    if (sc->cls_cap < n_blocks) {
+        if (sc->d_cls) RT_HIP(hipFree(sc->d_cls));
+        sc->d_cls = nullptr;
+        sc->cls_cap = 0;
+        const uint32_t cap = (n_blocks + 4095u) & ~4095u;
+        RT_HIP(hipMalloc((void **)&sc->d_cls, cap));
+        sc->cls_cap = cap;
+    }
+    return RT_OK;
+}
+
+// The blocks of a pass as classify_tiles counts them (rt_host_build.cpp): n_blocks = 0 when the
+// pass keeps its natural order, n_tiles = 0 when its width is not a multiple of the tile's.
+void pass_tiles(uint32_t W, uint32_t H, uint32_t row_offset, uint32_t row_stride, uint32_t num_rows, uint32_t tile_lw,
+                rttile::KTiles &k)
+{
+    k.n_blocks = k.n_tiles = 0;
+    const uint64_t n_pixels = static_cast<uint64_t>(W) * num_rows;
+    if (!W || !H || n_pixels == 0 || n_pixels % 64u || tile_lw > 6u) return;
+    k.n_blocks = static_cast<uint32_t>(n_pixels / 64u);
+    const uint32_t tw = 1u << tile_lw, th = 64u >> tile_lw;
+    const bool tiled = W % tw == 0u;
+    const uint32_t tiles_x = tiled ? W / tw : 1u, tiled_rows = tiled ? (num_rows / th) * th : 0u;
+    k.n_tiles = tiled ? tiles_x * (tiled_rows / th) : 0u;
+    k.pass = {W, H, row_offset, row_stride ? row_stride : 1u, tw, th, tiles_x};
+}
+
+// Enqueues the two kernels and the copy of the counts to sc->h_counts on `st`: the class bytes of
+// the pass k describes, then d_perm (null: none) and the counts.
+int enqueue_device_order(rt_scene *sc, const rt_camera &cam, rttile::KTiles &k, uint32_t *d_perm, hipStream_t st)
+{
+    k.cam = cam;
+    k.geom = sc->d_geom;
+    k.has_root = sc->geom_root ? 1u : 0u;
+    k.n_boxes = sc->geom_boxes;
+    k.n_always = sc->geom_always;
+    k.clus_pad = sc->geom_pad;
+    k.cls = sc->d_cls;
+    RT_HIP(rt::launch_classify_tiles(k, st));
+    RT_HIP(rt::launch_order_blocks(sc->d_cls, k.n_blocks, d_perm, sc->d_counts, st));
+    RT_HIP(hipMemcpyAsync(sc->h_counts, sc->d_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
+
+// The least recently used order leaves when kOrders are cached. One with a permutation of its own
+// (computed on the host) is freed once the device is idle: renders in flight may still read it.
+// One in a pool slot just leaves: the slot's event guards its next use.
+int evict_order(rt_scene *sc)
+{
+    if (sc->orders.size() < rt_scene::kOrders) return RT_OK;
+    auto lru = std::min_element(sc->orders.begin(), sc->orders.end(),
+                                [](const rt_scene::Order &a, const rt_scene::Order &b) { return a.used < b.used; });
+    if (lru->d_perm && lru->slot < 0) {
+        RT_HIP(hipDeviceSynchronize());
+        RT_HIP(hipFree(lru->d_perm));
+    }
+    sc->orders.erase(lru);
+    return RT_OK;
+}
+
+// A miss under tile_classes = 1: the order of the pass in a free slot of the pool, by the two
+// kernels on the scene's own stream. The host waits for that stream's event alone (it needs the
+// counts to size the launches), and the caller's stream waits for it too.
+int device_order(rt_scene *sc, const rt_camera &cam, rttile::KTiles &kt, hipStream_t st, rt_scene::Order &e)
+{
+    if (int rc = evict_order(sc); rc) return rc;
+    int slot = -1;
+    for (int i = 0; i < static_cast<int>(rt_scene::kOrders) && slot < 0; ++i) {
+        bool taken = false;
+        for (const auto &o : sc->orders) taken = taken || o.slot == i;
+        if (!taken) slot = i;
+    }
+    if (slot < 0) return fail(RT_ERR_DEVICE, "pass_order: no free permutation slot");
+    if (int rc = tiles_ready(sc, kt.n_blocks); rc) return rc;
+    if (sc->perm_pool[slot].cap < kt.n_blocks) {
+        // a larger pass than the pool was cut for: every slot no cached order holds grows to it
+        // (the first order of a scene allocates them all), after the last call that read it
+        for (int i = 0; i < static_cast<int>(rt_scene::kOrders); ++i) {
+            rt_scene::PermSlot &p = sc->perm_pool[i];
+            bool taken = false;
+            for (const auto &o : sc->orders) taken = taken || o.slot == i;
+            if (taken || p.cap >= kt.n_blocks) continue;
+            if (!p.ev_read) RT_HIP(hipEventCreateWithFlags(&p.ev_read, hipEventDisableTiming));
+            if (p.read_valid) RT_HIP(hipEventSynchronize(p.ev_read));
+            p.read_valid = false;
+            if (p.d) RT_HIP(hipFree(p.d));
+            p.d = nullptr;
+            p.cap = 0;
+            RT_HIP(hipMalloc((void **)&p.d, static_cast<size_t>(kt.n_blocks) * sizeof(uint32_t)));
+            p.cap = kt.n_blocks;
+        }
+    }
+    rt_scene::PermSlot &p = sc->perm_pool[slot];
+    if (p.read_valid) RT_HIP(hipStreamWaitEvent(sc->tile_st, p.ev_read, 0));
+    if (int rc = enqueue_device_order(sc, cam, kt, p.d, sc->tile_st); rc) return rc;
+    RT_HIP(hipEventRecord(sc->ev_tiles, sc->tile_st));
+    RT_HIP(hipEventSynchronize(sc->ev_tiles));
+    RT_HIP(hipStreamWaitEvent(st, sc->ev_tiles, 0));
+    e.t.n_lead = sc->h_counts[0];
+    e.t.n_sky = sc->h_counts[1];
+    if (static_cast<uint64_t>(e.t.n_lead) + e.t.n_sky > kt.n_blocks) return fail(RT_ERR_DEVICE, "pass_order: bad class counts from the device");
+    e.n_blocks = kt.n_blocks;
+    e.d_perm = p.d;
+    e.slot = slot;
+    return RT_OK;
+}
+
 // The dealing order of a pass over these rows with this camera (rt_scene::orders; computed on a
-// miss: classify_tiles on the host, the permutation uploaded once).
-int pass_order(rt_scene *sc, const rt_camera &cam, const rt::KParams &k, const rt_scene::Order **out)
+// miss: classify_tiles on the host, the permutation uploaded once; or, under tile_classes = 1
+// for a pass whose tiles are classified at all, on the device: device_order). `st`: the stream
+// of the call, on which order_used is recorded once the call's last reader is enqueued.
+int pass_order(rt_scene *sc, const rt_camera &cam, const rt::KParams &k, hipStream_t st, const rt_scene::Order **out)
 {
     *out = nullptr;
     std::vector<unsigned char> key(sizeof(rt_camera) + 7 * sizeof(uint32_t));
     const uint32_t g[7] = {k.W, k.H, k.row_offset, k.row_stride, k.num_rows, k.tile_lw, 0u};
     std::memcpy(key.data(), &cam, sizeof(rt_camera));
     std::memcpy(key.data() + sizeof(rt_camera), g, sizeof(g));
-    static uint64_t tick = 0;
     for (auto &o : sc->orders)
         if (o.key == key) {
-            o.used = ++tick;
+            o.used = ++sc->order_tick;
+            ++sc->order_hits;
             *out = &o;
             return RT_OK;
         }
     rt_scene::Order e;
     e.key.swap(key);
+    if (sc->opt.tile_classes == 1u) {
+        rttile::KTiles kt{};
+        pass_tiles(k.W, k.H, k.row_offset, k.row_stride, k.num_rows, k.tile_lw, kt);
+        if (kt.n_tiles && kt.n_blocks <= kDeviceOrderMaxBlocks) {
+            if (int rc = device_order(sc, cam, kt, st, e); rc) return rc;
+            ++sc->device_orders;
+            e.used = ++sc->order_tick;
+            sc->orders.push_back(std::move(e));
+            *out = &sc->orders.back();
+            return RT_OK;
+        }
+    }
     e.t = classify_tiles(cam, k.W, k.H, k.row_offset, k.row_stride, k.num_rows, k.tile_lw, sc->geom);
 #ifdef RT_ORDER_IDENTITY  // A/B build switch: the class machinery over the natural order (one middle group)
     for (uint32_t i = 0; i < e.t.perm.size(); ++i) e.t.perm[i] = i;
     e.t.n_lead = e.t.n_sky = 0;
 #endif
+    e.n_blocks = static_cast<uint32_t>(e.t.perm.size());
+    ++sc->host_orders;
     if (!e.t.perm.empty()) {
         RT_HIP(hipMalloc((void **)&e.d_perm, e.t.perm.size() * sizeof(uint32_t)));
         const hipError_t ce = hipMemcpy(e.d_perm, e.t.perm.data(), e.t.perm.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -641,16 +834,21 @@ int pass_order(rt_scene *sc, const rt_camera &cam, const rt::KParams &k, const r
             return fail(RT_ERR_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(ce));
         }
     }
-    if (sc->orders.size() >= rt_scene::kOrders) {
-        auto lru = std::min_element(sc->orders.begin(), sc->orders.end(),
-                                    [](const rt_scene::Order &a, const rt_scene::Order &b) { return a.used < b.used; });
-        RT_HIP(hipDeviceSynchronize());  // renders in flight may still read its permutation
-        if (lru->d_perm) RT_HIP(hipFree(lru->d_perm));
-        sc->orders.erase(lru);
-    }
-    e.used = ++tick;
+    if (int rc = evict_order(sc); rc) return rc;
+    e.used = ++sc->order_tick;
     sc->orders.push_back(std::move(e));
     *out = &sc->orders.back();
+    return RT_OK;
+}
+
+// After the last work of a call that reads the order's permutation is enqueued on (or ordered
+// before the tail of) `st`: a permutation in a pool slot is not written again before that work.
+int order_used(rt_scene *sc, const rt_scene::Order *ord, hipStream_t st)
+{
+    if (!ord || ord->slot < 0) return RT_OK;
+    rt_scene::PermSlot &p = sc->perm_pool[ord->slot];
+    RT_HIP(hipEventRecord(p.ev_read, st));
+    p.read_valid = true;
     return RT_OK;
 }
 
@@ -1077,10 +1275,10 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     // last pass (all samples, one thread per pixel, no slots), the passes deal the others
     const rt_scene::Order *ord = nullptr;
     if (order_ok && !pairs)
-        if (int rc = pass_order(sc, *camera, k, &ord); rc) return rc;
+        if (int rc = pass_order(sc, *camera, k, st, &ord); rc) return rc;
     // (max_depth 0: every sample's colour is 0, main.cxx:74, not the sky's)
     const bool sky_kernel = ord && ord->d_perm && ord->t.n_sky && P.max_depth > 0 && !(O.diag & RT_DIAG_NO_SKY) && !moments;
-    const uint32_t sky_pos0 = sky_kernel ? static_cast<uint32_t>(64u * (ord->t.perm.size() - ord->t.n_sky)) : k.n_pixels;
+    const uint32_t sky_pos0 = sky_kernel ? static_cast<uint32_t>(64u * static_cast<uint64_t>(ord->n_blocks - ord->t.n_sky)) : k.n_pixels;
     const uint32_t ring = static_cast<uint32_t>(sc->calls % rt_scene::kRing);
     ++sc->calls;
     auto others_running = [&] { return pipe && sc->last_ws >= 0 && hipEventQuery(sc->ev_done[sc->last_ws]) == hipErrorNotReady; };
@@ -1154,7 +1352,7 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
         if (ordered) {
             const rthost::tile_order &t = ord->t;
             const uint64_t S = s1 - s0;
-            const uint64_t nbl[3] = {t.n_lead, t.perm.size() - t.n_lead - t.n_sky, sky_kernel ? 0u : t.n_sky};
+            const uint64_t nbl[3] = {t.n_lead, ord->n_blocks - t.n_lead - t.n_sky, sky_kernel ? 0u : t.n_sky};
             k.block_perm = ord->d_perm;
 #ifdef RT_ORDER_NULLPERM  // A/B build switch (with RT_ORDER_IDENTITY): the identity permutation not read
             k.block_perm = nullptr;
@@ -1411,7 +1609,8 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
             sc->free_valid[wb] = true;
         }
     }
-    return RT_OK;
+    // (every launch above that reads the order's permutation is ordered before st's tail)
+    return order_used(sc, ord, st);
 }
 
 int render_compat(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
@@ -1512,10 +1711,10 @@ int render_aov_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, c
     // the dealing order and its proven-sky blocks, under the beauty's conditions for sky_kernel
     const rt_scene::Order *ord = nullptr;
     if (sc->has_geom && cull && !(O.diag & RT_DIAG_NATURAL_ORDER))
-        if (int rc = pass_order(sc, *camera, k, &ord); rc) return rc;
+        if (int rc = pass_order(sc, *camera, k, st, &ord); rc) return rc;
     a.block_perm = ord ? ord->d_perm : nullptr;
     const bool sky = a.block_perm && ord->t.n_sky && !(O.diag & RT_DIAG_NO_SKY);
-    a.sky_block0 = sky ? static_cast<uint32_t>(ord->t.perm.size() - ord->t.n_sky) : a.n_blocks;
+    a.sky_block0 = sky ? ord->n_blocks - ord->t.n_sky : a.n_blocks;
     a.albedo = A.albedo;
     a.normal = A.normal;
     a.depth = A.depth;
@@ -1529,7 +1728,7 @@ int render_aov_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, c
                      cull_mode, a.shade_lds, static_cast<size_t>(a.lds_units) * 16u, occ, sc->cu_count, grid, a.n_blocks,
                      a.n_blocks - a.sky_block0, a.block_perm ? 1 : 0, a.samples, P.spp);
     RT_HIP(rt::launch_aov(cull_mode, a, grid, st));
-    return RT_OK;
+    return order_used(sc, ord, st);
 }
 } // namespace
 
@@ -1599,6 +1798,47 @@ int rt_scene_usage_get(const rt_scene *sc, rt_scene_usage *out)
     u.static_lds_bytes = static_cast<uint32_t>(sc->static_lds[1]);
     u.max_lds_bytes = static_cast<uint32_t>(sc->max_lds);
     *out = u;
+    return RT_OK;
+}
+
+int rt_scene_order_counts(rt_scene *sc, uint64_t *host_orders, uint64_t *device_orders, uint64_t *hits)
+{
+    if (!sc) return fail(RT_ERR_INVALID, "rt_scene_order_counts: null scene");
+    if (host_orders) *host_orders = sc->host_orders;
+    if (device_orders) *device_orders = sc->device_orders;
+    if (hits) *hits = sc->order_hits;
+    return RT_OK;
+}
+
+// The device twin of rt_tile_order: the two kernels on the caller's stream over
+// this scene's geometry, the permutation into the caller's device buffer, the counts read back
+// once the stream is idle.
+int rt_tile_order_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, uint32_t *d_perm, uint32_t cap,
+                         uint32_t *n_blocks, uint32_t *n_lead, uint32_t *n_sky, void *stream)
+{
+    if (!sc || !camera || !params || !n_blocks || !n_lead || !n_sky || (cap && !d_perm))
+        return fail(RT_ERR_INVALID, "rt_tile_order_device: null argument");
+    if (camera->mode > RT_CAMERA_CORRECTED) return fail(RT_ERR_INVALID, "rt_tile_order_device: bad camera mode");
+    const uint32_t rstride = params->row_stride ? params->row_stride : 1u;
+    const uint32_t rows = params->num_rows ? params->num_rows
+                          : params->row_offset >= params->height ? 0u
+                                                                 : (params->height - params->row_offset + rstride - 1u) / rstride;
+    if (static_cast<uint64_t>(params->width) * rows >= (1ull << 32))
+        return fail(RT_ERR_INVALID, "rt_tile_order_device: more than 2^32 pixels in one pass");
+    rttile::KTiles kt{};
+    pass_tiles(params->width, params->height, params->row_offset, rstride, rows, 3u, kt);
+    *n_blocks = kt.n_blocks;
+    *n_lead = *n_sky = 0;
+    if (!kt.n_blocks) return RT_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RT_HIP(hipSetDevice(sc->device));
+    if (int rc = tiles_ready(sc, kt.n_blocks); rc) return rc;
+    const bool fits = cap >= kt.n_blocks;
+    if (int rc = enqueue_device_order(sc, *camera, kt, fits ? d_perm : nullptr, st); rc) return rc;
+    RT_HIP(hipStreamSynchronize(st));
+    *n_lead = sc->h_counts[0];
+    *n_sky = sc->h_counts[1];
+    if (cap && !fits) return fail(RT_ERR_CAPACITY, "rt_tile_order_device: perm buffer too small");
     return RT_OK;
 }
 

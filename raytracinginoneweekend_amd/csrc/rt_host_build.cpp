@@ -6,6 +6,7 @@
 // Compiled with -ffp-contract=off: the camera basis and the huge-scene generator must round
 // exactly like the reference's (g++, x86-64 SSE, no contraction).
 #include "rt_host_build.h"
+#include "rt_tiles.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -74,6 +75,7 @@ rt_options library_defaults()
     o.wave_queue_rays = 1u << 25;
     o.diag = 0;
     o.ring_pass_bytes = 384ull << 20;
+    o.tile_classes = 0;  // dealing orders computed on the host
     return o;
 }
 
@@ -93,6 +95,7 @@ int check_options(const rt_options &o)
     // (bit 18 is unassigned: it stays the unknown bit the option tests reject)
     if (o.diag & ~(((RT_DIAG_SKY_SERIAL << 1) - 1u) | RT_DIAG_NO_TRAP_END)) return bad("diag (unknown bit)");
     if ((o.diag & RT_DIAG_SHADE_LDS) && (o.diag & RT_DIAG_SHADE_GLOBAL)) return bad("diag (shade_lds with shade_global)");
+    if (o.tile_classes > 1) return bad("tile_classes (0 host, 1 device)");
     return RT_OK;
 }
 
@@ -143,6 +146,7 @@ int parse_options(const char *text, rt_options &o)
         else if (key == "transpose_max") ok = u32(n.transpose_max);
         else if (key == "wave_queue_rays") ok = u32(n.wave_queue_rays);
         else if (key == "diag") ok = u32(n.diag);
+        else if (key == "tile_classes") ok = u32(n.tile_classes);
         else {
             known = false;
             for (const auto &d : kDiag)
@@ -748,73 +752,6 @@ scene_geom scene_geometry(const rt_sphere *s, const blob_t &b)
     return g;
 }
 
-namespace {
-// closed intervals in double: every operation's result contains every value its operands can take
-struct iv {
-    double lo, hi;
-};
-iv operator+(iv a, iv b) { return {a.lo + b.lo, a.hi + b.hi}; }
-iv operator-(iv a, iv b) { return {a.lo - b.hi, a.hi - b.lo}; }
-iv operator-(iv a, double c) { return {a.lo - c, a.hi - c}; }
-iv operator*(iv a, iv b)
-{
-    const double p[4] = {a.lo * b.lo, a.lo * b.hi, a.hi * b.lo, a.hi * b.hi};
-    return {std::min(std::min(p[0], p[1]), std::min(p[2], p[3])), std::max(std::max(p[0], p[1]), std::max(p[2], p[3]))};
-}
-iv operator*(double c, iv a) { return c >= 0 ? iv{c * a.lo, c * a.hi} : iv{c * a.hi, c * a.lo}; }
-iv sq(iv a)
-{
-    if (a.lo >= 0) return {a.lo * a.lo, a.hi * a.hi};
-    if (a.hi <= 0) return {a.hi * a.hi, a.lo * a.lo};
-    return {0.0, std::max(a.lo * a.lo, a.hi * a.hi)};
-}
-iv grow(iv a, double e) { return {a.lo - e, a.hi + e}; }
-double mag(iv a) { return std::max(std::fabs(a.lo), std::fabs(a.hi)); }
-
-// Every ray o + t d (t >= 0) with o in the box o[], d in the box d[] misses the box [lo, hi]:
-// the t for which a coordinate of some ray of the beam can lie in the slab form one interval
-// per axis (o_lo + t d_lo <= hi and o_hi + t d_hi >= lo), which contains each single ray's
-// slab interval; if the three have no common t >= 0, no ray of the beam meets the box.
-bool beam_misses(const iv o[3], const iv d[3], const double lo[3], const double hi[3])
-{
-    double t0 = 0.0, t1 = INFINITY;
-    for (int k = 0; k < 3; ++k) {
-        const double a = hi[k] - o[k].lo;  // t d_lo <= a
-        if (d[k].lo > 0) t1 = std::min(t1, a / d[k].lo);
-        else if (d[k].lo < 0) t0 = std::max(t0, a / d[k].lo);
-        else if (a < 0) return true;
-        const double b = lo[k] - o[k].hi;  // t d_hi >= b
-        if (d[k].hi > 0) t0 = std::max(t0, b / d[k].hi);
-        else if (d[k].hi < 0) t1 = std::min(t1, b / d[k].hi);
-        else if (b > 0) return true;
-    }
-    // empty with a relative margin far above the double divisions' rounding
-    return t1 < 0 || t0 > t1 * (1 + 1e-9) + 1e-12;
-}
-
-// No ray of the beam gets a candidate from sphere S in the kernel's binary32 test
-// (raytracer.hxx:52-92 as rt_kernel.hip test_block8 evaluates it), proven in exact arithmetic
-// with margins of 1e-5 of the terms' magnitudes, where the binary32 evaluation errs by < 2^-21:
-// either the discriminant b^2 - a c is negative for every ray, or every ray starts outside S
-// (c > 0) moving away from it (b > 0) with b 2^-22 < kMIN a / 2, so that both roots are negative
-// and the rounded far root stays below kMIN (the kernel's own shortcut for the ground, whose
-// condition the float values then meet too).
-bool sphere_missed(const iv o[3], const iv d[3], const rt_sphere &S)
-{
-    const iv oc[3] = {o[0] - static_cast<double>(S.center[0]), o[1] - static_cast<double>(S.center[1]),
-                      o[2] - static_cast<double>(S.center[2])};
-    const double r2 = static_cast<double>(S.radius) * S.radius;
-    const iv a = sq(d[0]) + sq(d[1]) + sq(d[2]);
-    const iv b = oc[0] * d[0] + oc[1] * d[1] + oc[2] * d[2];
-    const iv c = (sq(oc[0]) + sq(oc[1]) + sq(oc[2])) - r2;
-    const double bm = mag(oc[0]) * mag(d[0]) + mag(oc[1]) * mag(d[1]) + mag(oc[2]) * mag(d[2]);
-    const double cm = mag(oc[0]) * mag(oc[0]) + mag(oc[1]) * mag(oc[1]) + mag(oc[2]) * mag(oc[2]) + r2;
-    const iv disc = sq(b) - a * c;
-    if (disc.hi < -1e-5 * (bm * bm + a.hi * cm)) return true;
-    return b.lo > 1e-5 * bm && c.lo > 1e-5 * cm && b.hi * 0x1p-22 < 0.5 * 0.008 * a.lo;
-}
-} // namespace
-
 tile_order classify_tiles(const rt_camera &cam, uint32_t W, uint32_t H, uint32_t row_offset, uint32_t row_stride,
                           uint32_t num_rows, uint32_t tile_lw, const scene_geom &g, bool sky_only)
 {
@@ -828,55 +765,11 @@ tile_order classify_tiles(const rt_camera &cam, uint32_t W, uint32_t H, uint32_t
     const uint32_t n_tiles = tiled ? tiles_x * (tiled_rows / th) : 0u;
     const uint32_t st = row_stride ? row_stride : 1u;
     std::vector<uint8_t> cls(n_blocks, 1);  // 0 lead, 1 other, 2 sky; untiled blocks stay 1
-    const double lens = std::fabs(static_cast<double>(cam.lens_radius));
-    auto classify_one = [&](uint32_t t) {
-        const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
-        const double x0 = static_cast<double>(tx) * tw, x1 = x0 + tw;  // x in [x0, x1), jitter < 1
-        const double y0 = row_offset + static_cast<double>(ty) * th * st, y1 = y0 + static_cast<double>(th - 1) * st + 1;
-        // uu = x/W + U/W, vv = y/H + U/H in binary32 (a few ulps around the exact values)
-        const iv uu = grow({x0 / W, x1 / W}, 1e-6 * (x1 / W) + 1e-12);
-        const iv vv = grow({y0 / H, y1 / H}, 1e-6 * (y1 / H) + 1e-12);
-        const iv omv = iv{1.0, 1.0} - vv;
-        // lens offset {uu rd.x, vv rd.y, 0}, |rd_k| <= lens (camera.hxx:52-54)
-        const double ox = lens * mag(uu), oy = lens * mag(vv);
-        const iv off[3] = {{-ox, ox}, {-oy, oy}, {0.0, 0.0}};
-        iv o[3], d[3];
-        for (int k = 0; k < 3; ++k) {
-            const double org = cam.origin[k], llc = cam.lower_left_corner[k], hor = cam.horizontal[k], ver = cam.vertical[k];
-            o[k] = grow(iv{org, org} + off[k], 1e-6 * (std::fabs(org) + mag(off[k])) + 1e-30);
-            // camera.hxx:56: llc + hor u + ver (1 - v) - offset (- origin in the corrected mode)
-            iv dk = ((iv{llc, llc} + hor * uu) + ver * omv) - off[k];
-            double m = std::fabs(llc) + std::fabs(hor) * mag(uu) + std::fabs(ver) * mag(omv) + mag(off[k]);
-            if (cam.mode == RT_CAMERA_CORRECTED) {
-                dk = dk - org;
-                m += std::fabs(org);
-            }
-            d[k] = grow(dk, 1e-5 * m + 1e-30);
-        }
-        const double o1 = mag(o[0]) + mag(o[1]) + mag(o[2]);
-        // twice the kernel's per-ray pad (rt_kernel.hip closest_hit: 1e-3 |o|_1 + clus_pad)
-        const double pad = 2.0 * (1e-3 * o1 + g.clus_pad) + 1e-6;
-        auto misses_box = [&](const float *r) {
-            double lo[3], hi[3];
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = static_cast<double>(r[k]) - r[3 + k] - pad;
-                hi[k] = static_cast<double>(r[k]) + r[3 + k] + pad;
-            }
-            return beam_misses(o, d, lo, hi);
-        };
-        bool sky = !g.has_root || misses_box(g.root);
-        for (size_t i = 0; sky && i < g.always.size(); ++i) sky = sphere_missed(o, d, g.always[i]);
-        if (sky) {
-            cls[t] = 2;
-            return;
-        }
-        if (sky_only) return;
-        for (size_t c = 0; c + 6 <= g.boxes.size(); c += 6)
-            if (!misses_box(g.boxes.data() + c)) {
-                cls[t] = 0;
-                break;
-            }
-    };
+    // the beam arithmetic is rt_tiles.h's, shared with the device's classify_tiles_kernel
+    const rttile::pass_view pv{W, H, row_offset, st, tw, th, tiles_x};
+    const rttile::geom_view gv{g.has_root ? g.root : nullptr, g.always.data(), static_cast<uint32_t>(g.always.size()),
+                               g.boxes.data(), static_cast<uint32_t>(g.boxes.size() / 6u), g.clus_pad};
+    auto classify_one = [&](uint32_t t) { cls[t] = rttile::classify_tile(cam, pv, gv, t, sky_only); };
     // a frame's first render with a camera waits for it: config 3's 14 400 tiles take 1.05-1.16 ms
     // on one core of the GPU box's host, 0.55-0.80 on 8 threads (each writes its own tiles;
     // tests/sanitize host_check runs it under TSAN)

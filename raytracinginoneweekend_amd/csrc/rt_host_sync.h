@@ -14,6 +14,7 @@
 #include "../../include/rt_api.h"
 #include "rt_device.h"
 #include "rt_host_build.h"
+#include "rt_tiles.h"
 
 namespace rt {
 hipError_t launch_render(int variant, int cull, const KParams &p, uint32_t grid, hipStream_t stream, int wpb = 4);
@@ -41,6 +42,9 @@ hipError_t launch_temporal(const KTemporal &k, hipStream_t stream);
 // rt_preview.hip
 hipError_t launch_preview_split(const KPreviewSplit &k, hipStream_t stream);
 hipError_t launch_preview_merge(const KPreviewMerge &k, hipStream_t stream);
+// rt_tiles.hip
+hipError_t launch_classify_tiles(const rttile::KTiles &k, hipStream_t stream);
+hipError_t launch_order_blocks(const uint8_t *cls, uint32_t n_blocks, uint32_t *perm, uint32_t *counts, hipStream_t stream);
 } // namespace rt
 
 #define RT_HIP(call)                                                                      \

@@ -628,6 +628,31 @@ class DeviceScene:
         """A preview session on this scene (Preview; preview_params makes the record)."""
         return Preview(self, params)
 
+    def tile_order(self, camera, params, stream=None):
+        """rt_tile_order_device: the pass's dealing order computed by the device's classification
+        kernels from this scene's geometry, as tile_order() returns the host's:
+        (perm, n_lead, n_sky), perm copied back from a device buffer (a torch tensor on the
+        scene's device)."""
+        import torch
+        cam = _cam(camera, params)
+        nb, nl, ns = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        st = C.c_void_p(stream or 0)
+        check(lib().rt_tile_order_device(self.handle, C.byref(cam), C.byref(params), None, 0, C.byref(nb), C.byref(nl),
+                                         C.byref(ns), st))
+        if not nb.value:
+            return np.zeros(0, dtype=np.uint32), nl.value, ns.value
+        buf = torch.empty(nb.value, dtype=torch.int32, device=f"cuda:{self.device}")
+        check(lib().rt_tile_order_device(self.handle, C.byref(cam), C.byref(params), C.c_void_p(buf.data_ptr()), nb.value,
+                                         C.byref(nb), C.byref(nl), C.byref(ns), st))
+        return buf.cpu().numpy().view(np.uint32), nl.value, ns.value
+
+    def order_counts(self):
+        """rt_scene_order_counts: dealing orders this scene computed on the host and on the device,
+        and the calls that found theirs cached, as a dict (host_orders, device_orders, hits)."""
+        h, d, n = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().rt_scene_order_counts(self.handle, C.byref(h), C.byref(d), C.byref(n)))
+        return {"host_orders": h.value, "device_orders": d.value, "hits": n.value}
+
     def usage(self):
         """rt_scene_usage_get: device bytes held and the last render's cut, as a dict."""
         u = abi.RtSceneUsage()
