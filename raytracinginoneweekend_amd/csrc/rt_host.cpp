@@ -1,13 +1,13 @@
 // rt_host.cpp — the device half of the C-ABI's host side (include/rt_api.h): device scene upload,
-// pass planning under the scene's options, frames in flight, the render entry points that replace
-// `cuda_impl` (src/main.cxx:18, src/CUDA/cuda_impl.cu:384), the cached context of the synchronous
-// host-buffer calls with the one path they all take through it (rt_host_sync.h SyncCall), and the
-// multi-GPU context. The filters and temporal accumulation are rt_host_post.cpp; the host-only
-// half (camera and scene constructors, cluster builder, options, PPM writer, the synchronous
-// calls' plane layout) is rt_host_build.cpp.
-#include <dlfcn.h>
+// the stages of a render under the scene's options (kernel choice, the frame's plan from
+// rt_plan.cpp, workspaces, the launches of every pass), frames in flight, the render entry points
+// that replace `cuda_impl` (src/main.cxx:18, src/CUDA/cuda_impl.cu:384), and the cached context of
+// the synchronous host-buffer calls with the one path they all take through it (rt_host_sync.h
+// SyncCall). The multi-GPU context is rt_host_multi.cpp; the filters and temporal accumulation are
+// rt_host_post.cpp; the host-only half is rt_host_build.cpp (camera and scene constructors,
+// cluster builder, options, PPM writer, the synchronous calls' plane layout) and rt_plan.cpp (the
+// pass planner).
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <algorithm>
 #include <cerrno>
@@ -28,6 +28,7 @@
 #include "rt_device.h"
 #include "rt_host_build.h"
 #include "rt_host_sync.h"
+#include "rt_plan.h"
 
 using namespace rthost;
 
@@ -43,38 +44,6 @@ constexpr size_t kSegWords = kMaxWs * 8 * rt::kQueueStride;
 constexpr size_t kCompatCtr = kSegWords + kMaxWs * 8 + 16;
 constexpr size_t kCtrWords = kCompatCtr + rt::kQueueStride;
 
-
-// Item dealing (guided): each queue's chunks shrink geometrically from 1/K of its remaining
-// share per wave down to 128 items — few queue atomics, big coherent chunks for most of the
-// launch, small ones at its end. Config 3 frame stream: K = 6 3.93 ms/frame with single-frame
-// latency unchanged (5.3-5.4 ms); K = 4 3.89-3.92 but 6.2 ms latency; fixed 512-item chunks
-// with a 64-item tail 4.39 ms (round 1; the fixed scheme was removed in round 4). A pass
-// issued while no other render runs (a lone frame) deals with K = 12 — its end is not hidden
-// by other launches, and smaller last chunks even it out (config 3 lone frame 3.37-3.45 vs
-// 3.55-3.59 ms, frame stream alike at K = 6/9/12/16; profiles/r03/ab/guided_k.txt).
-float guided_l2b(uint32_t total_waves, bool in_flight)
-{
-    const double k = in_flight ? 6.0 : 12.0;
-    const double wq = std::max(1.0, total_waves / 8.0);
-    const double beta = std::max(1.0 - 1.0 / (k * wq), 1.0 / (1 << 20));
-    return static_cast<float>(std::log2(beta));
-}
-
-// Workgroups per CU of a render launch. A launch that finds no other render in flight (a
-// single frame, the first of a stream) takes the occupancy: the lowest latency. One issued
-// while earlier renders still run takes half of it, (occ + 1) / 2, so consecutive launches run
-// side by side instead of each waiting for the previous one's workgroups to retire, and each
-// one's drain overlaps the others' bulk: half the occupancy, and for passes of at most
-// kShortPassItems samples with n render streams ceil(occ / (n - 1)) (4 streams: a third).
-// Measured with 3 streams (occupancy 6, in-flight grid 3 / 4 / 6):
-// config 3 frame stream 3.80-3.92 / 3.81-3.88 / 3.89-3.93 ms; 2-way row share 1.97-2.01 /
-// 2.03-2.05 / 2.08; 8-way row share 0.63 / 0.66 / 0.68 (2: 0.66); configs 4 and 5 equal.
-// With 4 streams (GPU_MAX_HW_QUEUES=8): grid 2: config 3 3.83-3.84 ms, 8-way 0.60-0.61; grid
-// 3: 3.84-3.86, 0.65 — but config 3 with the corrected camera (7 segments per primary, 29 ms
-// frames) 32.0-34.3 ms at grid 2 vs 29.8 at grid 3 (28.8 with 2 streams and full grids), so
-// the third applies to short passes only. Round 3 re-swept 3/5/7 (7 streams): the default best
-// or within noise (profiles/r03/ab/knobs_s3.txt).
-constexpr uint64_t kShortPassItems = 32ull << 20;
 // the deep launch of a lone pass stages the shading records in LDS (A/B build switch)
 // lone split passes accumulate in two parts, the first beside the deep launch (A/B build switch)
 #ifndef RT_LONE_SKY_ROOM
@@ -94,17 +63,6 @@ constexpr uint64_t kShortPassItems = 32ull << 20;
 #ifndef RT_DEEP_STATIC
 #define RT_DEEP_STATIC 1
 #endif
-#ifndef RT_SHORT_OTHERS  // A/B build switch: the divisor for short passes in flight (-1: streams - 1)
-#define RT_SHORT_OTHERS -1
-#endif
-int grid_wg_per_cu(int occ, bool in_flight, uint32_t streams, uint64_t pass_items)
-{
-    if (!in_flight) return occ;
-    const int short_others = RT_SHORT_OTHERS > 0 ? RT_SHORT_OTHERS : std::max(1, static_cast<int>(streams) - 1);
-    const int others = pass_items <= kShortPassItems ? short_others
-                                                     : std::min(2, std::max(1, static_cast<int>(streams) - 1));
-    return std::max(1, (occ + others - 1) / others);
-}
 
 } // namespace
 
@@ -267,7 +225,10 @@ uint32_t rows_of(const rt_params &p)
     return p.row_offset >= p.height ? 0 : (p.height - p.row_offset + st - 1) / st;
 }
 
-int check_params(const rt_params *p)
+} // namespace
+
+// (rt_host_sync.h: rt_host_multi.cpp's entry points check their params the same way)
+int rthost::check_params(const rt_params *p)
 {
     if (!p) return fail(RT_ERR_INVALID, "params: null");
     if (!p->width || !p->height || !p->spp) return fail(RT_ERR_INVALID, "params: width, height and spp must be > 0");
@@ -283,6 +244,8 @@ int check_params(const rt_params *p)
         return fail(RT_ERR_INVALID, "params: unknown flag");
     return RT_OK;
 }
+
+namespace {
 
 // The arguments of the feature-buffer calls, decided before any HIP call.
 int check_aov(const rt_params *p, const rt_aov_buffers *a, const char *who)
@@ -344,24 +307,6 @@ bool camera_in_fast_range(const rt_camera &c)
     return std::fabs(c.lens_radius) <= 0x1p19f;
 }
 
-// deep queue of a pass: 8 regions of 1/1024 of its samples each (at least 512): 0.8% of the
-// samples, where 0.2-0.3% reach the split depth on config 3; paths past a full region stay in the
-// main launch. A pass of fewer than rt_options.deep_min_items samples (2^25) issued while no
-// other render runs (a lone frame) is not split: its deep launch would be a serial tail of
-// about max_depth - split iterations, which such a pass's own drain does not outweigh (config
-// 3's 8-way row share alone: 1.28-1.30 ms split vs 1.03-1.10). Passes issued while others run
-// (a frame stream) are split at any size: the unsplit drain costs issue (the 8-way share ran
-// 42% more VALU instructions per sample than the full frame) and the deep launches run beside
-// the other frames (8-way share, 7 streams: 0.50-0.51 ms per frame vs 0.58-0.59 unsplit).
-uint32_t deep_region_cap(uint64_t n_samples)
-{
-    return static_cast<uint32_t>(std::max<uint64_t>(512u, n_samples / 1024u));
-}
-size_t deep_px_bytes(uint64_t n_pixels) { return (n_pixels + 255u) & ~static_cast<size_t>(255u); }
-size_t deep_queue_bytes(uint64_t n_pixels, uint64_t n_samples)
-{
-    return deep_px_bytes(n_pixels) + static_cast<size_t>(8u) * deep_region_cap(n_samples) * 60u;
-}
 // a nonzero key of the camera basis and the depth limit (FNV-1a over their bytes)
 unsigned long long camera_key(const rt_camera &c, uint32_t max_depth)
 {
@@ -663,6 +608,8 @@ int rt_scene_create_ex(const rt_sphere *spheres, uint32_t n_spheres, const rt_ma
     return RT_OK;
 }
 
+} // extern "C"
+
 namespace {
 // ---- dealing orders computed on the device --------------------------------
 // order_blocks_kernel is one workgroup that walks the blocks 1024 at a time: passes above this
@@ -901,7 +848,7 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
                        uint64_t *d_segments, float *d_var = nullptr);
 } // namespace
 
-int rt_render_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, float *d_rgb, void *stream,
+extern "C" int rt_render_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, float *d_rgb, void *stream,
                      uint64_t *d_segments)
 {
     if (!sc || !camera || !d_rgb) return fail(RT_ERR_INVALID, "rt_render_device: null argument");
@@ -931,7 +878,7 @@ int check_var_params(const rt_params *p, const char *who)
 }
 } // namespace
 
-int rt_render_var_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, float *d_rgb, float *d_var,
+extern "C" int rt_render_var_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, float *d_rgb, float *d_var,
                          void *stream, uint64_t *d_segments)
 {
     if (!sc) return fail(RT_ERR_INVALID, "rt_render_var_device: null scene");
@@ -986,21 +933,47 @@ int frame_params(const rt_scene *sc, const rt_camera *camera, const rt_params &P
     return RT_OK;
 }
 
-// d_var (rt_render_var_device, DESIGN.md §4.10): the frame also yields the variance of each pixel's
-// mean luminance. Its samples' colours must reach the accumulation one by one, so it is planned as
-// under RT_DIAG_NO_PAIRS | RT_DIAG_NO_SKY whatever the scene's options say.
-int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
-                       uint64_t *d_segments, float *d_var)
-{
-    const bool moments = d_var != nullptr;
-    rt::KParams k{};
-    if (int rc = frame_params(sc, camera, P, k, "rt_render_device"); rc) return rc;
-    const uint64_t n_pixels = k.n_pixels;
-    if (n_pixels == 0) return RT_OK;
+// ---- the stages of a render (render_device_impl, below, is their sequence) ----------------------
 
-    // Variant: exact (bit-exact) or fast (tolerance); clustered culling unless brute force is
-    // asked for; the scalar-cache A/B variant is brute force only. Each needs its blob in LDS
-    // next to the static LDS of the kernel of its traversal (sc->static_lds[culled]).
+// The shading records (the blob's tail) join the geometry in LDS unless that costs workgroups
+// per CU; RT_DIAG_SHADE_LDS / RT_DIAG_SHADE_GLOBAL force the choice (same bits). occ_for(in_lds,
+// &occ): the kernel's (cached) blocks per CU with the geometry alone or the whole blob in LDS;
+// `fits`: the whole blob fits beside the kernel's static LDS; `query_unfit`: the second
+// occupancy is asked for also when it does not.
+struct ShadePlace {
+    bool in_lds;
+    int occ;  // of the placement chosen
+};
+template <class OccFor>
+int place_shade(uint32_t diag, bool fits, bool query_unfit, OccFor occ_for, ShadePlace &out)
+{
+    int occ_geo = 0, occ_all = 0;
+    if (int rc = occ_for(0, &occ_geo); rc) return rc;
+    if (fits || query_unfit)
+        if (int rc = occ_for(1, &occ_all); rc) return rc;
+    out.in_lds = fits && ((diag & RT_DIAG_SHADE_LDS) ? true : (diag & RT_DIAG_SHADE_GLOBAL) ? false : occ_all >= occ_geo);
+    out.occ = out.in_lds ? occ_all : occ_geo;
+    return RT_OK;
+}
+
+// The kernel of a render call: what choose_kernel decides (and pair_occupancy completes).
+struct KernelChoice {
+    int variant, cull_mode;
+    bool cull, wave;
+    bool shade_fits;  // an LDS variant whose whole blob fits beside the kernel's static LDS
+    size_t lds;       // dynamic LDS bytes (k.lds_units)
+    int occ;          // workgroups per CU of the single-sample kernel
+    int occ_pr;       // ... of its sample-pair instantiation (occ when there is none)
+    bool pairs_ok;    // passes may store sample pairs
+    bool order_ok;    // passes may be dealt by tile classes
+};
+
+// Variant: exact (bit-exact) or fast (tolerance); clustered culling unless brute force is
+// asked for; the scalar-cache A/B variant is brute force only. Each needs its blob in LDS
+// next to the static LDS of the kernel of its traversal (sc->static_lds[culled]). Fills the
+// scene's part of k (blob, traversal switches, trap windows, where the shading records sit).
+int choose_kernel(rt_scene *sc, const rt_camera &camera, const rt_params &P, bool moments, rt::KParams &k, KernelChoice &c)
+{
     const rt_options &O = sc->opt;
     int variant = (P.flags & RT_FLAG_FAST_MATH) ? rt::V_FAST_LDS : rt::V_EXACT_LDS;
     bool cull = !(P.flags & RT_FLAG_BRUTE_FORCE) && sc->n_clusters[1] > 0;
@@ -1037,15 +1010,13 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     k.iso = (O.diag & RT_DIAG_NO_SHORTCUT) ? 0u : 1u;
     k.transpose_max = O.transpose_max;
     k.diag_unbounded_nb = (O.diag & RT_DIAG_UNBOUNDED_NB) ? 1u : 0u;
-    k.fast_roots = sc->in_fast_range && camera_in_fast_range(*camera) && !(O.diag & RT_DIAG_IEEE_ROOTS) ? 1u : 0u;
+    k.fast_roots = sc->in_fast_range && camera_in_fast_range(camera) && !(O.diag & RT_DIAG_IEEE_ROOTS) ? 1u : 0u;
     k.shade_offset = sc->shade_offset[b];
     // the windows hold for paths of at most rt::kTrapDepth segments: deeper renders get the empty set
     k.trap = reinterpret_cast<const float2 *>(sc->trap) +
              (P.max_depth > rt::kTrapDepth ? std::max<size_t>(sc->n_spheres, 1u) : 0u);
-    // the shading records (the blob's tail) join the geometry in LDS unless that costs
-    // workgroups per CU; RT_DIAG_SHADE_LDS / RT_DIAG_SHADE_GLOBAL force the choice (same bits)
     auto occ_for = [&](int in_lds, int *out) -> int {
-        int &o = sc->occ[variant][cull ? 1 : 0][in_lds];
+        int &o = sc->occ[variant][b][in_lds];
         if (o < 0) {
             const size_t bytes = variant == rt::V_EXACT_SCALAR ? 0 : static_cast<size_t>(in_lds ? k.blob_units : k.shade_offset) * 16u;
             RT_HIP(rt::occupancy_render(variant, cull_mode, &o, bytes));
@@ -1054,19 +1025,47 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
         *out = o;
         return RT_OK;
     };
-    int occ_geo = 0, occ_all = 0;
-    if (int rc = occ_for(0, &occ_geo); rc) return rc;
-    if (int rc = occ_for(1, &occ_all); rc) return rc;
-    const bool shade_fits = static_cast<size_t>(k.blob_units) * 16u + sc->static_lds[cull] <= sc->max_lds;
-    k.shade_lds = variant != rt::V_EXACT_SCALAR && shade_fits &&
-                  ((O.diag & RT_DIAG_SHADE_LDS) ? true : (O.diag & RT_DIAG_SHADE_GLOBAL) ? false : occ_all >= occ_geo);
+    c.shade_fits = variant != rt::V_EXACT_SCALAR && static_cast<size_t>(k.blob_units) * 16u + sc->static_lds[b] <= sc->max_lds;
+    ShadePlace place{};
+    if (int rc = place_shade(O.diag, c.shade_fits, true, occ_for, place); rc) return rc;
+    k.shade_lds = place.in_lds;
     k.lds_units = variant == rt::V_EXACT_SCALAR ? 0u : (k.shade_lds ? k.blob_units : k.shade_offset);
-    const size_t lds = static_cast<size_t>(k.lds_units) * 16u;
-    const int occ = k.shade_lds ? occ_all : occ_geo;
+    c.variant = variant;
+    c.cull_mode = cull_mode;
+    c.cull = cull;
+    c.wave = wave;
+    c.lds = static_cast<size_t>(k.lds_units) * 16u;
+    c.occ = c.occ_pr = place.occ;
+    // (sample pairs, rt_plan.cpp: culled LDS kernels only; the variance render's samples must
+    // reach the accumulation one by one)
+    c.pairs_ok = !wave && cull_mode == 7 && variant != rt::V_EXACT_SCALAR && !(O.diag & RT_DIAG_NO_PAIRS) && !moments &&
+                 c.lds + sc->static_lds_pairs <= sc->max_lds;
+    // passes dealt by tile classes: the culled LDS kernels with a scene geometry to classify
+    c.order_ok = sc->has_geom && cull_mode == 7 && !wave && variant != rt::V_EXACT_SCALAR && !(O.diag & RT_DIAG_NATURAL_ORDER);
+    return RT_OK;
+}
 
-    // deep-path split, unless a pass with this camera (and depth limit) has overflowed the deep
-    // queue on this scene: paths that long are common there (the corrected camera: 8.4% of the
-    // samples pass 8 segments, 59% of the segments), and a partial split only adds a tail
+// the pair instantiation's own occupancy (its parked colours add static LDS): the
+// grid of a paired pass is sized by it
+int pair_occupancy(rt_scene *sc, const rt::KParams &k, KernelChoice &c)
+{
+    if (!c.pairs_ok) return RT_OK;
+    int &o = sc->occ_pairs[c.variant][k.shade_lds ? 1 : 0];
+    if (o < 0) {
+        RT_HIP(rt::occupancy_render(c.variant, c.cull_mode, &o, c.lds, true));
+        o = std::max(o, 1);
+    }
+    c.occ_pr = o;
+    return RT_OK;
+}
+
+// The split depth of a render with this camera key: rt_options.deep_split, unless a pass with
+// this camera (and depth limit) has overflowed the deep queue on this scene: paths that long are
+// common there (the corrected camera: 8.4% of the samples pass 8 segments, 59% of the segments),
+// and a partial split only adds a tail. Takes the overflow reports the device left since the
+// last call into sc->deep_off first.
+uint32_t deep_split_for(rt_scene *sc, unsigned long long deep_key)
+{
     for (uint32_t w = 0; w < kMaxWs; ++w) {
         // take-and-clear in one atomic step: a report the device writes meanwhile is kept
         const unsigned long long v = __atomic_exchange_n(sc->deep_over + w, 0ull, __ATOMIC_ACQ_REL);
@@ -1080,537 +1079,564 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     sc->deep_off.erase(std::remove_if(sc->deep_off.begin(), sc->deep_off.end(),
                                       [&](const auto &e) { return sc->calls - e.second > rt_scene::kDeepOffCalls; }),
                        sc->deep_off.end());
-    const unsigned long long deep_key = camera_key(*camera, P.max_depth);
     const bool deep_off = std::find_if(sc->deep_off.begin(), sc->deep_off.end(),
                                        [&](const auto &e) { return e.first == deep_key; }) != sc->deep_off.end();
-    const uint32_t deep_split = deep_off ? 0u : O.deep_split;
-    // culled scenes only: with a handful of spheres (the simple scene, brute force) a deep
-    // segment is cheap and the deep launch's overhead outweighs the drain it saves
-    // (config 2: 0.98-1.00 vs 0.98-0.99 ms per frame)
-    const bool may_split = deep_split && !wave && cull_mode == 7 && deep_split < P.max_depth;
+    return deep_off ? 0u : sc->opt.deep_split;
+}
 
-    // Pass planning. The slot workspace of one pass (12 B per sample and pixel) stays within
-    // max_pass_bytes; passes hold a multiple of 4 samples so no reduce block straddles two.
-    // Frames in flight: render pass p runs on internal stream xs[p % bufs] with workspace
-    // w = p % n_ws, ordered after that stream's previous render and after the caller-stream
-    // work that last read workspace w (the accumulation of pass p - n_ws); render kernels
-    // touch no caller memory, so the caller stream sees the same results in the same order.
-    // One stream: everything on the caller stream. Under max_workspace_bytes one workspace per
-    // stream goes first, then the passes shrink (frames in flight are what keeps the machine
-    // full), then the streams; the bits never depend on the cut. Config 3 under 4 GiB: 2.68 ms
-    // per frame in that order (7 workspaces, 52-sample passes) vs 2.79 shrinking the passes first
-    // (14 workspaces, 24-sample passes), 2.56 uncapped (19.1 GiB; profiles/r04).
-    const uint64_t per_sample = n_pixels * 12ull;
-    // Sample pairs: a pass's full blocks of 4 samples take two pair slots each,
-    // its tail samples one: half the slot memory. Their bookkeeping costs the main launch ~3% of
-    // the frame period (profiles/r05/ab/pairs_cost.txt), so they are taken under a workspace cap
-    // (after one workspace per stream, before shorter passes) or on request (diag `pairs`), by
-    // passes issued while other renders run; a pass issued alone (a lone frame) takes single
-    // samples, whose shorter items end the launch sooner (config 3: 3.23-3.26 vs 3.38-3.45 ms),
-    // in a workspace of its own beside the ring. Culled LDS kernels only (the wavefront variant,
-    // brute force and the scalar-cache variant store single samples).
-    const bool pairs_ok = !wave && cull_mode == 7 && variant != rt::V_EXACT_SCALAR && !(O.diag & RT_DIAG_NO_PAIRS) &&
-                          !moments && lds + sc->static_lds_pairs <= sc->max_lds;
-    // passes dealt by tile classes: the culled LDS kernels with a scene geometry to classify
-    const bool order_ok = sc->has_geom && cull_mode == 7 && !wave && variant != rt::V_EXACT_SCALAR &&
-                          !(O.diag & RT_DIAG_NATURAL_ORDER);
-    // the pair instantiation's own occupancy (its parked colours add static LDS): the
-    // grid of a paired pass is sized by it
-    int occ_pr = occ;
-    if (pairs_ok) {
-        int &o = sc->occ_pairs[variant][k.shade_lds ? 1 : 0];
-        if (o < 0) {
-            RT_HIP(rt::occupancy_render(variant, cull_mode, &o, lds, true));
-            o = std::max(o, 1);
-        }
-        occ_pr = o;
-    }
-    bool pairs = pairs_ok && (O.diag & RT_DIAG_PAIRS);
-    const uint32_t full_blocks_end = P.spp & ~3u;  // samples [0, full_blocks_end) form blocks of 4
-    auto slot_rows = [&](uint64_t a, uint64_t b, bool pr) -> uint64_t {  // samples [a, b), a a multiple of 4
-        const uint64_t nb = (std::min<uint64_t>(b, full_blocks_end) - std::min<uint64_t>(a, full_blocks_end)) / 4u;
-        return pr ? (b - a) - 2u * nb : (b - a);
-    };
-    // the most slot rows of a pass of at most sp samples: a pass holding the tail (single samples)
-    // can take more rows than a full one (pairs)
-    auto max_rows = [&](uint64_t sp, bool pr) {
-        uint64_t m = 0;
-        for (uint64_t a = 0; a < P.spp; a += sp) m = std::max(m, slot_rows(a, std::min<uint64_t>(P.spp, a + sp), pr));
-        return m;
-    };
-    auto ws_bytes = [&](uint64_t sp, bool pr) { return per_sample * max_rows(sp, pr); };
-    const uint64_t items_cap = ((1ull << 31) - 8192) / n_pixels;  // items fit 31 bits
-    uint64_t spp_full = std::min<uint64_t>({P.spp, O.max_pass_bytes / per_sample, items_cap});
-    if (spp_full < P.spp) spp_full &= ~3ull;
-    if (spp_full == 0) spp_full = 4;
-    if (n_pixels * std::min<uint64_t>(spp_full, P.spp) >= (1ull << 31) - 8192)
-        return fail(RT_ERR_INVALID, "rt_render_device: too many pixels in one call");
-    auto wave_cap = [&](uint64_t sp) {
-        return static_cast<uint32_t>(std::min<uint64_t>(n_pixels * std::min<uint64_t>(sp, P.spp), O.wave_queue_rays));
-    };
-    auto n_ws_of = [](uint32_t streams, uint32_t wsps) { return streams > 1 ? streams * wsps : 1u; };
-    // Ring passes (rt_options.ring_pass_bytes): with frames in flight, a pass issued while other
-    // renders run holds at most that many slot bytes, the frame's samples cut into equal passes
-    // of a multiple of 4; a frame that fits one pass of max_pass_bytes and is issued alone (a
-    // lone frame, the drop-in's synchronous call) still runs in one pass, in a workspace of its
-    // own. The ring's 14 workspaces then hold 32-sample passes on config 3 (6.2 GiB in all
-    // instead of 19.2, frame period alike: profiles/r05/ab/ring_pass.txt) and the lone frame
-    // keeps its single launch pair. Ring passes hold at least kRingMinSamples samples per pixel:
-    // every pass reads and writes the frame's running sums (24 B per pixel), which 4-sample
-    // passes made 5% of config 4's frame (46.6 vs 44.2 ms); below that the passes stay as they were.
-    constexpr uint64_t kRingMinSamples = 32;
-    auto ring_of = [&](uint64_t sp, uint32_t streams) -> uint64_t {
-        const uint64_t sf = std::min<uint64_t>(sp, P.spp);
-        if (streams <= 1 || !O.ring_pass_bytes) return sf;
-        const uint64_t cap = (O.ring_pass_bytes / per_sample) & ~3ull;
-        if (cap >= sf || cap < kRingMinSamples) return sf;
-        const uint64_t n = (P.spp + cap - 1) / cap;  // passes of the frame at that size
-        return std::min<uint64_t>(cap, (((P.spp + n - 1) / n) + 3u) & ~3ull);
-    };
-    // a lone frame's one pass in its own workspace (beside the ring's smaller ones)
-    auto lone_whole = [&](uint64_t sp, uint32_t streams) { return streams > 1 && sp >= P.spp && ring_of(sp, streams) < P.spp; };
-    auto dq_of = [&](uint64_t sp) -> uint64_t {
-        return may_split ? deep_queue_bytes(n_pixels, n_pixels * std::min<uint64_t>(sp, P.spp)) : 0u;
-    };
-    // the ring's workspaces (pairs when there is a ring) and the lone passes' own one (singles:
-    // a whole lone frame, or a ring pass issued alone when the ring holds pairs)
-    auto footprint = [&](uint32_t streams, uint32_t wsps, uint64_t sp) -> uint64_t {
-        const uint64_t sr = ring_of(sp, streams);
-        const bool ring_pairs = pairs && streams > 1, whole = lone_whole(sp, streams);
-        uint64_t t = static_cast<uint64_t>(n_ws_of(streams, wsps)) * (ws_bytes(sr, ring_pairs) + dq_of(sr));
-        if (whole) t += ws_bytes(sp, false) + dq_of(sp);
-        else if (ring_pairs) t += ws_bytes(sr, false) + dq_of(sr);
-        if (sr < P.spp) t += moments ? 2u * per_sample : per_sample;  // the multi-pass sums (and moments)
-        if (wave) t += 2ull * wave_cap(sp) * 52u + 512u;
-        return t;
-    };
-    uint32_t bufs = wave ? 1u : render_streams_of(O);  // the wavefront variant: caller stream only
-    uint32_t wsps = O.workspaces_per_stream;
-    uint64_t spp_pass = spp_full;
-    if (const uint64_t cap = O.max_workspace_bytes) {
-        while (footprint(bufs, wsps, spp_pass) > cap) {
-            if (bufs > 1 && wsps > 1) {
-                wsps = 1;
-                continue;
-            }
-            if (bufs > 1 && pairs_ok && !pairs) {
-                pairs = true;
-                continue;
-            }
-            if (spp_pass > 4) {
-                spp_pass = std::max<uint64_t>(4, (std::min<uint64_t>(spp_pass, P.spp) - 1) & ~3ull);
-                continue;
-            }
-            spp_pass = spp_full;
-            if (bufs > 1) --bufs;
-            else return fail(RT_ERR_CAPACITY, "rt_render_device: max_workspace_bytes " + std::to_string(cap) +
-                                                  " below one 4-sample pass of this frame (" +
-                                                  std::to_string(footprint(1, 1, 4)) + " bytes)");
-        }
-    }
-    const bool pipe = bufs > 1;
-    const uint32_t n_ws = n_ws_of(bufs, wsps);
-    const uint64_t spe = std::min<uint64_t>(spp_pass, P.spp);  // a lone pass
-    const uint64_t spr = ring_of(spp_pass, bufs);                // a ring pass
-    const bool ring_pairs = pairs && pipe, whole = lone_whole(spp_pass, bufs);
-    const uint32_t lone_ws = (ring_pairs || whole) ? n_ws : kMaxWs;  // the lone passes' workspace (singles), if any
-    auto pass_of = [&](uint32_t w) { return w == lone_ws && whole ? spe : spr; };
-    auto ws_size = [&](uint32_t w) { return ws_bytes(pass_of(w), ring_pairs && w != lone_ws); };
-    // under a cap, workspaces left larger (or more numerous) by earlier frames are re-cut once
-    if (O.max_workspace_bytes) {
+// wavefront variant: two ray queues of cap rays (52 B each) and their counters, and the bounce
+// kernel's grid
+struct WaveQueues {
+    uint32_t cap = 0;
+    rt::RayQueue a{}, b{};
+    int grid = 0;
+};
+
+// The plan's memory: under a cap, workspaces left larger (or more numerous) by earlier frames are
+// re-cut once; then the multi-pass sums, the ring's slots, the lone passes' and the ray queues.
+// (The deep queues are bound pass by pass, bind_deep_queue.) Records the cut for rt_scene_usage_get.
+int reserve(rt_scene *sc, const Plan &pl, const KernelChoice &c, WaveQueues &wq)
+{
+    const PlanInput &in = pl.in;
+    const uint64_t per_sample = in.n_pixels * 12ull;
+    const bool multi_pass = pl.ring_samples < in.spp;
+    if (in.max_workspace_bytes) {
         uint64_t after = 0;
         for (uint32_t w = 0; w < kMaxWs; ++w) {
-            const bool used = w < n_ws || w == lone_ws;
-            after += used ? std::max<uint64_t>(sc->slots_bytes[w], ws_size(w)) : sc->slots_bytes[w];
-            after += used && may_split ? std::max<uint64_t>(sc->deep_bytes[w], dq_of(pass_of(w))) : sc->deep_bytes[w];
+            const bool used = w < pl.n_ws || w == pl.lone_ws;
+            after += used ? std::max<uint64_t>(sc->slots_bytes[w], pl.slot_bytes(w)) : sc->slots_bytes[w];
+            after += used && in.may_split ? std::max<uint64_t>(sc->deep_bytes[w], pl.deep_bytes(w)) : sc->deep_bytes[w];
         }
-        after += spr < P.spp ? std::max<uint64_t>(sc->acc_bytes, per_sample) : sc->acc_bytes;
-        after += spr < P.spp && moments ? std::max<uint64_t>(sc->mom_bytes, per_sample) : sc->mom_bytes;
-        after += wave ? std::max<uint64_t>(sc->wq_bytes, 2ull * wave_cap(spp_pass) * 52u + 512u) : sc->wq_bytes;
-        if (after > O.max_workspace_bytes)
+        after += multi_pass ? std::max<uint64_t>(sc->acc_bytes, per_sample) : sc->acc_bytes;
+        after += multi_pass && in.moments ? std::max<uint64_t>(sc->mom_bytes, per_sample) : sc->mom_bytes;
+        after += in.wave ? std::max<uint64_t>(sc->wq_bytes, pl.wave_bytes()) : sc->wq_bytes;
+        if (after > in.max_workspace_bytes)
             if (int rc = free_workspaces(sc); rc) return rc;
     }
-    sc->used_streams = bufs;
-    sc->used_ws = n_ws + (lone_ws < kMaxWs ? 1u : 0u);
-    sc->used_pass = static_cast<uint32_t>(spr);
+    sc->used_streams = pl.streams;
+    sc->used_ws = pl.n_ws + (pl.has_lone() ? 1u : 0u);
+    sc->used_pass = static_cast<uint32_t>(pl.ring_samples);
     sc->used_deep = 0;
     sc->used_pairs = sc->used_split = sc->used_lead = sc->used_sky = 0;
-    if (spr < P.spp)
+    if (multi_pass)
         if (int rc = ensure((void **)&sc->acc, &sc->acc_bytes, per_sample); rc) return rc;
-    if (spr < P.spp && moments)
+    if (multi_pass && in.moments)
         if (int rc = ensure((void **)&sc->mom, &sc->mom_bytes, per_sample); rc) return rc;
-    for (uint32_t w = 0; w < n_ws; ++w)
-        if (int rc = ensure((void **)&sc->slots[w], &sc->slots_bytes[w], ws_size(w)); rc) return rc;
-    if (lone_ws < kMaxWs)
-        if (int rc = ensure((void **)&sc->slots[lone_ws], &sc->slots_bytes[lone_ws], ws_size(lone_ws)); rc) return rc;
-    // wavefront variant: two ray queues of cap rays (52 B each) and their counters
-    uint32_t wcap = 0;
-    rt::RayQueue wqa{}, wqb{};
-    int wgrid = 0;
-    if (wave) {
-        wcap = wave_cap(spp_pass);
-        const size_t qbytes = static_cast<size_t>(wcap) * 52u;
+    for (uint32_t w = 0; w < pl.n_ws; ++w)
+        if (int rc = ensure((void **)&sc->slots[w], &sc->slots_bytes[w], pl.slot_bytes(w)); rc) return rc;
+    if (pl.has_lone())
+        if (int rc = ensure((void **)&sc->slots[pl.lone_ws], &sc->slots_bytes[pl.lone_ws], pl.slot_bytes(pl.lone_ws)); rc) return rc;
+    if (in.wave) {
+        wq.cap = pl.wave_cap;
+        const size_t qbytes = static_cast<size_t>(wq.cap) * 52u;
         if (int rc = ensure(&sc->wq, &sc->wq_bytes, 2 * qbytes + 512); rc) return rc;
         auto carve = [&](char *base, rt::RayQueue &q) {
             q.f = reinterpret_cast<float *>(base);
-            q.rng = reinterpret_cast<uint64_t *>(base + static_cast<size_t>(wcap) * 36u);
-            q.item = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(wcap) * 44u);
-            q.depth = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(wcap) * 48u);
+            q.rng = reinterpret_cast<uint64_t *>(base + static_cast<size_t>(wq.cap) * 36u);
+            q.item = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(wq.cap) * 44u);
+            q.depth = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(wq.cap) * 48u);
         };
         char *w0 = static_cast<char *>(sc->wq);
-        carve(w0, wqa);
-        carve(w0 + qbytes, wqb);
-        wqa.count = reinterpret_cast<uint32_t *>(w0 + 2 * qbytes);
-        wqb.count = reinterpret_cast<uint32_t *>(w0 + 2 * qbytes + 256);
-        int &ow = sc->occ_wave[cull ? 1 : 0];
+        carve(w0, wq.a);
+        carve(w0 + qbytes, wq.b);
+        wq.a.count = reinterpret_cast<uint32_t *>(w0 + 2 * qbytes);
+        wq.b.count = reinterpret_cast<uint32_t *>(w0 + 2 * qbytes + 256);
+        int &ow = sc->occ_wave[c.cull ? 1 : 0];
         if (ow < 0) {
-            RT_HIP(rt::occupancy_wave_bounce(cull_mode, &ow, lds));
+            RT_HIP(rt::occupancy_wave_bounce(c.cull_mode, &ow, c.lds));
             ow = std::max(ow, 1);
         }
-        wgrid = ow * sc->cu_count;
+        wq.grid = ow * sc->cu_count;
     }
+    return RT_OK;
+}
+
+// What every pass of a call shares.
+struct Frame {
+    rt_scene *sc;
+    const rt_params &P;
+    hipStream_t st;  // the caller's stream
+    float *d_rgb, *d_var;
+    uint64_t *d_segments;
+    KernelChoice c;
+    Plan pl;  // (pl.in.may_split: the passes may have a deep queue)
+    uint32_t deep_split;  // the split depth for this camera (0: none)
+    unsigned long long deep_key;
+    const rt_scene::Order *ord;  // the frame's dealing order, if any
+    bool sky_kernel;             // the proven-sky tiles are rendered by sky_kernel at the last pass
+    uint32_t sky_pos0;           // the first pixel position of those tiles (n_pixels: none)
+    uint32_t ring;               // the call's slot in the timing events' ring
+    // more than one render stream: passes rotate over sc->xs and the ring's workspaces
+    bool pipe() const { return pl.streams > 1; }
+};
+
+// One render pass: samples [s0, s1) of every pixel.
+struct Pass {
+    uint32_t s0, s1;
+    bool in_flight;   // another render still running (then this one takes a partial grid, grid_wg_per_cu)
+    bool pass_pairs;  // its full blocks of 4 samples stored as pairs
+    uint32_t wb;      // its workspace
+    hipStream_t xst;  // its stream
+    bool ordered;     // dealt by tile classes
+    uint32_t grid;    // workgroups of the main launch
+    bool two_part;    // the accumulation in two parts, the first beside the deep launch
+    bool sky_aside;   // the sky kernel on another stream (then the accumulation waits for ev_sky)
+    uint32_t stats_waves;  // the instrumented build: waves of the launch the counters cover
+};
+
+unsigned long long *seg_counters(const rt_scene *sc, uint32_t wb)
+{
+    return reinterpret_cast<unsigned long long *>(sc->queue_ctr + kSegWords) + 4u * wb;
+}
+
+// Every pass takes the next workspace and stream: pass p + 1's render overlaps pass p's drain
+// and accumulation, within a frame and across frames; a whole lone frame, and a pass issued
+// alone when the ring holds pairs, take the lone passes' workspace (single samples). The
+// stream waits until the workspace is free, and the pass's counters are zeroed on it.
+int begin_pass(const Frame &f, Pass &p, rt::KParams &k)
+{
+    rt_scene *sc = f.sc;
+    const Plan &pl = f.pl;
+    p.wb = 0;
+    if (pl.has_lone() && ((p.s1 - p.s0) > pl.ring_samples || (pl.ring_pairs && !p.in_flight))) {
+        p.wb = pl.lone_ws;
+    } else if (f.pipe()) {
+        p.wb = sc->next_buf % pl.n_ws;
+        sc->next_buf = p.wb + 1u;
+    }
+    const uint32_t wb = p.wb;
+    p.xst = f.pipe() ? sc->xs[wb % pl.streams] : f.st;
+    k.slots = sc->slots[wb];
+    k.queue_ctr = sc->queue_ctr + wb * 8u * rt::kQueueStride;
+    unsigned long long *seg_b = seg_counters(sc, wb);
+    k.segments = f.d_segments ? (f.pipe() ? seg_b : reinterpret_cast<unsigned long long *>(f.d_segments)) : nullptr;
+    if (f.pipe() && sc->free_valid[wb]) RT_HIP(hipStreamWaitEvent(p.xst, sc->ev_free[wb], 0));
+    if (sc->ctr_dirty[wb]) {
+        RT_HIP(hipMemsetAsync(k.queue_ctr, 0, 8 * rt::kQueueStride * sizeof(uint32_t), p.xst));
+        RT_HIP(hipMemsetAsync(seg_b, 0, 3 * sizeof(unsigned long long), p.xst));
+    }
+    sc->ctr_dirty[wb] = true;
+    if (p.s0 == 0) RT_HIP(hipEventRecord(sc->ev_begin[f.ring], p.xst));
+    k.sample_begin = p.s0;
+    k.sample_end = p.s1;
+    k.n_pair_items = static_cast<uint32_t>(((p.s1 - p.s0) - pl.slot_rows(p.s0, p.s1, p.pass_pairs)) * pl.in.n_pixels);
+    if (k.n_pair_items) ++sc->used_pairs;
+    return RT_OK;
+}
+
+// The pass's items, its main launch's grid and its dealing groups: lead tiles
+// first, then the others (then the proven sky tiles, unless the sky kernel renders them) in
+// single-sample passes of the culled LDS kernels, else the natural order.
+void deal_groups(const Frame &f, Pass &p, rt::KParams &k)
+{
+    rt_scene *sc = f.sc;
+    const rt_scene::Order *ord = f.ord;
+    const uint64_t n_pixels = k.n_pixels;
+    const uint32_t s0 = p.s0, s1 = p.s1;
+    p.ordered = ord && ord->d_perm && !k.n_pair_items;
+    fill_frame_consts(k);
+    // items: the pass's pair items and its single tail samples (one slot each); with the sky
+    // kernel, the positions before the sky tiles'
+    const uint64_t n_samples = n_pixels * (s1 - s0);
+    const uint64_t rows = f.pl.slot_rows(s0, s1, p.pass_pairs);
+    k.n_items = static_cast<uint32_t>((p.ordered && f.sky_kernel ? f.sky_pos0 : n_pixels) * rows);
+    k.n_slots = static_cast<uint32_t>(n_pixels * rows);
+    int wg_cu = grid_wg_per_cu(p.pass_pairs ? f.c.occ_pr : f.c.occ, p.in_flight, f.pl.streams, n_samples);
+    // A lone pass whose sky kernel runs beside it: the main launch's workgroups fill every
+    // CU's registers (72 VGPRs x 7 waves per SIMD), so the sky kernel would start only as they
+    // retire and end the frame after them. The main launch leaves room in proportion to the
+    // sky's share of the pixels (config 3, 73% sky: 2 of 7 workgroups per CU; lone frame
+    // 2.466-2.474 ms vs 2.528-2.547 with none, 2.474-2.495 with 1; period unchanged;
+    // profiles/r06/ab/sky_room.txt). RT_LONE_SKY_ROOM >= 0 (A/B build switch) fixes it.
+    if (!p.in_flight && f.sky_kernel && p.ordered && s1 == f.P.spp && f.pipe() && !(sc->opt.diag & RT_DIAG_SKY_SERIAL)) {
+        const double sky_frac = 1.0 - static_cast<double>(f.sky_pos0) / static_cast<double>(n_pixels);
+        const int room = RT_LONE_SKY_ROOM >= 0 ? RT_LONE_SKY_ROOM : static_cast<int>(wg_cu * sky_frac * 0.4 + 0.5);
+        wg_cu = std::max(1, wg_cu - room);
+    }
+    p.grid = static_cast<uint32_t>(
+        std::max<uint64_t>(1, std::min<uint64_t>(static_cast<uint64_t>(wg_cu) * sc->cu_count, (k.n_items + 255u) / 256u)));
+    k.n_blocks = (k.n_items + 63u) / 64u;
+    k.guided_l2b = guided_l2b(p.grid * 4u, p.in_flight);
+    k.block_perm = nullptr;
+    k.n_groups = 1;
+    k.grp_blocks[0] = k.n_blocks;
+    k.grp_items[0] = k.n_items;
+    k.grp_pix[0] = 0;
+    k.grp_pix[1] = k.grp_pix[2] = k.grp_pix[3] = k.n_pixels;
+    k.div_grp[0] = make_udiv(k.n_pixels);
+    if (p.ordered) {
+        const rthost::tile_order &t = ord->t;
+        const uint64_t S = s1 - s0;
+        const uint64_t nbl[3] = {t.n_lead, ord->n_blocks - t.n_lead - t.n_sky, f.sky_kernel ? 0u : t.n_sky};
+        k.block_perm = ord->d_perm;
+#ifdef RT_ORDER_NULLPERM  // A/B build switch (with RT_ORDER_IDENTITY): the identity permutation not read
+        k.block_perm = nullptr;
+#endif
+        k.n_groups = f.sky_kernel ? 2 : 3;
+        for (int g = 0; g < 3; ++g) {
+            k.grp_pix[g + 1] = k.grp_pix[g] + static_cast<uint32_t>(64u * nbl[g]);
+            k.grp_items[g] = static_cast<uint32_t>(64u * nbl[g] * S);
+            k.grp_blocks[g] = static_cast<uint32_t>(nbl[g] * S);  // nbl[g] blocks per sample
+            k.div_grp[g] = make_udiv(static_cast<uint32_t>(std::max<uint64_t>(64u * nbl[g], 1u)));
+        }
+        sc->used_lead = t.n_lead;
+        sc->used_sky = f.sky_kernel ? t.n_sky : 0u;
+    } else {
+        sc->used_lead = sc->used_sky = 0;
+    }
+}
+
+// deep-path split: this workspace's deep queue (its counters in the queue-counter block), for
+// the passes that are split. Leaves k.deep_depth = 0 for the others.
+int bind_deep_queue(const Frame &f, Pass &p, rt::KParams &k)
+{
+    rt_scene *sc = f.sc;
+    const rt_options &O = sc->opt;
+    const uint64_t n_pixels = k.n_pixels, n_samples = n_pixels * (p.s1 - p.s0);
+    const uint32_t wb = p.wb;
+    k.deep_depth = 0;
+    k.deep_mode = 0;
+    p.two_part = false;
+    // (diag lone_unsplit: a lone pass dealt by tile classes is not split, its trapped paths
+    // starting in its first items; slower, the accumulation then waits for the whole launch)
+    if (!(f.pl.in.may_split && (n_samples >= O.deep_min_items || p.in_flight) &&
+          (p.in_flight || !p.ordered || !(O.diag & RT_DIAG_LONE_UNSPLIT))))
+        return RT_OK;
+    const uint32_t rcap = deep_region_cap(n_samples), cap = 8u * rcap;
+    const size_t px_bytes = deep_px_bytes(n_pixels);
+    bool fresh = false;
+    if (int rc = ensure(&sc->deep[wb], &sc->deep_bytes[wb], deep_queue_bytes(n_pixels, n_samples), &fresh); rc)
+        return rc;
+    if (fresh) {  // new memory: no flag set, no pair arrival counted
+        sc->deep_clean[wb] = 0;
+        RT_HIP(hipMemsetAsync(sc->deep[wb], 0, sc->deep_bytes[wb], p.xst));
+    } else if (sc->deep_meet_at[wb] != px_bytes + static_cast<size_t>(cap) * 56u) {
+        // another layout: its arrival words lie where other arrays were (every pass that
+        // keeps the layout leaves them zero: the second arrival of a pair resets its word)
+        RT_HIP(hipMemsetAsync(static_cast<char *>(sc->deep[wb]) + px_bytes + static_cast<size_t>(cap) * 56u, 0,
+                              static_cast<size_t>(cap) * 4u, p.xst));
+    }
+    sc->deep_meet_at[wb] = px_bytes + static_cast<size_t>(cap) * 56u;
+    if (sc->deep_clean[wb] < px_bytes)  // flags over bytes a queue may have used
+        RT_HIP(hipMemsetAsync(sc->deep[wb], 0, px_bytes, p.xst));
+    // every accumulation clears the flags its pass set, and the bytes past px_bytes are
+    // this pass's queue storage: only the leading px_bytes are known to be zero after it
+    sc->deep_clean[wb] = px_bytes;
+    char *base = static_cast<char *>(sc->deep[wb]);
+    k.deep.px = reinterpret_cast<uint8_t *>(base);
+    base += px_bytes;
+    k.deep.f = reinterpret_cast<float *>(base);
+    k.deep.rng = reinterpret_cast<uint64_t *>(base + static_cast<size_t>(cap) * 36u);
+    k.deep.slot = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(cap) * 44u);
+    k.deep.hid = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(cap) * 48u);
+    k.deep.link = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(cap) * 52u);
+    k.deep.meet = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(cap) * 56u);
+    k.deep.ctr = k.queue_ctr;
+    k.deep.rcap = rcap;
+    k.deep_depth = f.deep_split;
+    p.two_part = RT_TWO_PART && f.pipe() && !p.in_flight;
+    return RT_OK;
+}
+
+// wavefront variant: the pass's items in chunks of the queues' capacity: one generation launch,
+// then max_depth bounce launches (each takes every ray of its input queue; continuing rays go
+// to the other queue)
+int launch_wavefront(const Frame &f, const Pass &p, const rt::KParams &k, const WaveQueues &wq)
+{
+    rt::KWave w{};
+    w.p = k;
+    w.cap = wq.cap;
+    for (uint32_t c0 = 0; c0 < k.n_items; c0 += wq.cap) {
+        w.item_begin = c0;
+        w.n_chunk = std::min(wq.cap, k.n_items - c0);
+        w.out = wq.a;
+        RT_HIP(rt::launch_wave_gen(w, p.xst));
+        rt::RayQueue qi = wq.a, qo = wq.b;
+        for (uint32_t b = 0; b < std::max(1u, f.P.max_depth); ++b) {
+            RT_HIP(hipMemsetAsync(qo.count, 0, sizeof(uint32_t), p.xst));
+            w.in = qi;
+            w.out = qo;
+            RT_HIP(rt::launch_wave_bounce(f.c.cull_mode, w, static_cast<uint32_t>(wq.grid), p.xst));
+            std::swap(qi, qo);
+        }
+    }
+    return RT_OK;
+}
+
+// The main launch on the pass's stream, and ev_main after it where the first part of the
+// accumulation waits for it alone.
+int launch_main(const Frame &f, Pass &p, const rt::KParams &k)
+{
+    rt_scene *sc = f.sc;
+    RT_HIP(rt::launch_render(f.c.variant, f.c.cull_mode, k, p.grid, p.xst));
+    p.stats_waves = p.grid * 4u;
+    if (p.two_part) {
+        if (!sc->ev_main[p.wb]) RT_HIP(hipEventCreateWithFlags(&sc->ev_main[p.wb], hipEventDisableTiming));
+        RT_HIP(hipEventRecord(sc->ev_main[p.wb], p.xst));
+    }
+    return RT_OK;
+}
+
+// The deep launch of a split pass: the queued paths, same stream; the main launch's grid, or for
+// a pass issued alone 8-wave workgroups with the shading records in LDS where that holds more waves.
+int launch_deep(const Frame &f, Pass &p, const rt::KParams &k)
+{
+    rt_scene *sc = f.sc;
+    const rt_options &O = sc->opt;
+    const int variant = f.c.variant;
+    ++sc->used_split;
+    rt::KParams kd = k;
+    kd.deep_mode = k.deep_depth;
+    kd.deep_depth = 0;
+    // the deep paths bounce inside glass spheres, inside the box over all clusters:
+    // the level-3 gate only costs there (alike within box noise, fewer box tests;
+    // same bits)
+    kd.use_root = 0u;
+#ifdef RT_DEEP_TMAX  // A/B build switch: every deep launch's transposition threshold
+    kd.transpose_max = std::min<uint32_t>(O.transpose_max, RT_DEEP_TMAX);
+#endif
+    // its waves at the top issue priority: each path is a chain of ~56 dependent
+    // iterations, and beside other renders' waves every iteration waits for the
+    // SIMD's other waves (config 3's 8-way share, split, 7 streams: 0.513-0.515 ms vs
+    // 0.569-0.571; profiles/r03/ab/deep_prio.txt)
+    kd.deep_prio = 1u;
+    // the shading records in LDS for the deep launch of a pass issued alone: its
+    // paths bounce in glass and shade every segment, and its few busy waves wait on
+    // each global round trip (config 3 single frame: deep launch 0.59 vs 0.65 ms).
+    // Not beside other renders: its larger workgroups then displace theirs (frame
+    // stream 2.69-2.73 vs 2.57-2.59 ms per frame, 8-way share 0.45 vs 0.42)
+    int wpb = 4;
+    uint32_t dgrid = p.grid;
+    if (RT_DEEP_LDS_STAGE && !p.in_flight && variant != rt::V_EXACT_SCALAR && !k.shade_lds && f.c.shade_fits) {
+        kd.shade_lds = 1u;
+        kd.lds_units = k.blob_units;
+        // 8-wave groups share the LDS copy (3 x 8 waves per CU instead of 3 x 4), the
+        // grid is what is resident at once, and the chunks are dealt statically: the
+        // launch was ~0.28 ms even for paths of one segment, most of it thousands of
+        // waves probing the regions' counters and groups waiting for residency
+        int &ow = sc->occ_deep_wide[variant];
+        if (ow < 0) {
+            const size_t bytes = static_cast<size_t>(k.blob_units) * 16u;
+            size_t st8 = 0, st4 = 0;
+            int o8 = 0, o4 = 0;
+            RT_HIP(rt::deep_occupancy(variant, 8, bytes, &o8, &st8));
+            // against the 4-wave deep kernel it replaces, with the same blob in LDS
+            // (the main kernel's occupancy stood in for it)
+            RT_HIP(rt::deep_occupancy(variant, 4, bytes, &o4, &st4));
+            // (the instrumented kernel follows the product's choice: wide whenever it fits)
+            ow = bytes + st8 <= sc->max_lds && (o8 * 8 > o4 * 4 || (variant == rt::V_STATS_LDS && o8 > 0)) ? o8 : 0;
+        }
+        if (RT_DEEP_WIDE && ow > 0) {
+            wpb = 8;
+            dgrid = static_cast<uint32_t>(ow * sc->cu_count);
+            kd.deep_static = RT_DEEP_STATIC ? 1u : 0u;
+            // its waves run alone on their SIMDs, so a cluster's transposed member
+            // test (three LDS round trips) pays off for fewer requesting lanes: at
+            // most 4 here (lone deep launch 0.351-0.360 vs 0.370-0.377 ms at 16;
+            // 1-8 alike, per-lane tests always 0.400-0.405; profiles/r05/deep/
+            // lone_deep_tmax.txt)
+            kd.transpose_max = std::min<uint32_t>(O.transpose_max, RT_LONE_DEEP_TMAX);
+        }
+    }
+    const bool stats_deep_only = variant == rt::V_STATS_LDS && (O.diag & RT_DIAG_STATS_DEEP_ONLY);
+    if (stats_deep_only) {
+        // diagnostics: the counters and events of the deep launch alone
+        RT_HIP(hipMemsetAsync(sc->dbg, 0, 16 * sizeof(unsigned long long), p.xst));
+        RT_HIP(hipMemsetAsync(sc->dbg + rt::kDbgEvBase, 0, rt::kDbgEvents * sizeof(unsigned long long), p.xst));
+    }
+    RT_HIP(rt::launch_render(variant, f.c.cull_mode, kd, dgrid, p.xst, wpb));
+    sc->used_deep = static_cast<uint32_t>(wpb) | (kd.deep_static ? 16u : 0u);
+    if (stats_deep_only) p.stats_waves = dgrid * static_cast<uint32_t>(wpb);
+    return RT_OK;
+}
+
+// The sky kernel at the frame's last pass: the sky tiles' pixels, every sample of the frame;
+// position i's sum to its sample-0 slot (which no pass of these groups uses), read by this
+// pass's accumulation. A pass issued alone runs it on another stream, after the workspace is
+// free, beside the main launch (which leaves it room) and the deep launch; beside other renders
+// it follows the pass on its stream.
+int launch_sky_tiles(const Frame &f, Pass &p, const rt::KParams &k)
+{
+    rt_scene *sc = f.sc;
+    const uint32_t wb = p.wb;
+    rt::KSky ks{};
+    ks.fc = k.fc;
+    ks.block_perm = k.block_perm;
+    ks.pos0 = f.sky_pos0;
+    ks.n_pix = k.n_pixels - f.sky_pos0;
+    ks.sums = k.slots + 3u * static_cast<size_t>(f.sky_pos0);
+    ks.segments = k.segments;
+    p.sky_aside = f.pipe() && !p.in_flight && !(sc->opt.diag & RT_DIAG_SKY_SERIAL);
+    if (!p.sky_aside) {
+        RT_HIP(rt::launch_sky(ks, p.xst));
+        return RT_OK;
+    }
+    // the next render stream, not a stream of its own: HIP maps streams to hardware
+    // queues round-robin in creation order, and a ninth stream shared a queue with one
+    // of the render streams, behind whose main launch the sky kernel then waited (one
+    // lone frame in three at 4 queues: 0.83 vs 0.69 ms on the 8-way share). Consecutive
+    // render streams sit on different queues.
+    hipStream_t sky_st = sc->xs[(wb % f.pl.streams + 1u) % f.pl.streams];
+    if (sc->free_valid[wb]) RT_HIP(hipStreamWaitEvent(sky_st, sc->ev_free[wb], 0));
+    // (the counters it adds to are this pass's: zeroed on xst before the main launch)
+    if (ks.segments) {
+        if (!sc->ev_main[wb]) RT_HIP(hipEventCreateWithFlags(&sc->ev_main[wb], hipEventDisableTiming));
+        if (!p.two_part) RT_HIP(hipEventRecord(sc->ev_main[wb], p.xst));
+        RT_HIP(hipStreamWaitEvent(sky_st, sc->ev_main[wb], 0));
+    }
+    RT_HIP(rt::launch_sky(ks, sky_st));
+    RT_HIP(hipEventRecord(sc->ev_sky, sky_st));
+    return RT_OK;
+}
+
+// The pass's samples into the frame on the caller's stream, after the pass's stream (and the sky
+// kernel's); then the workspace is free again.
+int accumulate(const Frame &f, const Pass &p, const rt::KParams &k)
+{
+    rt_scene *sc = f.sc;
+    const rt_params &P = f.P;
+    const uint32_t wb = p.wb, s0 = p.s0, s1 = p.s1;
+    const uint32_t full_blocks_end = P.spp & ~3u;  // samples [0, full_blocks_end) form blocks of 4
+    rt::KAccum a{};
+    a.slots = sc->slots[wb];
+    a.acc = sc->acc;
+    a.out = f.d_rgb;
+    a.out_u8 = nullptr;
+    a.mom = sc->mom;
+    a.var = f.d_var;
+    a.n_pixels = k.n_pixels;
+    a.n_samples = s1 - s0;
+    a.n_blocks = (std::min(s1, full_blocks_end) - std::min(s0, full_blocks_end)) / 4u;
+    a.paired = k.n_pair_items ? 1u : 0u;
+    a.first = s0 == 0;
+    a.last = s1 == P.spp;
+    a.spp = P.spp;
+    a.W = P.width;
+    a.tiles_x = k.tiles_x;
+    a.tiled_rows = k.tiled_rows;
+    a.tile_lw = k.tile_lw;
+    a.row_offset = k.row_offset;
+    a.row_stride = k.row_stride;
+    a.full_frame = k.full_frame;
+    if (f.pipe() && f.d_segments) a.seg_from = seg_counters(sc, wb), a.seg_to = reinterpret_cast<unsigned long long *>(f.d_segments);
+    a.queue_reset = k.queue_ctr;
+    a.queue_words = 8 * rt::kQueueStride;
+    a.block_perm = k.block_perm;
+    a.sky_pos0 = f.sky_pos0;
+    if (k.deep_depth) {
+        a.deep_over = sc->deep_over_dev + wb;
+        a.deep_key = f.deep_key;
+        a.deep_rcap = k.deep.rcap;
+    }
+    if (p.two_part) {
+        // a pass issued while no other render runs (a lone frame, the first of a stream):
+        // the pixels without deep samples accumulate beside the deep launch, the others (and
+        // the counters) after it. In a frame stream the other frames' work fills that time,
+        // and the extra launch per pass measured ~1% slower there.
+        rt::KAccum a1 = a;
+        a1.seg_from = a1.seg_to = nullptr;
+        a1.queue_reset = nullptr;
+        a1.deep_over = nullptr;
+        a1.deep_px = k.deep.px;
+        a1.part = 1;
+        RT_HIP(hipStreamWaitEvent(f.st, sc->ev_main[wb], 0));
+        RT_HIP(rt::launch_accumulate(a1, f.st));
+        a.deep_px = k.deep.px;
+        a.part = 2;
+    } else if (k.deep_depth) {
+        a.deep_px = k.deep.px;  // one part; clears the flags the main launch set
+        a.part = 3;
+    }
+    if (f.pipe()) RT_HIP(hipStreamWaitEvent(f.st, sc->ev_done[wb], 0));
+    if (p.sky_aside) RT_HIP(hipStreamWaitEvent(f.st, sc->ev_sky, 0));
+    RT_HIP(rt::launch_accumulate(a, f.st));
+    sc->ctr_dirty[wb] = false;
+    if (f.pipe()) {
+        RT_HIP(hipEventRecord(sc->ev_free[wb], f.st));
+        sc->free_valid[wb] = true;
+    }
+    return RT_OK;
+}
+
+// d_var (rt_render_var_device, DESIGN.md §4.10): the frame also yields the variance of each pixel's
+// mean luminance. Its samples' colours must reach the accumulation one by one, so it is planned as
+// under RT_DIAG_NO_PAIRS | RT_DIAG_NO_SKY whatever the scene's options say.
+int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
+                       uint64_t *d_segments, float *d_var)
+{
+    const bool moments = d_var != nullptr;
+    rt::KParams k{};
+    if (int rc = frame_params(sc, camera, P, k, "rt_render_device"); rc) return rc;
+    if (k.n_pixels == 0) return RT_OK;
+    const rt_options &O = sc->opt;
+    Frame f{sc, P, st, d_rgb, d_var, d_segments};
+    const KernelChoice &c = f.c;
+    const Plan &pl = f.pl;
+
+    // the kernel, and whether this camera's passes are split (culled scenes only: with a handful
+    // of spheres (the simple scene, brute force) a deep segment is cheap and the deep launch's
+    // overhead outweighs the drain it saves; config 2: 0.98-1.00 vs 0.98-0.99 ms per frame)
+    if (int rc = choose_kernel(sc, *camera, P, moments, k, f.c); rc) return rc;
+    f.deep_key = camera_key(*camera, P.max_depth);
+    f.deep_split = deep_split_for(sc, f.deep_key);
+    const bool may_split = f.deep_split && !c.wave && c.cull_mode == 7 && f.deep_split < P.max_depth;
+    if (int rc = pair_occupancy(sc, k, f.c); rc) return rc;
+
+    // the cut of the frame (rt_plan.cpp), then its memory
+    const PlanInput in{k.n_pixels, P.spp, c.wave ? 1u : render_streams_of(O),  // the wavefront variant: caller stream only
+                       O.workspaces_per_stream, O.max_pass_bytes, O.max_workspace_bytes, O.ring_pass_bytes, O.wave_queue_rays,
+                       c.wave, moments, c.pairs_ok, (O.diag & RT_DIAG_PAIRS) != 0u, may_split};
+    if (int rc = plan_frame(in, f.pl); rc) return rc;
+    WaveQueues wq;
+    if (int rc = reserve(sc, pl, c, wq); rc) return rc;
 
     // the frame's dealing order (not with sample pairs) and the sky kernel: the
     // tiles proven to send every primary ray to the sky are rendered by sky_kernel at the frame's
     // last pass (all samples, one thread per pixel, no slots), the passes deal the others
-    const rt_scene::Order *ord = nullptr;
-    if (order_ok && !pairs)
-        if (int rc = pass_order(sc, *camera, k, st, &ord); rc) return rc;
+    if (c.order_ok && !pl.pairs)
+        if (int rc = pass_order(sc, *camera, k, st, &f.ord); rc) return rc;
     // (max_depth 0: every sample's colour is 0, main.cxx:74, not the sky's)
-    const bool sky_kernel = ord && ord->d_perm && ord->t.n_sky && P.max_depth > 0 && !(O.diag & RT_DIAG_NO_SKY) && !moments;
-    const uint32_t sky_pos0 = sky_kernel ? static_cast<uint32_t>(64u * static_cast<uint64_t>(ord->n_blocks - ord->t.n_sky)) : k.n_pixels;
-    const uint32_t ring = static_cast<uint32_t>(sc->calls % rt_scene::kRing);
+    f.sky_kernel = f.ord && f.ord->d_perm && f.ord->t.n_sky && P.max_depth > 0 && !(O.diag & RT_DIAG_NO_SKY) && !moments;
+    f.sky_pos0 = f.sky_kernel ? static_cast<uint32_t>(64u * static_cast<uint64_t>(f.ord->n_blocks - f.ord->t.n_sky)) : k.n_pixels;
+    f.ring = static_cast<uint32_t>(sc->calls % rt_scene::kRing);
     ++sc->calls;
-    auto others_running = [&] { return pipe && sc->last_ws >= 0 && hipEventQuery(sc->ev_done[sc->last_ws]) == hipErrorNotReady; };
-    // a frame issued alone that fits one pass takes it whole (lone_whole); otherwise ring passes
-    const uint64_t first_pass = whole && !others_running() && !(O.diag & RT_DIAG_IN_FLIGHT) ? spe : spr;
+
+    auto others_running = [&] { return f.pipe() && sc->last_ws >= 0 && hipEventQuery(sc->ev_done[sc->last_ws]) == hipErrorNotReady; };
+    // a frame issued alone that fits one pass takes it whole (Plan::whole); otherwise ring passes
+    const uint64_t first_pass =
+        pl.whole && !others_running() && !(O.diag & RT_DIAG_IN_FLIGHT) ? pl.lone_samples : pl.ring_samples;
     for (uint32_t s0 = 0, s1 = 0; s0 < P.spp; s0 = s1) {
-        s1 = static_cast<uint32_t>(std::min<uint64_t>(P.spp, s0 + (s0 == 0 ? first_pass : spr)));
-        // another render still running? (then this one takes a partial grid, grid_wg_per_cu)
-        const bool in_flight = others_running() || (pipe && (O.diag & RT_DIAG_IN_FLIGHT));
-        // every pass takes the next workspace and stream: pass p + 1's render overlaps pass
-        // p's drain and accumulation, within a frame and across frames; a whole lone frame, and
-        // a pass issued alone when the ring holds pairs, take the lone passes' workspace (single
-        // samples)
-        const bool pass_pairs = ring_pairs && in_flight;
-        uint32_t wb = 0;
-        if (lone_ws < kMaxWs && ((s1 - s0) > spr || (ring_pairs && !in_flight))) {
-            wb = lone_ws;
-        } else if (pipe) {
-            wb = sc->next_buf % n_ws;
-            sc->next_buf = wb + 1u;
-        }
-        hipStream_t xst = pipe ? sc->xs[wb % bufs] : st;
-        k.slots = sc->slots[wb];
-        k.queue_ctr = sc->queue_ctr + wb * 8u * rt::kQueueStride;
-        unsigned long long *seg_b = reinterpret_cast<unsigned long long *>(sc->queue_ctr + kSegWords) + 4u * wb;
-        k.segments = d_segments ? (pipe ? seg_b : reinterpret_cast<unsigned long long *>(d_segments)) : nullptr;
-        if (pipe && sc->free_valid[wb]) RT_HIP(hipStreamWaitEvent(xst, sc->ev_free[wb], 0));
-        if (sc->ctr_dirty[wb]) {
-            RT_HIP(hipMemsetAsync(k.queue_ctr, 0, 8 * rt::kQueueStride * sizeof(uint32_t), xst));
-            RT_HIP(hipMemsetAsync(seg_b, 0, 3 * sizeof(unsigned long long), xst));
-        }
-        sc->ctr_dirty[wb] = true;
-        if (s0 == 0) RT_HIP(hipEventRecord(sc->ev_begin[ring], xst));
-        k.sample_begin = s0;
-        k.sample_end = s1;
-        k.n_pair_items = static_cast<uint32_t>(((s1 - s0) - slot_rows(s0, s1, pass_pairs)) * n_pixels);
-        if (k.n_pair_items) ++sc->used_pairs;
-        // dealing order: lead tiles first, then the others (then the proven sky
-        // tiles, unless the sky kernel renders them) in single-sample passes of the culled LDS
-        // kernels, else the natural order
-        const bool ordered = ord && ord->d_perm && !k.n_pair_items;
-        fill_frame_consts(k);
-        // items: the pass's pair items and its single tail samples (one slot each); with the sky
-        // kernel, the positions before the sky tiles'
-        const uint64_t n_samples = n_pixels * (s1 - s0);
-        k.n_items = static_cast<uint32_t>((ordered && sky_kernel ? sky_pos0 : n_pixels) * slot_rows(s0, s1, pass_pairs));
-        k.n_slots = static_cast<uint32_t>(n_pixels * slot_rows(s0, s1, pass_pairs));
-        int wg_cu = grid_wg_per_cu(pass_pairs ? occ_pr : occ, in_flight, bufs, n_samples);
-        // A lone pass whose sky kernel runs beside it: the main launch's workgroups fill every
-        // CU's registers (72 VGPRs x 7 waves per SIMD), so the sky kernel would start only as they
-        // retire and end the frame after them. The main launch leaves room in proportion to the
-        // sky's share of the pixels (config 3, 73% sky: 2 of 7 workgroups per CU; lone frame
-        // 2.466-2.474 ms vs 2.528-2.547 with none, 2.474-2.495 with 1; period unchanged;
-        // profiles/r06/ab/sky_room.txt). RT_LONE_SKY_ROOM >= 0 (A/B build switch) fixes it.
-        if (!in_flight && sky_kernel && ordered && s1 == P.spp && pipe && !(O.diag & RT_DIAG_SKY_SERIAL)) {
-            const double sky_frac = 1.0 - static_cast<double>(sky_pos0) / static_cast<double>(n_pixels);
-            const int room = RT_LONE_SKY_ROOM >= 0 ? RT_LONE_SKY_ROOM : static_cast<int>(wg_cu * sky_frac * 0.4 + 0.5);
-            wg_cu = std::max(1, wg_cu - room);
-        }
-        const uint32_t grid = static_cast<uint32_t>(
-            std::max<uint64_t>(1, std::min<uint64_t>(static_cast<uint64_t>(wg_cu) * sc->cu_count, (k.n_items + 255u) / 256u)));
-        k.n_blocks = (k.n_items + 63u) / 64u;
-        k.guided_l2b = guided_l2b(grid * 4u, in_flight);
-        k.block_perm = nullptr;
-        k.n_groups = 1;
-        k.grp_blocks[0] = k.n_blocks;
-        k.grp_items[0] = k.n_items;
-        k.grp_pix[0] = 0;
-        k.grp_pix[1] = k.grp_pix[2] = k.grp_pix[3] = k.n_pixels;
-        k.div_grp[0] = make_udiv(k.n_pixels);
-        if (ordered) {
-            const rthost::tile_order &t = ord->t;
-            const uint64_t S = s1 - s0;
-            const uint64_t nbl[3] = {t.n_lead, ord->n_blocks - t.n_lead - t.n_sky, sky_kernel ? 0u : t.n_sky};
-            k.block_perm = ord->d_perm;
-#ifdef RT_ORDER_NULLPERM  // A/B build switch (with RT_ORDER_IDENTITY): the identity permutation not read
-            k.block_perm = nullptr;
-#endif
-            k.n_groups = sky_kernel ? 2 : 3;
-            for (int g = 0; g < 3; ++g) {
-                k.grp_pix[g + 1] = k.grp_pix[g] + static_cast<uint32_t>(64u * nbl[g]);
-                k.grp_items[g] = static_cast<uint32_t>(64u * nbl[g] * S);
-                k.grp_blocks[g] = static_cast<uint32_t>(nbl[g] * S);  // nbl[g] blocks per sample
-                k.div_grp[g] = make_udiv(static_cast<uint32_t>(std::max<uint64_t>(64u * nbl[g], 1u)));
-            }
-            sc->used_lead = t.n_lead;
-            sc->used_sky = sky_kernel ? t.n_sky : 0u;
-        } else {
-            sc->used_lead = sc->used_sky = 0;
-        }
-        // deep-path split: this workspace's deep queue (its counters in the queue-counter block)
-        k.deep_depth = 0;
-        k.deep_mode = 0;
-        bool two_part = false;
-        uint32_t stats_waves = 0;  // the instrumented build: waves of the launch the counters cover
-        // (diag lone_unsplit: a lone pass dealt by tile classes is not split, its trapped paths
-        // starting in its first items; slower, the accumulation then waits for the whole launch)
-        if (may_split && (n_samples >= O.deep_min_items || in_flight) &&
-            (in_flight || !ordered || !(O.diag & RT_DIAG_LONE_UNSPLIT))) {
-            const uint32_t rcap = deep_region_cap(n_samples), cap = 8u * rcap;
-            const size_t px_bytes = deep_px_bytes(n_pixels);
-            bool fresh = false;
-            if (int rc = ensure(&sc->deep[wb], &sc->deep_bytes[wb], deep_queue_bytes(n_pixels, n_samples), &fresh); rc)
-                return rc;
-            if (fresh) {  // new memory: no flag set, no pair arrival counted
-                sc->deep_clean[wb] = 0;
-                RT_HIP(hipMemsetAsync(sc->deep[wb], 0, sc->deep_bytes[wb], xst));
-            } else if (sc->deep_meet_at[wb] != px_bytes + static_cast<size_t>(cap) * 56u) {
-                // another layout: its arrival words lie where other arrays were (every pass that
-                // keeps the layout leaves them zero: the second arrival of a pair resets its word)
-                RT_HIP(hipMemsetAsync(static_cast<char *>(sc->deep[wb]) + px_bytes + static_cast<size_t>(cap) * 56u, 0,
-                                      static_cast<size_t>(cap) * 4u, xst));
-            }
-            sc->deep_meet_at[wb] = px_bytes + static_cast<size_t>(cap) * 56u;
-            if (sc->deep_clean[wb] < px_bytes)  // flags over bytes a queue may have used
-                RT_HIP(hipMemsetAsync(sc->deep[wb], 0, px_bytes, xst));
-            // every accumulation clears the flags its pass set, and the bytes past px_bytes are
-            // this pass's queue storage: only the leading px_bytes are known to be zero after it
-            sc->deep_clean[wb] = px_bytes;
-            char *base = static_cast<char *>(sc->deep[wb]);
-            k.deep.px = reinterpret_cast<uint8_t *>(base);
-            base += px_bytes;
-            k.deep.f = reinterpret_cast<float *>(base);
-            k.deep.rng = reinterpret_cast<uint64_t *>(base + static_cast<size_t>(cap) * 36u);
-            k.deep.slot = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(cap) * 44u);
-            k.deep.hid = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(cap) * 48u);
-            k.deep.link = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(cap) * 52u);
-            k.deep.meet = reinterpret_cast<uint32_t *>(base + static_cast<size_t>(cap) * 56u);
-            k.deep.ctr = k.queue_ctr;
-            k.deep.rcap = rcap;
-            k.deep_depth = deep_split;
-            two_part = RT_TWO_PART && pipe && !in_flight;
-        }
+        s1 = static_cast<uint32_t>(std::min<uint64_t>(P.spp, s0 + (s0 == 0 ? first_pass : pl.ring_samples)));
+        Pass p{s0, s1};
+        p.in_flight = others_running() || (f.pipe() && (O.diag & RT_DIAG_IN_FLIGHT));
+        p.pass_pairs = pl.ring_pairs && p.in_flight;
+        if (int rc = begin_pass(f, p, k); rc) return rc;
+        deal_groups(f, p, k);
+        if (int rc = bind_deep_queue(f, p, k); rc) return rc;
         if (O.diag & RT_DIAG_VERBOSE)
             std::fprintf(stderr, "[rt] variant=%d cull=%d shade_lds=%u lds=%zu B occ=%d WG/CU cus=%d grid=%u items=%u "
                                  "samples=[%u,%u) streams=%u workspaces=%u split=%u guided log2(beta)*1e6=%u\n",
-                         variant, cull_mode, k.shade_lds, lds, occ, sc->cu_count, grid, k.n_items, s0, s1, bufs, n_ws,
-                         k.deep_depth, static_cast<uint32_t>(-k.guided_l2b * 1e6f));
-        if (wave) {
-            // items in chunks of wcap: one generation launch, then max_depth bounce launches
-            // (each takes every ray of its input queue; continuing rays go to the other queue)
-            rt::KWave w{};
-            w.p = k;
-            w.cap = wcap;
-            for (uint32_t c0 = 0; c0 < k.n_items; c0 += wcap) {
-                w.item_begin = c0;
-                w.n_chunk = std::min(wcap, k.n_items - c0);
-                w.out = wqa;
-                RT_HIP(rt::launch_wave_gen(w, xst));
-                rt::RayQueue qi = wqa, qo = wqb;
-                for (uint32_t b = 0; b < std::max(1u, P.max_depth); ++b) {
-                    RT_HIP(hipMemsetAsync(qo.count, 0, sizeof(uint32_t), xst));
-                    w.in = qi;
-                    w.out = qo;
-                    RT_HIP(rt::launch_wave_bounce(cull_mode, w, static_cast<uint32_t>(wgrid), xst));
-                    std::swap(qi, qo);
-                }
-            }
+                         c.variant, c.cull_mode, k.shade_lds, c.lds, c.occ, sc->cu_count, p.grid, k.n_items, s0, s1, pl.streams,
+                         pl.n_ws, k.deep_depth, static_cast<uint32_t>(-k.guided_l2b * 1e6f));
+        if (c.wave) {
+            if (int rc = launch_wavefront(f, p, k, wq); rc) return rc;
         } else {
-            RT_HIP(rt::launch_render(variant, cull_mode, k, grid, xst));
-            stats_waves = grid * 4u;
-            if (two_part) {
-                if (!sc->ev_main[wb]) RT_HIP(hipEventCreateWithFlags(&sc->ev_main[wb], hipEventDisableTiming));
-                RT_HIP(hipEventRecord(sc->ev_main[wb], xst));
-            }
-            if (k.deep_depth) {  // the deep launch: the queued paths, same grid, same stream
-                ++sc->used_split;
-                rt::KParams kd = k;
-                kd.deep_mode = k.deep_depth;
-                kd.deep_depth = 0;
-                // the deep paths bounce inside glass spheres, inside the box over all clusters:
-                // the level-3 gate only costs there (alike within box noise, fewer box tests;
-                // same bits)
-                kd.use_root = 0u;
-#ifdef RT_DEEP_TMAX  // A/B build switch: every deep launch's transposition threshold
-                kd.transpose_max = std::min<uint32_t>(O.transpose_max, RT_DEEP_TMAX);
-#endif
-                // its waves at the top issue priority: each path is a chain of ~56 dependent
-                // iterations, and beside other renders' waves every iteration waits for the
-                // SIMD's other waves (config 3's 8-way share, split, 7 streams: 0.513-0.515 ms vs
-                // 0.569-0.571; profiles/r03/ab/deep_prio.txt)
-                kd.deep_prio = 1u;
-                // the shading records in LDS for the deep launch of a pass issued alone: its
-                // paths bounce in glass and shade every segment, and its few busy waves wait on
-                // each global round trip (config 3 single frame: deep launch 0.59 vs 0.65 ms).
-                // Not beside other renders: its larger workgroups then displace theirs (frame
-                // stream 2.69-2.73 vs 2.57-2.59 ms per frame, 8-way share 0.45 vs 0.42)
-                int wpb = 4;
-                uint32_t dgrid = grid;
-                if (RT_DEEP_LDS_STAGE && !in_flight && variant != rt::V_EXACT_SCALAR && !k.shade_lds && shade_fits) {
-                    kd.shade_lds = 1u;
-                    kd.lds_units = k.blob_units;
-                    // 8-wave groups share the LDS copy (3 x 8 waves per CU instead of 3 x 4), the
-                    // grid is what is resident at once, and the chunks are dealt statically: the
-                    // launch was ~0.28 ms even for paths of one segment, most of it thousands of
-                    // waves probing the regions' counters and groups waiting for residency
-                    int &ow = sc->occ_deep_wide[variant];
-                    if (ow < 0) {
-                        const size_t bytes = static_cast<size_t>(k.blob_units) * 16u;
-                        size_t st8 = 0, st4 = 0;
-                        int o8 = 0, o4 = 0;
-                        RT_HIP(rt::deep_occupancy(variant, 8, bytes, &o8, &st8));
-                        // against the 4-wave deep kernel it replaces, with the same blob in LDS
-                        // (the main kernel's occupancy stood in for it)
-                        RT_HIP(rt::deep_occupancy(variant, 4, bytes, &o4, &st4));
-                        // (the instrumented kernel follows the product's choice: wide whenever it fits)
-                        ow = bytes + st8 <= sc->max_lds && (o8 * 8 > o4 * 4 || (variant == rt::V_STATS_LDS && o8 > 0)) ? o8 : 0;
-                    }
-                    if (RT_DEEP_WIDE && ow > 0) {
-                        wpb = 8;
-                        dgrid = static_cast<uint32_t>(ow * sc->cu_count);
-                        kd.deep_static = RT_DEEP_STATIC ? 1u : 0u;
-                        // its waves run alone on their SIMDs, so a cluster's transposed member
-                        // test (three LDS round trips) pays off for fewer requesting lanes: at
-                        // most 4 here (lone deep launch 0.351-0.360 vs 0.370-0.377 ms at 16;
-                        // 1-8 alike, per-lane tests always 0.400-0.405; profiles/r05/deep/
-                        // lone_deep_tmax.txt)
-                        kd.transpose_max = std::min<uint32_t>(O.transpose_max, RT_LONE_DEEP_TMAX);
-                    }
-                }
-                if (variant == rt::V_STATS_LDS && (O.diag & RT_DIAG_STATS_DEEP_ONLY)) {
-                    // diagnostics: the counters and events of the deep launch alone
-                    RT_HIP(hipMemsetAsync(sc->dbg, 0, 16 * sizeof(unsigned long long), xst));
-                    RT_HIP(hipMemsetAsync(sc->dbg + rt::kDbgEvBase, 0, rt::kDbgEvents * sizeof(unsigned long long), xst));
-                }
-                RT_HIP(rt::launch_render(variant, cull_mode, kd, dgrid, xst, wpb));
-                sc->used_deep = static_cast<uint32_t>(wpb) | (kd.deep_static ? 16u : 0u);
-                if (variant == rt::V_STATS_LDS && (O.diag & RT_DIAG_STATS_DEEP_ONLY)) stats_waves = dgrid * static_cast<uint32_t>(wpb);
-            }
+            if (int rc = launch_main(f, p, k); rc) return rc;
+            if (k.deep_depth)
+                if (int rc = launch_deep(f, p, k); rc) return rc;
         }
-        bool sky_aside = false;  // the sky kernel on another stream (then the accumulation waits for ev_sky)
-        if (sky_kernel && s1 == P.spp) {
-            // the sky tiles' pixels, every sample of the frame; position i's sum to its sample-0
-            // slot (which no pass of these groups uses), read by this pass's accumulation. A pass
-            // issued alone runs it on another stream, after the workspace is free, beside the main
-            // launch (which leaves it room) and the deep launch; beside other renders it follows
-            // the pass on its stream
-            rt::KSky ks{};
-            ks.fc = k.fc;
-            ks.block_perm = k.block_perm;
-            ks.pos0 = sky_pos0;
-            ks.n_pix = k.n_pixels - sky_pos0;
-            ks.sums = k.slots + 3u * static_cast<size_t>(sky_pos0);
-            ks.segments = k.segments;
-            sky_aside = pipe && !in_flight && !(O.diag & RT_DIAG_SKY_SERIAL);
-            if (sky_aside) {
-                // the next render stream, not a stream of its own: HIP maps streams to hardware
-                // queues round-robin in creation order, and a ninth stream shared a queue with one
-                // of the render streams, behind whose main launch the sky kernel then waited (one
-                // lone frame in three at 4 queues: 0.83 vs 0.69 ms on the 8-way share). Consecutive
-                // render streams sit on different queues.
-                hipStream_t sky_st = sc->xs[(wb % bufs + 1u) % bufs];
-                if (sc->free_valid[wb]) RT_HIP(hipStreamWaitEvent(sky_st, sc->ev_free[wb], 0));
-                // (the counters it adds to are this pass's: zeroed on xst before the main launch)
-                if (ks.segments) {
-                    if (!sc->ev_main[wb]) RT_HIP(hipEventCreateWithFlags(&sc->ev_main[wb], hipEventDisableTiming));
-                    if (!two_part) RT_HIP(hipEventRecord(sc->ev_main[wb], xst));
-                    RT_HIP(hipStreamWaitEvent(sky_st, sc->ev_main[wb], 0));
-                }
-                RT_HIP(rt::launch_sky(ks, sky_st));
-                RT_HIP(hipEventRecord(sc->ev_sky, sky_st));
-            } else {
-                RT_HIP(rt::launch_sky(ks, xst));
-            }
+        if (f.sky_kernel && s1 == P.spp)
+            if (int rc = launch_sky_tiles(f, p, k); rc) return rc;
+        if (c.variant == rt::V_STATS_LDS) sc->dbg_waves = p.stats_waves;
+        if (s1 == P.spp) RT_HIP(hipEventRecord(sc->ev_end[f.ring], p.xst));
+        if (f.pipe()) {
+            RT_HIP(hipEventRecord(sc->ev_done[p.wb], p.xst));
+            sc->last_ws = static_cast<int>(p.wb);
         }
-        if (variant == rt::V_STATS_LDS) sc->dbg_waves = stats_waves;
-        if (s1 == P.spp) RT_HIP(hipEventRecord(sc->ev_end[ring], xst));
-        if (pipe) {
-            RT_HIP(hipEventRecord(sc->ev_done[wb], xst));
-            sc->last_ws = static_cast<int>(wb);
-        }
-        rt::KAccum a{};
-        a.slots = sc->slots[wb];
-        a.acc = sc->acc;
-        a.out = d_rgb;
-        a.out_u8 = nullptr;
-        a.mom = sc->mom;
-        a.var = d_var;
-        a.n_pixels = k.n_pixels;
-        a.n_samples = s1 - s0;
-        a.n_blocks = (std::min(s1, full_blocks_end) - std::min(s0, full_blocks_end)) / 4u;
-        a.paired = k.n_pair_items ? 1u : 0u;
-        a.first = s0 == 0;
-        a.last = s1 == P.spp;
-        a.spp = P.spp;
-        a.W = P.width;
-        a.tiles_x = k.tiles_x;
-        a.tiled_rows = k.tiled_rows;
-        a.tile_lw = k.tile_lw;
-        a.row_offset = k.row_offset;
-        a.row_stride = k.row_stride;
-        a.full_frame = k.full_frame;
-        if (pipe && d_segments) a.seg_from = seg_b, a.seg_to = reinterpret_cast<unsigned long long *>(d_segments);
-        a.queue_reset = k.queue_ctr;
-        a.queue_words = 8 * rt::kQueueStride;
-        a.block_perm = k.block_perm;
-        a.sky_pos0 = sky_pos0;
-        if (k.deep_depth) {
-            a.deep_over = sc->deep_over_dev + wb;
-            a.deep_key = deep_key;
-            a.deep_rcap = k.deep.rcap;
-        }
-        if (two_part) {
-            // a pass issued while no other render runs (a lone frame, the first of a stream):
-            // the pixels without deep samples accumulate beside the deep launch, the others (and
-            // the counters) after it. In a frame stream the other frames' work fills that time,
-            // and the extra launch per pass measured ~1% slower there.
-            rt::KAccum a1 = a;
-            a1.seg_from = a1.seg_to = nullptr;
-            a1.queue_reset = nullptr;
-            a1.deep_over = nullptr;
-            a1.deep_px = k.deep.px;
-            a1.part = 1;
-            RT_HIP(hipStreamWaitEvent(st, sc->ev_main[wb], 0));
-            RT_HIP(rt::launch_accumulate(a1, st));
-            a.deep_px = k.deep.px;
-            a.part = 2;
-        } else if (k.deep_depth) {
-            a.deep_px = k.deep.px;  // one part; clears the flags the main launch set
-            a.part = 3;
-        }
-        if (pipe) RT_HIP(hipStreamWaitEvent(st, sc->ev_done[wb], 0));
-        if (sky_aside) RT_HIP(hipStreamWaitEvent(st, sc->ev_sky, 0));
-        RT_HIP(rt::launch_accumulate(a, st));
-        sc->ctr_dirty[wb] = false;
-        if (pipe) {
-            RT_HIP(hipEventRecord(sc->ev_free[wb], st));
-            sc->free_valid[wb] = true;
-        }
+        if (int rc = accumulate(f, p, k); rc) return rc;
     }
     // (every launch above that reads the order's permutation is ordered before st's tail)
-    return order_used(sc, ord, st);
+    return order_used(sc, f.ord, st);
 }
 
 int render_compat(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
@@ -1689,8 +1715,7 @@ int render_aov_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, c
     a.fast_roots = sc->in_fast_range && camera_in_fast_range(*camera) && !(O.diag & RT_DIAG_IEEE_ROOTS) ? 1u : 0u;
     a.shade_offset = sc->shade_offset[b];
     a.n_spheres = sc->n_spheres;
-    // the shading records join the geometry in LDS unless that costs workgroups per CU, as for the
-    // render kernels; RT_DIAG_SHADE_LDS / RT_DIAG_SHADE_GLOBAL force the choice (same bits)
+    // the shading records join the geometry in LDS by the render kernels' rule (place_shade)
     auto occ_for = [&](int in_lds, int *out) -> int {
         int &o = sc->occ_aov[b][in_lds];
         if (o < 0) {
@@ -1701,13 +1726,11 @@ int render_aov_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, c
         return RT_OK;
     };
     const bool shade_fits = static_cast<size_t>(sc->blob_units[b]) * 16u + static_lds <= sc->max_lds;
-    int occ_geo = 0, occ_all = 0;
-    if (int rc = occ_for(0, &occ_geo); rc) return rc;
-    if (shade_fits)
-        if (int rc = occ_for(1, &occ_all); rc) return rc;
-    a.shade_lds = shade_fits && ((O.diag & RT_DIAG_SHADE_LDS) ? true : (O.diag & RT_DIAG_SHADE_GLOBAL) ? false : occ_all >= occ_geo);
+    ShadePlace place{};
+    if (int rc = place_shade(O.diag, shade_fits, false, occ_for, place); rc) return rc;
+    a.shade_lds = place.in_lds;
     a.lds_units = a.shade_lds ? sc->blob_units[b] : sc->shade_offset[b];
-    const int occ = a.shade_lds ? occ_all : occ_geo;
+    const int occ = place.occ;
     // the dealing order and its proven-sky blocks, under the beauty's conditions for sky_kernel
     const rt_scene::Order *ord = nullptr;
     if (sc->has_geom && cull && !(O.diag & RT_DIAG_NATURAL_ORDER))
@@ -1758,8 +1781,6 @@ int rt_render_cuda_impl(uint32_t width, uint32_t height, uint8_t *rgb_out)
     rt_params p{width, height, 48, 32, 0, 0, 1, 0, RT_FLAG_CUDA_COMPAT};  // cuda_impl.cu:62-63
     return rt_render_rgb8(s, ns, m, nm, &cam, &p, rgb_out, nullptr);
 }
-
-} // extern "C"
 
 int rt_scene_kernel_times(rt_scene *sc, uint32_t max, float *ms, uint32_t *n)
 {
@@ -2182,541 +2203,5 @@ int rt_render_rgb8(const rt_sphere *spheres, uint32_t n_spheres, const rt_materi
     if (!rgb_out) return fail(RT_ERR_INVALID, "rt_render_rgb8: null output");
     return render_host(spheres, n_spheres, materials, n_materials, camera, params, nullptr, rgb_out, stats);
 }
-
-} // extern "C"
-
-// ---- single-process multi-GPU render: interleaved row tiles + RCCL gather over xGMI -----
-// RCCL is opened with dlopen (librccl.so.1) on first use, so the library has no link-time
-// dependency on it and shares the process's RCCL if another component (torch) loaded it.
-namespace {
-struct rccl_api {
-    decltype(&ncclCommInitAll) comm_init_all = nullptr;
-    decltype(&ncclCommDestroy) comm_destroy = nullptr;
-    decltype(&ncclSend) send = nullptr;
-    decltype(&ncclRecv) recv = nullptr;
-    decltype(&ncclGroupStart) group_start = nullptr;
-    decltype(&ncclGroupEnd) group_end = nullptr;
-    decltype(&ncclGetErrorString) error_string = nullptr;
-    bool ok = false;
-};
-const rccl_api &rccl()
-{
-    static rccl_api api = [] {
-        rccl_api a;
-        void *h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-        if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!h) return a;
-        a.comm_init_all = reinterpret_cast<decltype(a.comm_init_all)>(dlsym(h, "ncclCommInitAll"));
-        a.comm_destroy = reinterpret_cast<decltype(a.comm_destroy)>(dlsym(h, "ncclCommDestroy"));
-        a.send = reinterpret_cast<decltype(a.send)>(dlsym(h, "ncclSend"));
-        a.recv = reinterpret_cast<decltype(a.recv)>(dlsym(h, "ncclRecv"));
-        a.group_start = reinterpret_cast<decltype(a.group_start)>(dlsym(h, "ncclGroupStart"));
-        a.group_end = reinterpret_cast<decltype(a.group_end)>(dlsym(h, "ncclGroupEnd"));
-        a.error_string = reinterpret_cast<decltype(a.error_string)>(dlsym(h, "ncclGetErrorString"));
-        a.ok = a.comm_init_all && a.comm_destroy && a.send && a.recv && a.group_start && a.group_end && a.error_string;
-        return a;
-    }();
-    return api;
-}
-
-// RT_DIAG_STANDIN_TRANSPORT: RCCL's point-to-point calls restated as stream-ordered device
-// copies between ranks that share one device, so that the RCCL gather branch of
-// rt_multi_render_device (grouped send/recv per peer on the ranks' streams, slot offsets, tile
-// reuse across frames in flight) runs on one GPU. Semantics kept: within a group, a send on
-// rank a's stream to peer b pairs with the receive on rank b's stream from a; the receive's
-// stream waits for the send stream's prior work, copies, and the send stream's later work
-// waits for the copy (the tile may not be overwritten before it has left), as with RCCL.
-namespace standin {
-struct comm { int rank, n, dev; };
-struct op { bool is_send; const void *src; void *dst; size_t bytes; int peer; comm *c; hipStream_t st; };
-thread_local std::vector<op> g_ops;
-thread_local int g_depth = 0;
-size_t type_bytes(ncclDataType_t t) { return t == ncclFloat ? 4u : t == ncclUint8 ? 1u : 0u; }
-ncclResult_t comm_init_all(ncclComm_t *comms, int n, const int *devs)
-{
-    for (int i = 0; i < n; ++i) comms[i] = reinterpret_cast<ncclComm_t>(new comm{i, n, devs ? devs[i] : i});
-    return ncclSuccess;
-}
-ncclResult_t comm_destroy(ncclComm_t c)
-{
-    delete reinterpret_cast<comm *>(c);
-    return ncclSuccess;
-}
-ncclResult_t push(bool is_send, const void *src, void *dst, size_t count, ncclDataType_t t, int peer, ncclComm_t c,
-                  hipStream_t st)
-{
-    comm *cc = reinterpret_cast<comm *>(c);
-    if (!cc || !type_bytes(t) || peer < 0 || peer >= cc->n || peer == cc->rank) return ncclInvalidArgument;
-    // only grouped calls are emulated: a call outside a group is refused and leaves nothing behind
-    // for the next group to pair with
-    if (!g_depth) return ncclInvalidUsage;
-    g_ops.push_back({is_send, src, dst, count * type_bytes(t), peer, cc, st});
-    return ncclSuccess;
-}
-ncclResult_t send(const void *buf, size_t count, ncclDataType_t t, int peer, ncclComm_t c, hipStream_t st)
-{
-    return push(true, buf, nullptr, count, t, peer, c, st);
-}
-ncclResult_t recv(void *buf, size_t count, ncclDataType_t t, int peer, ncclComm_t c, hipStream_t st)
-{
-    return push(false, nullptr, buf, count, t, peer, c, st);
-}
-ncclResult_t group_start()
-{
-    if (!g_depth) g_ops.clear();
-    ++g_depth;
-    return ncclSuccess;
-}
-ncclResult_t group_end()
-{
-    if (g_depth <= 0) return ncclInvalidUsage;
-    if (--g_depth) return ncclSuccess;
-    std::vector<op> ops;
-    ops.swap(g_ops);
-    std::vector<bool> used(ops.size(), false);
-    ncclResult_t res = ncclSuccess;
-    for (size_t i = 0; i < ops.size() && res == ncclSuccess; ++i) {
-        if (!ops[i].is_send) continue;
-        const op &sd = ops[i];
-        size_t j = 0;
-        for (; j < ops.size(); ++j)
-            if (!used[j] && !ops[j].is_send && ops[j].c->rank == sd.peer && ops[j].peer == sd.c->rank) break;
-        if (j == ops.size() || ops[j].bytes != sd.bytes) {
-            res = ncclInvalidUsage;
-            break;
-        }
-        used[i] = used[j] = true;
-        const op &rv = ops[j];
-        hipEvent_t sent = nullptr, landed = nullptr;
-        if (hipEventCreateWithFlags(&sent, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&landed, hipEventDisableTiming) != hipSuccess || hipEventRecord(sent, sd.st) != hipSuccess ||
-            hipStreamWaitEvent(rv.st, sent, 0) != hipSuccess ||
-            hipMemcpyAsync(rv.dst, sd.src, sd.bytes, hipMemcpyDeviceToDevice, rv.st) != hipSuccess ||
-            hipEventRecord(landed, rv.st) != hipSuccess || hipStreamWaitEvent(sd.st, landed, 0) != hipSuccess)
-            res = ncclUnhandledCudaError;
-        if (sent) (void)hipEventDestroy(sent);
-        if (landed) (void)hipEventDestroy(landed);
-    }
-    for (size_t i = 0; i < ops.size() && res == ncclSuccess; ++i)
-        if (!used[i]) res = ncclInvalidUsage;  // a receive without its send
-    return res;
-}
-const char *error_string(ncclResult_t r) { return r == ncclSuccess ? "success" : "stand-in transport: unmatched or failed call"; }
-} // namespace standin
-
-const rccl_api &standin_api()
-{
-    static rccl_api api = [] {
-        rccl_api a;
-        a.comm_init_all = standin::comm_init_all;
-        a.comm_destroy = standin::comm_destroy;
-        a.send = standin::send;
-        a.recv = standin::recv;
-        a.group_start = standin::group_start;
-        a.group_end = standin::group_end;
-        a.error_string = standin::error_string;
-        a.ok = true;
-        return a;
-    }();
-    return api;
-}
-} // namespace
-
-// Persistent multi-GPU context (rt_multi_*): rank r of N renders the rows y = r, r + N, ...
-// (interleaved single rows balance sky against ground) on its device into a packed tile;
-// optionally the gamma/u8 epilogue runs on the tile (3 B per pixel instead of 12 over xGMI);
-// the tiles are gathered to rank 0's device and de-interleaved into the caller's frame.
-// Everything that does not depend on the frame is built once at rt_multi_create: per-device
-// scenes, rank streams, the RCCL communicators (ncclCommInitAll over the distinct devices), the
-// segment counters; tiles and the gather buffer grow on first use of a frame size. Ranks that
-// share a device with rank 0 ("virtual ranks": a one-GPU rehearsal of an N-way split) move
-// their tile with a device copy where RCCL would send/recv; the tile layout, the gather buffer
-// and the de-interleave are the same code either way.
-struct rt_multi {
-    int n = 0;
-    std::vector<int> dev;
-    bool rccl = false;  // every rank on its own device: gather over RCCL
-    const rccl_api *api = nullptr;  // RCCL, or the stand-in (RT_DIAG_STANDIN_TRANSPORT)
-    std::vector<rt_scene *> sc;
-    std::vector<hipStream_t> st;        // rank r > 0: its stream (rank 0 runs on the caller's stream)
-    std::vector<ncclComm_t> comm;
-    std::vector<void *> tile;           // f32 tile per rank, on its device
-    std::vector<size_t> tile_bytes;
-    std::vector<void *> tile8;          // u8 tile per rank (RT_OUTPUT_RGB8)
-    std::vector<size_t> tile8_bytes;
-    std::vector<uint64_t *> seg;        // per rank: {segments, sphere tests, box tests}
-    void *gather = nullptr;             // on rank 0's device: N slots of the largest tile
-    size_t gather_bytes = 0;
-    std::vector<hipEvent_t> ev_ready;   // virtual rank r: its tile is complete
-    hipEvent_t ev_copied = nullptr;     // caller stream: virtual ranks' tiles copied out
-    bool copied_valid = false;
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
-};
-
-namespace {
-
-int multi_fail_destroy(rt_multi *m, int rc);
-
-// ensure() on a given device. Growing reallocates and so synchronises that device; the
-// buffers of a context grow only when a frame is larger than any before it (rt_api.h)
-int grow(int device, void **ptr, size_t *have, size_t want)
-{
-    if (*have >= want && *ptr) return RT_OK;
-    RT_HIP(hipSetDevice(device));
-    if (*ptr) {
-        RT_HIP(hipDeviceSynchronize());
-        RT_HIP(hipFree(*ptr));
-        *ptr = nullptr;
-        *have = 0;
-    }
-    RT_HIP(hipMalloc(ptr, std::max<size_t>(want, 256)));
-    *have = want;
-    return RT_OK;
-}
-
-uint32_t multi_rows(uint32_t H, int n, int r)
-{
-    return static_cast<uint32_t>(r) < H ? (H - static_cast<uint32_t>(r) + static_cast<uint32_t>(n) - 1) / static_cast<uint32_t>(n) : 0u;
-}
-
-} // namespace
-
-extern "C" {
-
-int rt_multi_create(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
-                    const int *devices, int n_ranks, rt_multi **out)
-{
-    return rt_multi_create_ex(spheres, n_spheres, materials, n_materials, devices, n_ranks, nullptr, out);
-}
-
-int rt_multi_create_ex(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
-                       const int *devices, int n_ranks, const rt_options *options, rt_multi **out)
-{
-    if (!out) return fail(RT_ERR_INVALID, "rt_multi_create: null output");
-    *out = nullptr;
-    rt_options opt;
-    if (options) {
-        if (int rc = check_options(*options); rc) return rc;
-        opt = *options;
-    } else if (int rc = default_options(opt); rc) {
-        return rc;
-    }
-    // two supported layouts: every rank on its own device (RCCL), or every rank on rank 0's
-    // device (virtual ranks); a mix would gather through cross-device copies no test covers.
-    // Checked before any HIP call.
-    bool distinct = true, all_same = true;
-    if (devices && n_ranks > 0) {
-        if (n_ranks > 64) return fail(RT_ERR_INVALID, "rt_multi_create: at most 64 ranks");
-        for (int r = 1; r < n_ranks; ++r) {
-            all_same = all_same && devices[r] == devices[0];
-            for (int q = 0; q < r; ++q) distinct = distinct && devices[q] != devices[r];
-        }
-        if (!distinct && !all_same)
-            return fail(RT_ERR_INVALID, "rt_multi_create: devices must be all distinct or all rank 0's device");
-    }
-    const bool standin = (opt.diag & RT_DIAG_STANDIN_TRANSPORT) != 0u;
-    if (standin && !(devices && n_ranks > 1 && all_same))
-        return fail(RT_ERR_INVALID, "rt_multi_create: the stand-in transport needs two or more ranks on one device");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RT_ERR_DEVICE, "rt_multi_create: no HIP device");
-    const int N = n_ranks <= 0 ? ndev : n_ranks;
-    if (!devices && N > ndev) return fail(RT_ERR_INVALID, "rt_multi_create: more ranks than devices (pass a device list)");
-    if (N > 64) return fail(RT_ERR_INVALID, "rt_multi_create: at most 64 ranks");
-    for (int r = 0; r < N; ++r) {
-        const int d = devices ? devices[r] : r;
-        if (d < 0 || d >= ndev) return fail(RT_ERR_INVALID, "rt_multi_create: bad device index");
-    }
-    rt_multi *m = new rt_multi();
-    m->n = N;
-    for (int r = 0; r < N; ++r) m->dev.push_back(devices ? devices[r] : r);
-    m->rccl = N > 1 && (distinct || standin);
-    m->api = standin ? &standin_api() : &rccl();
-    m->sc.assign(N, nullptr);
-    m->st.assign(N, nullptr);
-    m->tile.assign(N, nullptr);
-    m->tile_bytes.assign(N, 0);
-    m->tile8.assign(N, nullptr);
-    m->tile8_bytes.assign(N, 0);
-    m->seg.assign(N, nullptr);
-    m->ev_ready.assign(N, nullptr);
-    int rc = RT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-        return rc == RT_OK;
-    };
-    for (int r = 0; r < N && rc == RT_OK; ++r) {
-        rc = rt_scene_create_ex(spheres, n_spheres, materials, n_materials, m->dev[r], &opt, &m->sc[r]);
-        if (rc != RT_OK) break;
-        chk(hipSetDevice(m->dev[r]), "hipSetDevice");
-        if (r > 0) chk(hipStreamCreateWithFlags(&m->st[r], hipStreamNonBlocking), "hipStreamCreate");
-        chk(hipMalloc((void **)&m->seg[r], 3 * sizeof(uint64_t)), "hipMalloc");
-        chk(hipMemset(m->seg[r], 0, 3 * sizeof(uint64_t)), "hipMemset");
-        chk(hipEventCreateWithFlags(&m->ev_ready[r], hipEventDisableTiming), "hipEventCreate");
-    }
-    if (rc == RT_OK) {
-        chk(hipSetDevice(m->dev[0]), "hipSetDevice");
-        chk(hipEventCreateWithFlags(&m->ev_copied, hipEventDisableTiming), "hipEventCreate");
-        chk(hipEventCreate(&m->ev_t0), "hipEventCreate");
-        chk(hipEventCreate(&m->ev_t1), "hipEventCreate");
-    }
-    if (rc == RT_OK && m->rccl) {
-        const rccl_api &api = *m->api;
-        if (!api.ok) {
-            rc = fail(RT_ERR_COMM, "rt_multi_create: librccl.so.1 not loadable");
-        } else {
-            m->comm.assign(N, nullptr);
-            const ncclResult_t nr = api.comm_init_all(m->comm.data(), N, m->dev.data());
-            if (nr != ncclSuccess) {
-                m->comm.clear();
-                rc = fail(RT_ERR_COMM, std::string("ncclCommInitAll: ") + api.error_string(nr));
-            }
-        }
-    }
-    if (rc != RT_OK) return multi_fail_destroy(m, rc);
-    (void)hipSetDevice(m->dev[0]);
-    *out = m;
-    return RT_OK;
-}
-
-int rt_multi_destroy(rt_multi *m)
-{
-    if (!m) return RT_OK;
-    for (int r = 0; r < m->n; ++r) {
-        (void)hipSetDevice(m->dev[r]);
-        if (m->st[r]) (void)hipStreamSynchronize(m->st[r]);
-    }
-    (void)hipSetDevice(m->dev[0]);
-    (void)hipDeviceSynchronize();
-    for (auto c : m->comm)
-        if (c) m->api->comm_destroy(c);
-    for (int r = 0; r < m->n; ++r) {
-        (void)hipSetDevice(m->dev[r]);
-        if (m->tile[r]) (void)hipFree(m->tile[r]);
-        if (m->tile8[r]) (void)hipFree(m->tile8[r]);
-        if (m->seg[r]) (void)hipFree(m->seg[r]);
-        if (m->ev_ready[r]) (void)hipEventDestroy(m->ev_ready[r]);
-        if (m->st[r]) (void)hipStreamDestroy(m->st[r]);
-        if (m->sc[r]) rt_scene_destroy(m->sc[r]);
-    }
-    (void)hipSetDevice(m->dev[0]);
-    if (m->gather) (void)hipFree(m->gather);
-    for (hipEvent_t e : {m->ev_copied, m->ev_t0, m->ev_t1})
-        if (e) (void)hipEventDestroy(e);
-    delete m;
-    return RT_OK;
-}
-
-int rt_multi_info(const rt_multi *m, int *n_ranks, int *uses_rccl)
-{
-    if (!m) return fail(RT_ERR_INVALID, "rt_multi_info: null context");
-    if (n_ranks) *n_ranks = m->n;
-    if (uses_rccl) *uses_rccl = m->rccl ? 1 : 0;
-    return RT_OK;
-}
-
-int rt_multi_render_device(rt_multi *m, const rt_camera *camera, const rt_params *params, uint32_t format,
-                           void *d_out, void *stream)
-{
-    if (!m || !camera || !d_out) return fail(RT_ERR_INVALID, "rt_multi_render_device: null argument");
-    if (format != RT_OUTPUT_F32 && format != RT_OUTPUT_RGB8) return fail(RT_ERR_INVALID, "rt_multi_render_device: bad format");
-    if (int rc = check_params(params); rc != RT_OK) return rc;
-    const rt_params base = *params;
-    const int N = m->n;
-    const uint32_t W = base.width, H = base.height;
-    const size_t es = format == RT_OUTPUT_F32 ? 4u : 1u;
-    const size_t row_vals = static_cast<size_t>(W) * 3u;
-    const uint32_t rows_max = multi_rows(H, N, 0);
-    hipStream_t cs = static_cast<hipStream_t>(stream);
-    // buffers (grow only: a new, larger frame size costs one synchronisation)
-    for (int r = 0; r < N; ++r) {
-        const size_t rows = multi_rows(H, N, r);
-        if (int rc = grow(m->dev[r], &m->tile[r], &m->tile_bytes[r], std::max<size_t>(rows, 1) * row_vals * 4u); rc) return rc;
-        if (format == RT_OUTPUT_RGB8)
-            if (int rc = grow(m->dev[r], &m->tile8[r], &m->tile8_bytes[r], std::max<size_t>(rows, 1) * row_vals); rc) return rc;
-    }
-    if (N > 1)
-        if (int rc = grow(m->dev[0], &m->gather, &m->gather_bytes, static_cast<size_t>(N) * rows_max * row_vals * es); rc)
-            return rc;
-    auto tile_of = [&](int r) -> void * { return format == RT_OUTPUT_F32 ? m->tile[r] : m->tile8[r]; };
-    // 1. every rank renders its rows (rank 0 on the caller's stream); virtual ranks wait until
-    //    the caller stream has copied their previous tile out
-    for (int r = 0; r < N; ++r) {
-        const uint32_t rows = multi_rows(H, N, r);
-        if (!rows) continue;
-        rt_params p = base;
-        p.row_offset = static_cast<uint32_t>(r);
-        p.row_stride = static_cast<uint32_t>(N);
-        p.num_rows = rows;
-        p.flags &= ~static_cast<uint32_t>(RT_FLAG_FULL_FRAME);
-        hipStream_t rs = r == 0 ? cs : m->st[r];
-        RT_HIP(hipSetDevice(m->dev[r]));
-        if (r > 0 && !m->rccl && m->copied_valid) RT_HIP(hipStreamWaitEvent(rs, m->ev_copied, 0));
-        if (int rc = rt_render_device(m->sc[r], camera, &p, static_cast<float *>(m->tile[r]), rs, m->seg[r]); rc) return rc;
-        if (format == RT_OUTPUT_RGB8)
-            RT_HIP(rt::launch_epilogue(static_cast<const float *>(m->tile[r]), static_cast<uint8_t *>(m->tile8[r]),
-                                       static_cast<uint64_t>(rows) * row_vals, rs));
-        if (r > 0 && !m->rccl) RT_HIP(hipEventRecord(m->ev_ready[r], rs));
-    }
-    // 2. the gather: tile r -> slot r of the gather buffer on rank 0's device
-    const size_t slot_bytes = static_cast<size_t>(rows_max) * row_vals * es;
-    if (N > 1 && m->rccl) {
-        const rccl_api &api = *m->api;
-        ncclResult_t nr = api.group_start();
-        for (int r = 1; r < N && nr == ncclSuccess; ++r) {
-            const size_t cnt = static_cast<size_t>(multi_rows(H, N, r)) * row_vals;
-            if (!cnt) continue;
-            const ncclDataType_t ty = format == RT_OUTPUT_F32 ? ncclFloat : ncclUint8;
-            nr = api.send(tile_of(r), cnt, ty, 0, m->comm[r], m->st[r]);
-            if (nr == ncclSuccess)
-                nr = api.recv(static_cast<char *>(m->gather) + r * slot_bytes, cnt, ty, r, m->comm[0], cs);
-        }
-        const ncclResult_t ne = api.group_end();
-        if (nr == ncclSuccess) nr = ne;
-        if (nr != ncclSuccess) return fail(RT_ERR_COMM, std::string("RCCL gather: ") + api.error_string(nr));
-    } else if (N > 1) {
-        RT_HIP(hipSetDevice(m->dev[0]));
-        for (int r = 1; r < N; ++r) {
-            const size_t bytes = static_cast<size_t>(multi_rows(H, N, r)) * row_vals * es;
-            if (!bytes) continue;
-            RT_HIP(hipStreamWaitEvent(cs, m->ev_ready[r], 0));
-            RT_HIP(hipMemcpyAsync(static_cast<char *>(m->gather) + r * slot_bytes, tile_of(r), bytes,
-                                  hipMemcpyDeviceToDevice, cs));
-        }
-        RT_HIP(hipEventRecord(m->ev_copied, cs));
-        m->copied_valid = true;
-    }
-    // 3. de-interleave on rank 0's device: frame row r + i N <- tile r row i
-    RT_HIP(hipSetDevice(m->dev[0]));
-    const size_t row_bytes = row_vals * es;
-    for (int r = 0; r < N; ++r) {
-        const uint32_t rows = multi_rows(H, N, r);
-        if (!rows) continue;
-        const void *src = r == 0 ? tile_of(0) : static_cast<const void *>(static_cast<char *>(m->gather) + r * slot_bytes);
-        RT_HIP(hipMemcpy2DAsync(static_cast<char *>(d_out) + r * row_bytes, row_bytes * N, src, row_bytes, row_bytes,
-                                rows, hipMemcpyDeviceToDevice, cs));
-    }
-    return RT_OK;
-}
-
-} // extern "C"
-
-namespace {
-
-int multi_fail_destroy(rt_multi *m, int rc)
-{
-    const std::string msg = g_error;
-    rt_multi_destroy(m);
-    g_error = msg;
-    return rc;
-}
-
-// Synchronous host-buffer frame through a context: every rank's counters are zeroed, the frame
-// is enqueued on an internal stream of rank 0's device, copied to `out` and timed.
-int multi_render_host(rt_multi *m, const rt_camera *camera, const rt_params *params, uint32_t format, void *out,
-                      rt_stats *stats)
-{
-    if (!m || !camera || !out) return fail(RT_ERR_INVALID, "rt_multi_render: null argument");
-    if (int rc = check_params(params); rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t es = format == RT_OUTPUT_F32 ? 4u : 1u;
-    const size_t bytes = static_cast<size_t>(params->width) * params->height * 3u * es;
-    for (int r = 0; r < m->n; ++r) {
-        RT_HIP(hipSetDevice(m->dev[r]));
-        RT_HIP(hipMemset(m->seg[r], 0, 3 * sizeof(uint64_t)));
-    }
-    RT_HIP(hipSetDevice(m->dev[0]));
-    void *d_out = nullptr;
-    hipStream_t cs = nullptr;
-    RT_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    int rc = RT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-        return rc == RT_OK;
-    };
-    chk(hipMalloc(&d_out, bytes), "hipMalloc");
-    if (rc == RT_OK) chk(hipEventRecord(m->ev_t0, cs), "hipEventRecord");
-    if (rc == RT_OK) rc = rt_multi_render_device(m, camera, params, format, d_out, cs);
-    (void)hipSetDevice(m->dev[0]);
-    if (rc == RT_OK) chk(hipEventRecord(m->ev_t1, cs), "hipEventRecord");
-    if (rc == RT_OK) chk(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
-    for (int r = 0; r < m->n; ++r) {
-        (void)hipSetDevice(m->dev[r]);
-        if (m->st[r]) chk(hipStreamSynchronize(m->st[r]), "hipStreamSynchronize");
-    }
-    (void)hipSetDevice(m->dev[0]);
-    chk(hipStreamSynchronize(cs), "hipStreamSynchronize");
-    uint64_t segs[3] = {0, 0, 0};
-    for (int r = 0; r < m->n && rc == RT_OK; ++r) {
-        uint64_t v[3];
-        (void)hipSetDevice(m->dev[r]);
-        chk(hipMemcpy(v, m->seg[r], sizeof v, hipMemcpyDeviceToHost), "hipMemcpy");
-        for (int i = 0; i < 3; ++i) segs[i] += v[i];
-    }
-    (void)hipSetDevice(m->dev[0]);
-    float ms = 0.f;
-    if (rc == RT_OK) chk(hipEventElapsedTime(&ms, m->ev_t0, m->ev_t1), "hipEventElapsedTime");
-    if (d_out) (void)hipFree(d_out);
-    (void)hipStreamDestroy(cs);
-    if (rc == RT_OK && stats) {
-        stats->primaries = static_cast<uint64_t>(params->width) * params->height * params->spp;
-        stats->segments = segs[0];
-        stats->sphere_tests = segs[1];
-        stats->box_tests = segs[2];
-        stats->kernel_ms = ms;
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return rc;
-}
-
-int render_multi_once(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
-                      const rt_camera *camera, const rt_params *params, int ngpu, uint32_t format, void *out,
-                      rt_stats *stats)
-{
-    if (!camera || !out) return fail(RT_ERR_INVALID, "rt_render_multi: null argument");
-    if (int rc = check_params(params); rc != RT_OK) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RT_ERR_DEVICE, "rt_render_multi: no HIP device");
-    rt_multi *m = nullptr;
-    if (int rc = rt_multi_create(spheres, n_spheres, materials, n_materials, nullptr,
-                                 ngpu <= 0 ? ndev : std::min(ngpu, ndev), &m); rc)
-        return rc;
-    const int rc = multi_render_host(m, camera, params, format, out, stats);
-    const std::string msg = g_error;
-    rt_multi_destroy(m);
-    g_error = msg;
-    return rc;
-}
-
-} // namespace
-
-extern "C" {
-
-int rt_multi_render_f32(rt_multi *m, const rt_camera *camera, const rt_params *params, float *rgb_out, rt_stats *stats)
-{
-    return multi_render_host(m, camera, params, RT_OUTPUT_F32, rgb_out, stats);
-}
-
-int rt_multi_render_rgb8(rt_multi *m, const rt_camera *camera, const rt_params *params, uint8_t *rgb_out,
-                         rt_stats *stats)
-{
-    return multi_render_host(m, camera, params, RT_OUTPUT_RGB8, rgb_out, stats);
-}
-
-int rt_render_multi_f32(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
-                        uint32_t n_materials, const rt_camera *camera, const rt_params *params, int ngpu,
-                        float *rgb_out, rt_stats *stats)
-{
-    return render_multi_once(spheres, n_spheres, materials, n_materials, camera, params, ngpu, RT_OUTPUT_F32, rgb_out,
-                             stats);
-}
-
-int rt_render_multi_rgb8(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
-                         uint32_t n_materials, const rt_camera *camera, const rt_params *params, int ngpu,
-                         uint8_t *rgb_out, rt_stats *stats)
-{
-    return render_multi_once(spheres, n_spheres, materials, n_materials, camera, params, ngpu, RT_OUTPUT_RGB8, rgb_out,
-                             stats);
-}
-
 
 } // extern "C"

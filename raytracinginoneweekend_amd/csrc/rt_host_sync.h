@@ -1,7 +1,8 @@
-// rt_host_sync.h — what the device half's two files share (rt_host.cpp: scenes, renders, the
-// cached context; rt_host_post.cpp: the filters and temporal accumulation): the kernels'
-// launchers, the HIP error forms, and the one path every synchronous host-buffer entry point
-// takes through the cached per-device context (SyncCall, implemented in rt_host.cpp).
+// rt_host_sync.h — what the device half's three files share (rt_host.cpp: scenes, renders, the
+// cached context; rt_host_post.cpp: the filters and temporal accumulation; rt_host_multi.cpp: the
+// multi-GPU context): the kernels' launchers, the HIP error forms, the params check, and the one
+// path every synchronous host-buffer entry point takes through the cached per-device context
+// (SyncCall, implemented in rt_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,6 +65,9 @@ inline int hip_rc(hipError_t e, const char *what)
 
 // The device a scene was created on (rt_scene is rt_host.cpp's own record).
 int scene_device(const rt_scene *sc);
+
+// The params of a render call, decided before any HIP call (rt_host.cpp).
+int check_params(const rt_params *p);
 
 // The scene of a synchronous render: the context keeps its device scene between calls.
 struct SyncScene {

@@ -5,6 +5,5 @@ set -eu
 cd "$(dirname "$0")/../raytracinginoneweekend_amd/csrc"
 name=$1; shift
 mkdir -p ../../scripts/_abl/$name
-make -s OBJ=_obj_abl/$name OUT=../../scripts/_abl/$name/librt_mi355x.so \
-     FLAGS="-std=c++17 -O3 -fno-slp-vectorize --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fPIC -Wall $*"
+make -s OBJ=_obj_abl/$name OUT=../../scripts/_abl/$name/librt_mi355x.so DEFS="$*"
 echo "built scripts/_abl/$name/librt_mi355x.so ($*)"

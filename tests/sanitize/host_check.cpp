@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY (tests/test_sanitize_cpu.py): drives the host-only half of the
-// library (raytracinginoneweekend_amd/csrc/rt_host_build.cpp, compiled from the same source
+// library (raytracinginoneweekend_amd/csrc/rt_host_build.cpp and rt_plan.cpp, compiled from the same source
 // with -fsanitize=address,undefined or -fsanitize=thread by tests/sanitize/Makefile) and the CPU
 // restatement (oracle/rt_oracle.cpp) through their real inputs, and checks the results against
 // the reference's fixtures in tests/golden. Any sanitizer report fails the run (halt on error).
@@ -7,7 +7,8 @@
 //   host_check host <golden dir>        scene generators vs the reference's scene dumps, camera
 //                                       vs the restatement, cluster/neighbour-list builder on the
 //                                       huge scene and adversarial scenes, exact-division checks,
-//                                       the synchronous calls' plane layout, options parser (fixed and random strings), PPM writer
+//                                       the synchronous calls' plane layout, the pass planner's cuts,
+//                                       options parser (fixed and random strings), PPM writer
 //   host_check render <scene.bin> <golden.f32> W H spp depth seed row0 stride rows mode threads
 //                                       the restatement's render vs a golden frame, bit for bit
 //   host_check threads <scene.bin>      (TSan) the restatement on 1 and 4 threads, the exact-division
@@ -27,6 +28,7 @@
 #include <unistd.h>
 
 #include "../../raytracinginoneweekend_amd/csrc/rt_host_build.h"
+#include "../../raytracinginoneweekend_amd/csrc/rt_plan.h"
 
 extern "C" {
 int oracle_render_f32(const rt_sphere *, uint32_t, const rt_material *, uint32_t, const rt_camera *, const rt_params *,
@@ -301,6 +303,180 @@ void check_options()
     CHECK(rt_set_default_options(&o) == RT_ERR_INVALID);
 }
 
+// The pass planner (rt_plan.cpp) against its documented rules (the comments there, DESIGN.md §4.2
+// and §4.14), none of them taken from its own output.
+void check_plans()
+{
+    using rthost::Plan;
+    using rthost::PlanInput;
+    const rt_options D = rthost::library_defaults();
+    auto input = [&](uint64_t n_pixels, uint32_t spp, uint32_t streams, uint32_t wsps) {
+        return PlanInput{n_pixels, spp, streams, wsps, D.max_pass_bytes, 0, D.ring_pass_bytes, D.wave_queue_rays,
+                         false, false, true, false, true};
+    };
+    // ring passes: the frame's samples in equal passes of a multiple of 4 within ring_pass_bytes,
+    // at least 32; the frame issued alone then runs whole in a workspace of its own
+    {
+        const uint64_t per_sample = 160u * 90u * 12u;
+        const struct { uint64_t ring; uint64_t pass; bool lone; } cases[] = {{40, 32, true}, {64, 48, true}, {28, 96, false}};
+        for (const auto &c : cases) {
+            PlanInput in = input(160u * 90u, 96, 3, 2);
+            in.ring_pass_bytes = c.ring * per_sample;
+            Plan pl{};
+            CHECK(rthost::plan_frame(in, pl) == RT_OK);
+            CHECK(pl.ring_samples == c.pass && pl.lone_samples == 96u && pl.streams == 3u && pl.n_ws == 6u);
+            CHECK(pl.has_lone() == c.lone && pl.whole == c.lone && !pl.pairs && !pl.ring_pairs);
+            CHECK(pl.pass_samples(0) == c.pass && pl.slot_bytes(5) == c.pass * per_sample);
+            if (c.lone) CHECK(pl.lone_ws == 6u && pl.pass_samples(6) == 96u && pl.slot_bytes(6) == 96u * per_sample);
+        }
+        // the defaults at config 3 with 7 streams: a 384 MiB ring holds 36 samples, 128 in 4 passes of 32
+        CHECK(D.ring_pass_bytes == (384ull << 20) && D.workspaces_per_stream == 2u);
+        Plan pl{};
+        CHECK(rthost::plan_frame(input(1280u * 720u, 128, 7, D.workspaces_per_stream), pl) == RT_OK);
+        CHECK(pl.ring_samples == 32u && pl.n_ws == 14u && pl.has_lone() && pl.lone_ws == 14u && pl.whole && pl.lone_samples == 128u);
+    }
+    // the cap: one workspace per stream first, then pairs, then shorter passes, then fewer streams
+    auto deep_bytes = [](uint64_t n_pixels, uint64_t samples) {  // 8 regions of 1/1024 of the samples, at least 512, 60 B each
+        return ((n_pixels + 255u) & ~255ull) + 8u * std::max<uint64_t>(512u, n_pixels * samples / 1024u) * 60u;
+    };
+    // slot rows of samples [a, b) by counting: a full block of 4 below spp & ~3 takes 2 rows as pairs, every other sample 1
+    auto count_rows = [](uint32_t spp, uint32_t a, uint32_t b, bool paired) {
+        uint64_t rows = 0;
+        uint32_t s = a;
+        if (paired)
+            for (; s + 4u <= b && s + 4u <= (spp & ~3u); s += 4u) rows += 2u;
+        return rows + (b - s);
+    };
+    // the largest pass of the frame cut into passes of `pass` samples
+    auto most_rows = [&](uint32_t spp, uint64_t pass, bool paired) {
+        uint64_t m = 0;
+        for (uint64_t a = 0; a < spp; a += pass)
+            m = std::max(m, count_rows(spp, static_cast<uint32_t>(a), static_cast<uint32_t>(std::min<uint64_t>(spp, a + pass)), paired));
+        return m;
+    };
+    // The footprint of a cut from its fields alone, by the documented rules: the ring's workspaces
+    // (12 B per slot row and pixel, and a deep queue when the passes may be split), the lone
+    // passes' workspace of single samples (the whole frame, or a ring pass when the ring holds
+    // pairs), the multi-pass sums (and moments), and the wavefront variant's two ray queues of
+    // 52 B a ray with their counters.
+    auto footprint_by_rules = [&](const PlanInput &in, const Plan &pl) {
+        const uint64_t per_sample = in.n_pixels * 12u;
+        auto workspace = [&](uint64_t samples, bool paired) {
+            return most_rows(in.spp, samples, paired) * per_sample + (in.may_split ? deep_bytes(in.n_pixels, samples) : 0u);
+        };
+        const uint64_t n_ws = pl.streams > 1u ? pl.streams * pl.wsps : 1u;
+        const bool ring_pairs = pl.pairs && pl.streams > 1u;
+        uint64_t t = n_ws * workspace(pl.ring_samples, ring_pairs);
+        if (pl.whole) t += workspace(pl.lone_samples, false);
+        else if (ring_pairs) t += workspace(pl.ring_samples, false);
+        if (pl.ring_samples < in.spp) t += (in.moments ? 2u : 1u) * per_sample;
+        if (in.wave) t += 2u * std::min<uint64_t>(in.n_pixels * pl.lone_samples, in.wave_queue_rays) * 52u + 512u;
+        return t;
+    };
+    // Every combination of the five flags, also those choose_kernel never produces (pairs with the
+    // variance render; the wavefront variant with streams, pairs or a deep queue): the rules do
+    // not depend on which combinations are reachable.
+    int plans = 0, refused = 0, wholes = 0;
+    for (uint64_t n_pixels : {64u, 2304u, 14400u})
+        for (uint32_t spp : {1u, 3u, 4u, 7u, 16u, 64u, 96u, 130u})
+            for (uint32_t streams : {1u, 3u, 7u})
+                for (uint32_t wsps : {1u, 2u})
+                    for (uint32_t flags = 0; flags < 64u; ++flags) {
+                        PlanInput in = input(n_pixels, spp, streams, wsps);
+                        in.moments = flags & 1u;
+                        in.pairs_ok = flags & 2u;
+                        in.pairs_forced = flags & 4u;
+                        in.may_split = flags & 8u;
+                        in.wave = flags & 16u;
+                        // with and without ring passes (32 samples: the frames of 64 and more then run
+                        // whole in a workspace of their own when issued alone)
+                        if (flags & 32u) in.ring_pass_bytes = 32u * n_pixels * 12u;
+                        const uint64_t per_sample = n_pixels * 12u, s4 = std::min(4u, spp);
+                        const uint64_t dq4 = in.may_split ? deep_bytes(n_pixels, s4) : 0u;
+                        const uint64_t sums = spp > 4u ? (in.moments ? 2u : 1u) * per_sample : 0u;
+                        const uint64_t wave4 = in.wave ? 2u * std::min<uint64_t>(n_pixels * s4, in.wave_queue_rays) * 52u + 512u : 0u;
+                        // one stream, one workspace, 4-sample passes of single samples
+                        const uint64_t fp4 = s4 * per_sample + dq4 + sums + wave4;
+                        for (uint64_t cap : {uint64_t(0), uint64_t(1), fp4 / 2u, fp4 - 1u, fp4, fp4 + 1u, 2u * fp4, 3u * fp4 + per_sample,
+                                             5u * fp4, 8u * fp4, 13u * fp4, 21u * fp4, 40u * fp4, 100u * fp4}) {
+                            in.max_workspace_bytes = cap;
+                            Plan pl{};
+                            const int rc = rthost::plan_frame(in, pl);
+                            if (cap && fp4 > cap) {
+                                CHECK(rc == RT_ERR_CAPACITY);
+                                ++refused;
+                                continue;
+                            }
+                            CHECK(rc == RT_OK);
+                            if (rc != RT_OK) continue;
+                            ++plans;
+                            CHECK(pl.ring_samples <= pl.lone_samples && pl.lone_samples <= spp && pl.ring_samples >= 1u);
+                            if (pl.ring_samples < spp) CHECK(pl.ring_samples % 4u == 0u);
+                            if (pl.lone_samples < spp) CHECK(pl.lone_samples % 4u == 0u);
+                            CHECK(pl.streams >= 1u && pl.streams <= in.streams && pl.wsps >= 1u && pl.wsps <= wsps);
+                            CHECK(pl.n_ws == (pl.streams > 1u ? pl.streams * pl.wsps : 1u));
+                            CHECK(!pl.pairs || in.pairs_ok);
+                            CHECK(pl.ring_pairs == (pl.pairs && pl.streams > 1u));
+                            if (in.pairs_ok && in.pairs_forced) CHECK(pl.pairs);
+                            CHECK(pl.has_lone() == (pl.ring_pairs || pl.whole) && (!pl.has_lone() || pl.lone_ws == pl.n_ws));
+                            // a whole lone frame only beside a ring of smaller passes
+                            wholes += pl.whole;
+                            if (pl.whole) CHECK(pl.streams > 1u && pl.lone_samples == spp && pl.ring_samples < spp);
+                            const uint64_t by_rules = footprint_by_rules(in, pl);
+                            if (cap) CHECK(by_rules <= cap);
+                            CHECK(pl.footprint() == by_rules);
+                            if (!cap) CHECK(pl.streams == in.streams && pl.wsps == wsps && pl.lone_samples == spp);
+                            // pairs under the cap only after one workspace per stream
+                            if (pl.pairs && !in.pairs_forced && pl.streams > 1u) CHECK(pl.wsps == 1u);
+                            // shorter passes only after one workspace per stream and pairs
+                            if (cap && pl.streams > 1u && pl.lone_samples < spp) CHECK(pl.wsps == 1u && (!in.pairs_ok || pl.pairs));
+                            // fewer streams only when one more, at one workspace each, with pairs and
+                            // 4-sample passes, does not fit
+                            if (pl.streams < in.streams) {
+                                const uint64_t S = pl.streams + 1u;
+                                const uint64_t ring_rows = !in.pairs_ok ? s4 : spp >= 4u ? std::max<uint64_t>(2u, spp % 4u) : spp;
+                                const uint64_t need = S * (ring_rows * per_sample + dq4) + (in.pairs_ok ? s4 * per_sample + dq4 : 0u) + sums + wave4;
+                                CHECK(need > cap);
+                            }
+                        }
+                    }
+    CHECK(plans > 10000 && refused > 1000 && wholes > 1000);
+    {  // the two failures' texts
+        PlanInput in = input((1ull << 31) - 1u, 1, 3, 2);
+        Plan pl{};
+        CHECK(rthost::plan_frame(in, pl) == RT_ERR_INVALID);
+        CHECK(std::string(rt_last_error()) == "rt_render_device: too many pixels in one call");
+        in = input(2304, 16, 3, 2);
+        in.max_workspace_bytes = 1000;
+        CHECK(rthost::plan_frame(in, pl) == RT_ERR_CAPACITY);
+        const uint64_t fp4 = 4u * 2304u * 12u + deep_bytes(2304, 4) + 2304u * 12u;
+        CHECK(std::string(rt_last_error()) == "rt_render_device: max_workspace_bytes 1000 below one 4-sample pass of this frame (" +
+                                                  std::to_string(fp4) + " bytes)");
+    }
+    // slot rows: each full block of 4 samples below spp & ~3 takes 2 rows as pairs, every other sample 1
+    for (uint32_t spp = 1; spp <= 23u; ++spp) {
+        Plan pl{};
+        CHECK(rthost::plan_frame(input(64, spp, 1, 1), pl) == RT_OK);
+        for (uint32_t a = 0; a <= spp; a += 4u)
+            for (uint32_t b = a; b <= spp; ++b) {
+                CHECK(pl.slot_rows(a, b, true) == count_rows(spp, a, b, true));
+                CHECK(pl.slot_rows(a, b, false) == b - a);
+            }
+    }
+    // the grid of a launch: occupancy 6 with 3 streams: 3 in flight, 6 alone; 4 streams and a short pass: a third
+    CHECK(rthost::grid_wg_per_cu(6, true, 3, 1u << 20) == 3 && rthost::grid_wg_per_cu(6, true, 3, 1ull << 30) == 3);
+    CHECK(rthost::grid_wg_per_cu(6, false, 3, 1u << 20) == 6);
+    CHECK(rthost::grid_wg_per_cu(6, true, 4, rthost::kShortPassItems) == 2 && rthost::grid_wg_per_cu(6, true, 4, rthost::kShortPassItems + 1u) == 3);
+    CHECK(rthost::grid_wg_per_cu(1, true, 7, 1) == 1 && rthost::grid_wg_per_cu(5, true, 1, 1) == 5);
+    // the deep queue: 8 regions of 1/1024 of the samples, never below 512 entries, 60 B an entry,
+    // after one flag byte per pixel rounded up to 256
+    CHECK(rthost::deep_region_cap(0) == 512u && rthost::deep_region_cap(1000) == 512u && rthost::deep_region_cap(1024u * 512u) == 512u);
+    CHECK(rthost::deep_region_cap(1024u * 513u) == 513u && rthost::deep_region_cap(1280ull * 720u * 128u) == 115200u);
+    CHECK(rthost::deep_px_bytes(2304) == 2304u && rthost::deep_px_bytes(2590) == 2816u && rthost::deep_px_bytes(1) == 256u);
+    CHECK(rthost::deep_queue_bytes(2304, 2304u * 16u) == 2304u + 8u * 512u * 60u);
+    CHECK(rthost::guided_l2b(1024, true) < 0.f && rthost::guided_l2b(1024, false) > rthost::guided_l2b(1024, true));
+}
+
 void check_ppm(const std::string &golden)
 {
     const std::vector<char> ref = read_file(golden + "/c1_simple_200x100_s1.ppm");
@@ -391,6 +567,7 @@ int main(int argc, char **argv)
         check_tiles(golden);
         check_divisions();
         check_plane_layout();
+        check_plans();
         check_options();
         check_ppm(golden);
         std::printf("host_check host: %s (%d failed checks)\n", g_fail ? "FAIL" : "ok", g_fail);
