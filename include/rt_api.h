@@ -638,6 +638,77 @@ int rt_temporal_device(const rt_temporal_params *params, const rt_camera *camera
 int rt_temporal(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
                 const rt_temporal_buffers *buffers, rt_stats *stats);
 
+/* ---- guided upsampling of a low-resolution frame ---------------------------------
+ * The stage that brings a filtered image of lo_width x lo_height up to width x height: a joint-
+ * bilateral upsample (Kopf et al. 2007) whose four bilinear taps are tested against first-hit guides
+ * of the output size with the temporal stage's consistency tests. Both sets of guides are what
+ * rt_render_aov writes for the same camera at the two sizes. Depth is t in units of the un-normalised
+ * ray direction, and that direction is a function of (u, v) alone, so depths of the two sizes compare
+ * directly: the stage takes no camera. All arithmetic is binary32, every operation rounded on its
+ * own, in the order written; divisions are IEEE divisions.
+ *
+ * Planes are packed row-major, pitch = their width. Low resolution, lw x lh: lo_color[lh][lw][3]
+ * (required), lo_variance[lh][lw] (given iff out_variance is), lo_normal[lh][lw][3], lo_depth[lh][lw],
+ * lo_sphere_id[lh][lw] (required). Output size, w x h, all required: normal[h][w][3], depth[h][w],
+ * alpha[h][w], sphere_id[h][w]. Outputs: out_color[h][w][3] (required), out_variance[h][w] (optional).
+ *
+ * Per output pixel p = (x, y):
+ *   1 position  px = (((float)x + 0.5f) / (float)w) * (float)lw - 0.5f
+ *               py = (((float)y + 0.5f) / (float)h) * (float)lh - 0.5f
+ *               fx = floorf(px), tx = px - fx, ix = (int)fx; fy, ty, iy likewise. For sides up to
+ *               65536 and lw <= w, lh <= h this gives ix in [-1, lw - 1] and iy in [-1, lh - 1]
+ *               ((x + 0.5) / w lies in (0, 1) after rounding too, since x + 0.5 is exact and below w);
+ *               the in-image test is made on every tap regardless
+ *   2 class     surface iff alpha(p) == 1.0f. Sky pixels and edge pixels take the id test only
+ *   3 taps      t = (ix + i, iy + j), j = 0, 1 (outer loop), i = 0, 1 (inner loop), with
+ *               wgt = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty). A tap outside the low-resolution
+ *               image is skipped for both sets of sums. From pw = ps[3] = pv = 0 (the plain sums):
+ *               pw = pw + wgt;  ps[c] = ps[c] + wgt * lo_color(t)[c]
+ *               pv = pv + (wgt * wgt) * lo_variance(t)
+ *               The guided sums gw, gs[3], gv are formed the same way from 0, but the tap is skipped
+ *               when lo_sphere_id(t) != sphere_id(p), or, for a surface pixel, d2 > normal_tol with
+ *               dn = lo_normal(t) - normal(p) per component and d2 = (dn.x dn.x + dn.y dn.y) + dn.z dn.z,
+ *               or, for a surface pixel, fabsf(lo_depth(t) - depth(p)) > depth_tol * depth(p)
+ *   4 result    gw >= 0.01f: out_color(p)[c] = gs[c] / gw, out_variance(p) = gv / (gw * gw) (the
+ *               variance of a weighted mean, as §4.10's levels and §4.11's resample). Otherwise the
+ *               plain bilinear value ps[c] / pw and pv / (pw * pw); pw >= 0.25, because the tap nearest
+ *               to (px, py) lies inside the image and both of its factors are at least 0.5
+ * NaN or infinite plane values give unspecified output values; no tap is read outside a plane whatever
+ * the values are.
+ *
+ * Every argument is checked before any HIP call; RT_ERR_INVALID names the field: a wrong size, a side
+ * outside 1..65536, lo_width > width or lo_height > height, a negative or non-finite tolerance,
+ * nonzero flags, a null required plane, lo_variance given without out_variance or the reverse, an
+ * output plane equal to an input plane or to the other output.                                        */
+typedef struct rt_upsample_params {
+    uint32_t size;                /* sizeof(rt_upsample_params): the record's revision (32 bytes)      */
+    uint32_t width, height;       /* the output's, 1..65536                                            */
+    uint32_t lo_width, lo_height; /* the low-resolution planes', 1..width, 1..height                   */
+    float normal_tol;             /* >= 0: the largest squared normal distance of a guided tap         */
+    float depth_tol;              /* >= 0: the largest relative depth difference of a guided tap       */
+    uint32_t flags;               /* none defined: must be 0                                           */
+} rt_upsample_params;
+typedef struct rt_upsample_buffers {
+    uint32_t size;                /* sizeof(rt_upsample_buffers)                                       */
+    const float *lo_color;        /* [lh][lw][3] required                                              */
+    const float *lo_variance;     /* [lh][lw]; given iff out_variance is                               */
+    const float *lo_normal, *lo_depth;
+    const uint32_t *lo_sphere_id; /* required                                                          */
+    const float *normal, *depth, *alpha;
+    const uint32_t *sphere_id;    /* [h][w], required                                                  */
+    float *out_color;             /* [h][w][3] required                                                */
+    float *out_variance;          /* [h][w] optional                                                   */
+} rt_upsample_buffers;
+/* The defaults (DESIGN.md §4.15 records the sweep that chose them). A zero side is RT_ERR_INVALID.   */
+int rt_upsample_params_default(uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height,
+                               rt_upsample_params *out);
+/* Device pointers on the current device; one launch on `stream` (a hipStream_t, or NULL), no host
+ * synchronisation, no allocation.                                                                     */
+int rt_upsample_device(const rt_upsample_params *params, const rt_upsample_buffers *buffers, void *stream);
+/* Host pointers, synchronous; the device planes are the library's (kept in the cached per-device
+ * context rt_release_cached frees). stats (optional): kernel_ms, wall_ms; the counters are 0.         */
+int rt_upsample(const rt_upsample_params *params, const rt_upsample_buffers *buffers, rt_stats *stats);
+
 /* ---- the preview session: the whole denoised-preview loop, one call per frame ----
  * A device-resident object beside the stage entry points above. It owns every plane of the loop
  * rt_render_var -> rt_render_aov -> rt_temporal -> rt_denoise_var -> epilogue and the prev / cur
@@ -720,7 +791,8 @@ int rt_preview_params_default(uint32_t width, uint32_t height, uint32_t spp, rt_
 /* Allocates every plane of the session on the scene's device (one allocation).                  */
 int rt_preview_create(rt_scene *scene, const rt_preview_params *p, rt_preview **out);
 /* Enqueue one frame. d_rgb: [height][width][3] floats (linear) or NULL; d_rgb8: [height][width][3]
- * bytes (gamma 1/2.2) or NULL; one of them must be given. A NULL camera is RT_ERR_INVALID.        */
+ * bytes (gamma 1/2.2) or NULL; one of them must be given (an upscaled session, below: both of its
+ * output size). A NULL camera is RT_ERR_INVALID.                                                   */
 int rt_preview_frame_device(rt_preview *pv, const rt_camera *camera, uint64_t seed, float *d_rgb, uint8_t *d_rgb8,
                             void *stream);
 /* The next frame has no history (as the first one). Nothing is enqueued.                          */
@@ -736,6 +808,46 @@ int rt_preview_split_device(uint32_t width, uint32_t height, const float *beauty
                             const float *albedo, float *illumination, float *variance_out, void *stream);
 int rt_preview_merge_device(uint32_t width, uint32_t height, const float *filtered, const float *albedo, float *d_rgb,
                             uint8_t *d_rgb8, void *stream);
+/* ---- the upscaled session: a render scale --------------------------------------
+ * A session whose frames are rendered, accumulated and filtered at `p`'s size and shown at a larger
+ * one. rt_preview_params keeps describing the render resolution; this record adds the output. A frame
+ * of such a session, all on the caller's stream, no host synchronisation, no allocation after creation:
+ *   1-4        steps 1 to 4 above exactly as an ordinary session of the same `p` enqueues them
+ *   5 guides   rt_render_aov_device with rt_params {out_width, out_height, p->spp, p->max_depth, seed,
+ *              every row, flags 0} and samples = guide_samples: normal, depth, alpha, sphere_id, and
+ *              albedo only under RT_PREVIEW_DEMODULATE
+ *   6 upsample rt_upsample_device's launch: lo_color the filter's output (the plane step 5 of an
+ *              ordinary session would have merged), the low-resolution guides the frame's, the
+ *              output-size guides step 5's, no variance
+ *   7 merge    preview_merge at the output size: under DEMODULATE out = upsampled * max(albedo, 2^-7)
+ *              with the output-size albedo (the low-resolution one served the split), the upsampled
+ *              bits otherwise; d_rgb and d_rgb8 are [out_height][out_width][3]
+ * rt_preview_planes keeps reporting the render-size planes, rt_preview_reset and the history (which
+ * lives at the render size) are untouched, rt_preview_usage counts the output-size planes (part of
+ * the one allocation). rt_preview_create_upscaled checks `p` as rt_preview_create does, then `u` field
+ * by field (RT_ERR_INVALID names it: a wrong size, out_width or out_height outside 1..65536 or below
+ * p's, a product of 2^31 or more, guide_samples above p->spp, a negative or non-finite tolerance),
+ * then the scene, all before any HIP call.                                                          */
+typedef struct rt_preview_upscale {
+    uint32_t size;                  /* sizeof(rt_preview_upscale)                                       */
+    uint32_t out_width, out_height; /* >= p->width, p->height; 1..65536, product below 2^31             */
+    uint32_t guide_samples;         /* samples of the output-size guide pass, 0 = p->spp, <= p->spp     */
+    float normal_tol, depth_tol;    /* rt_upsample_params'                                              */
+} rt_preview_upscale;
+/* out_width x out_height with guide_samples 0 and rt_upsample_params_default's tolerances.            */
+int rt_preview_upscale_default(const rt_preview_params *p, uint32_t out_width, uint32_t out_height,
+                               rt_preview_upscale *out);
+int rt_preview_create_upscaled(rt_scene *scene, const rt_preview_params *p, const rt_preview_upscale *u,
+                               rt_preview **out);
+/* What the last frame of an upscaled session wrote at the output size (device pointers, valid until
+ * the next frame call; NULL before the first one; albedo NULL without RT_PREVIEW_DEMODULATE).
+ * RT_ERR_INVALID on a session made by rt_preview_create.                                              */
+typedef struct rt_preview_output_t {
+    uint32_t size, width, height;   /* filled by the call                                               */
+    const float *upsampled, *albedo, *normal, *depth, *alpha;
+    const uint32_t *sphere_id;
+} rt_preview_output_t;
+int rt_preview_output(rt_preview *pv, rt_preview_output_t *out);
 
 /* Device memory a scene holds and how its renders are cut (after the last render call).  */
 typedef struct rt_scene_usage {

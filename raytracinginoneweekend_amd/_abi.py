@@ -161,6 +161,54 @@ class RtTemporalBuffers(C.Structure):
     _fields_ = [("size", C.c_uint32)] + [(n, C.c_void_p) for n in TEMPORAL_PLANES]
 
 
+class RtUpsampleParams(C.Structure):
+    """rt_upsample_params (include/rt_api.h): the guided upsample's two image sizes and tap tests."""
+    _fields_ = [
+        ("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+        ("lo_width", C.c_uint32), ("lo_height", C.c_uint32),
+        ("normal_tol", C.c_float), ("depth_tol", C.c_float), ("flags", C.c_uint32),
+    ]
+
+
+# the planes of rt_upsample_buffers, in the record's order: name -> (channels, numpy dtype); the lo_
+# planes have the low-resolution size, the others the output's
+UPSAMPLE_PLANES = {
+    "lo_color": (3, np.float32), "lo_variance": (1, np.float32), "lo_normal": (3, np.float32),
+    "lo_depth": (1, np.float32), "lo_sphere_id": (1, np.uint32),
+    "normal": (3, np.float32), "depth": (1, np.float32), "alpha": (1, np.float32), "sphere_id": (1, np.uint32),
+    "out_color": (3, np.float32), "out_variance": (1, np.float32),
+}
+
+
+class RtUpsampleBuffers(C.Structure):
+    """rt_upsample_buffers (include/rt_api.h): the low-resolution image and guides, the guides of the
+    output size and the outputs of a guided upsample."""
+    _fields_ = [("size", C.c_uint32)] + [(n, C.c_void_p) for n in UPSAMPLE_PLANES]
+
+
+class RtPreviewUpscale(C.Structure):
+    """rt_preview_upscale (include/rt_api.h): the output size, guide samples and tap tests of an
+    upscaled preview session."""
+    _fields_ = [
+        ("size", C.c_uint32), ("out_width", C.c_uint32), ("out_height", C.c_uint32), ("guide_samples", C.c_uint32),
+        ("normal_tol", C.c_float), ("depth_tol", C.c_float),
+    ]
+
+
+# the planes of rt_preview_output_t, in the record's order: name -> (channels, numpy dtype)
+PREVIEW_OUTPUT_PLANES = {
+    "upsampled": (3, np.float32), "albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32),
+    "alpha": (1, np.float32), "sphere_id": (1, np.uint32),
+}
+
+
+class RtPreviewOutput(C.Structure):
+    """rt_preview_output_t (include/rt_api.h): what an upscaled session's last frame wrote at the
+    output size."""
+    _fields_ = ([("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
+                + [(n, C.c_void_p) for n in PREVIEW_OUTPUT_PLANES])
+
+
 class RtPreviewParams(C.Structure):
     """rt_preview_params (include/rt_api.h): a preview session's frame size, render, switches and the
     records of its temporal stage and its filter."""
@@ -207,6 +255,8 @@ assert C.sizeof(RtDenoiseParams) == 36 and C.sizeof(RtDenoiseBuffers) == 56
 assert C.sizeof(RtDenoiseVarBuffers) == 32
 assert C.sizeof(RtTemporalParams) == 32 and C.sizeof(RtTemporalBuffers) == 128
 assert C.sizeof(RtPreviewParams) == 96 and C.sizeof(RtPreviewPlanes) == 120
+assert C.sizeof(RtUpsampleParams) == 32 and C.sizeof(RtUpsampleBuffers) == 96
+assert C.sizeof(RtPreviewUpscale) == 24 and C.sizeof(RtPreviewOutput) == 64
 
 
 def ptr(arr, ctype=C.c_void_p):

@@ -97,6 +97,15 @@ def _declare(L):
                                          P(abi.RtTemporalBuffers), C.c_void_p]),
         "rt_temporal": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera), P(abi.RtTemporalBuffers),
                                   P(abi.RtStats)]),
+        "rt_upsample_params_default": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 P(abi.RtUpsampleParams)]),
+        "rt_upsample_device": (C.c_int, [P(abi.RtUpsampleParams), P(abi.RtUpsampleBuffers), C.c_void_p]),
+        "rt_upsample": (C.c_int, [P(abi.RtUpsampleParams), P(abi.RtUpsampleBuffers), P(abi.RtStats)]),
+        "rt_preview_upscale_default": (C.c_int, [P(abi.RtPreviewParams), C.c_uint32, C.c_uint32,
+                                                 P(abi.RtPreviewUpscale)]),
+        "rt_preview_create_upscaled": (C.c_int, [C.c_void_p, P(abi.RtPreviewParams), P(abi.RtPreviewUpscale),
+                                                 P(C.c_void_p)]),
+        "rt_preview_output": (C.c_int, [C.c_void_p, P(abi.RtPreviewOutput)]),
         "rt_preview_params_default": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, P(abi.RtPreviewParams)]),
         "rt_preview_create": (C.c_int, [C.c_void_p, P(abi.RtPreviewParams), P(C.c_void_p)]),
         "rt_preview_frame_device": (C.c_int, [C.c_void_p, P(abi.RtCamera), C.c_uint64, C.c_void_p, C.c_void_p,

@@ -304,6 +304,19 @@ struct KPreviewMerge {
     uint32_t W, H;
 };
 
+// The guided upsample (rt_upsample.hip; rt_upsample_device): the low-resolution
+// image (lw x lh; l_variance and o_variance both null: no variance) and its guides, the guides of
+// the output size (W x H), the outputs.
+struct KUpsample {
+    const float *l_color, *l_variance, *l_normal, *l_depth;
+    const uint32_t *l_id;
+    const float *normal, *depth, *alpha;
+    const uint32_t *id;
+    float *o_color, *o_variance;
+    uint32_t W, H, LW, LH;
+    float normal_tol, depth_tol;
+};
+
 // The wavefront variant's ray queue (structure of arrays, capacity cap rays): f = [9][cap]
 // floats {o.xyz, d.xyz, attenuation.xyz}, then the data-stream state, the item index (slot) and
 // the segment count of each ray; count = rays in the queue.

@@ -2024,8 +2024,8 @@ int SyncCall::run(const SyncSpec &s, const std::function<int()> &enqueue, const 
             if (pl->kind == Plane::Absent) continue;
             pl->dev = static_cast<char *>(cx.arena) + pl->at;
             if (rc == RT_OK && pl->kind == Plane::In)
-                chk(hipMemcpy(pl->dev, pl->host, s.n_px * pl->px_bytes, hipMemcpyHostToDevice), "hipMemcpy");
-            if (rc == RT_OK && pl->clear) chk(hipMemsetAsync(pl->dev, 0, s.n_px * pl->px_bytes, nullptr), "hipMemset");
+                chk(hipMemcpy(pl->dev, pl->host, pl->pixels(s.n_px) * pl->px_bytes, hipMemcpyHostToDevice), "hipMemcpy");
+            if (rc == RT_OK && pl->clear) chk(hipMemsetAsync(pl->dev, 0, pl->pixels(s.n_px) * pl->px_bytes, nullptr), "hipMemset");
         }
         // the work counters (rt_stats) come from the counting instantiation of the kernels, slower than
         // the product's: only when the caller asks for them (rt::render_impl does not, as cuda_impl)

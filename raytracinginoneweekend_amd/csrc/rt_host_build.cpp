@@ -850,7 +850,7 @@ size_t plane_layout(Plane *planes, size_t n_planes, size_t n_px)
         Plane &pl = planes[i];
         if (pl.kind == Plane::Absent) continue;
         pl.at = total;
-        total += (n_px * pl.px_bytes + 255u) & ~static_cast<size_t>(255u);
+        total += (pl.pixels(n_px) * pl.px_bytes + 255u) & ~static_cast<size_t>(255u);
     }
     return total;
 }

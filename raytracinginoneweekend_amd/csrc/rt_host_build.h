@@ -81,7 +81,9 @@ struct Plane {
     bool clear = false;  // zeroed on the device before the work
     size_t at = 0;       // plane_layout: its offset in the arena
     void *dev = nullptr;  // SyncCall::run: its address on the device
+    size_t n_px = 0;     // its pixels when the call has planes of two sizes (an input or a scratch plane); 0: the call's
     template <class T> T *as() const { return static_cast<T *>(dev); }
+    size_t pixels(size_t call_px) const { return n_px ? n_px : call_px; }
 };
 inline Plane plane_in(const void *host, uint32_t px_bytes)
 {
@@ -89,7 +91,7 @@ inline Plane plane_in(const void *host, uint32_t px_bytes)
 }
 inline Plane plane_out(void *host, uint32_t px_bytes) { return {host ? Plane::Out : Plane::Absent, host, px_bytes}; }
 inline Plane plane_scratch(bool wanted, uint32_t px_bytes) { return {wanted ? Plane::Scratch : Plane::Absent, nullptr, px_bytes}; }
-// Packs the planes that are there, n_px pixels each, in table order from offset 0 with every
+// Packs the planes that are there, n_px pixels each (or the plane's own count), in table order from offset 0 with every
 // offset a multiple of 256 bytes (`at`); returns the bytes they take together.
 size_t plane_layout(Plane *planes, size_t n_planes, size_t n_px);
 

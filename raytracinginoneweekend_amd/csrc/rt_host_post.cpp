@@ -1,9 +1,9 @@
 // rt_host_post.cpp — the post-process stages of the C-ABI (include/rt_api.h), which use nothing of
-// a device scene: the à-trous denoiser, its variance-guided form and temporal accumulation, each
-// with its argument checks, defaults, level driver, stream-ordered *_device entry point and the
-// synchronous host-plane call through the cached context (rt_host_sync.h SyncCall); and the preview
-// session, which runs those stages after a scene's two render calls, one frame per call. The
-// kernels are rt_denoise.hip, rt_temporal.hip and rt_preview.hip.
+// a device scene: the à-trous denoiser, its variance-guided form, temporal accumulation and the
+// guided upsample, each with its argument checks, defaults, level driver, stream-ordered *_device
+// entry point and the synchronous host-plane call through the cached context (rt_host_sync.h
+// SyncCall); and the preview session, which runs those stages after a scene's render calls, one
+// frame per call. The kernels are rt_denoise.hip, rt_temporal.hip, rt_upsample.hip and rt_preview.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -349,6 +349,77 @@ int temporal_host(const rt_temporal_params *params, const rt_camera *camera, con
     return rc;
 }
 
+// ---- guided upsampling (include/rt_api.h; kernel in rt_upsample.hip) ----------
+// rt_upsample_params_default: the values scripts/upscale_sweep.py chose
+constexpr float kUpNormalTol = 0.01f, kUpDepthTol = 0.3f;
+
+// The checks of the params' own values (w: the message up to the field's name).
+int check_upsample_ranges(const rt_upsample_params &p, const std::string &w)
+{
+    if (!p.width || p.width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
+    if (!p.height || p.height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    if (!p.lo_width || p.lo_width > p.width) return fail(RT_ERR_INVALID, w + "lo_width must be 1..width");
+    if (!p.lo_height || p.lo_height > p.height) return fail(RT_ERR_INVALID, w + "lo_height must be 1..height");
+    if (!std::isfinite(p.normal_tol) || p.normal_tol < 0.f) return fail(RT_ERR_INVALID, w + "normal_tol must be finite and not negative");
+    if (!std::isfinite(p.depth_tol) || p.depth_tol < 0.f) return fail(RT_ERR_INVALID, w + "depth_tol must be finite and not negative");
+    if (p.flags) return fail(RT_ERR_INVALID, w + "flags must be 0 (none is defined)");
+    return RT_OK;
+}
+
+// Every argument check, before any HIP call; fills the kernel's record from the caller's pointers.
+int check_upsample(const rt_upsample_params *p, const rt_upsample_buffers *b, const char *who, rt::KUpsample *k)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!p || !b) return fail(RT_ERR_INVALID, w + "null argument");
+    if (p->size != sizeof(rt_upsample_params)) return fail(RT_ERR_INVALID, w + "params.size is not sizeof(rt_upsample_params)");
+    if (b->size != sizeof(rt_upsample_buffers)) return fail(RT_ERR_INVALID, w + "buffers.size is not sizeof(rt_upsample_buffers)");
+    if (int rc = check_upsample_ranges(*p, w); rc != RT_OK) return rc;
+    const struct { const char *name; const void *ptr; } in[9] = {
+        {"lo_color", b->lo_color}, {"lo_normal", b->lo_normal}, {"lo_depth", b->lo_depth}, {"lo_sphere_id", b->lo_sphere_id},
+        {"normal", b->normal},     {"depth", b->depth},         {"alpha", b->alpha},       {"sphere_id", b->sphere_id},
+        {"lo_variance", b->lo_variance}};
+    for (int i = 0; i < 8; ++i)
+        if (!in[i].ptr) return fail(RT_ERR_INVALID, w + in[i].name + " is null");
+    if (!b->out_color) return fail(RT_ERR_INVALID, w + "out_color is null");
+    if (b->lo_variance && !b->out_variance) return fail(RT_ERR_INVALID, w + "lo_variance is given without out_variance");
+    if (b->out_variance && !b->lo_variance) return fail(RT_ERR_INVALID, w + "out_variance is given without lo_variance");
+    for (const auto &c : in) {
+        if (c.ptr && c.ptr == b->out_color) return fail(RT_ERR_INVALID, w + "out_color is also the input plane " + c.name);
+        if (c.ptr && c.ptr == b->out_variance) return fail(RT_ERR_INVALID, w + "out_variance is also the input plane " + c.name);
+    }
+    if (static_cast<const void *>(b->out_variance) == b->out_color) return fail(RT_ERR_INVALID, w + "out_variance is also out_color");
+    *k = rt::KUpsample{b->lo_color, b->lo_variance, b->lo_normal, b->lo_depth, b->lo_sphere_id, b->normal, b->depth,
+                       b->alpha,    b->sphere_id,   b->out_color, b->out_variance, p->width,    p->height, p->lo_width,
+                       p->lo_height, p->normal_tol, p->depth_tol};
+    return RT_OK;
+}
+
+// Synchronous upsample of host planes: the low-resolution planes (a pixel count of their own), the
+// output-size guides, then the outputs.
+int upsample_host(const rt_upsample_params *params, const rt_upsample_buffers *buffers, rt_stats *stats)
+{
+    rt::KUpsample k{};
+    if (int rc = check_upsample(params, buffers, "rt_upsample", &k); rc != RT_OK) return rc;
+    const size_t n = static_cast<size_t>(params->width) * params->height;
+    const size_t n_lo = static_cast<size_t>(params->lo_width) * params->lo_height;
+    const rt_upsample_buffers &b = *buffers;
+    Plane planes[11] = {plane_in(b.lo_color, 12), plane_in(b.lo_variance, 4), plane_in(b.lo_normal, 12),
+                        plane_in(b.lo_depth, 4),  plane_in(b.lo_sphere_id, 4), plane_in(b.normal, 12),
+                        plane_in(b.depth, 4),     plane_in(b.alpha, 4),       plane_in(b.sphere_id, 4),
+                        plane_out(b.out_color, 12), plane_out(b.out_variance, 4)};
+    for (int i = 0; i < 5; ++i) planes[i].n_px = n_lo;
+    SyncCall call;
+    const int rc = call.run({"rt_upsample", planes, 11, n, {n, 1}}, [&] {
+        auto f = [&](int i) { return planes[i].as<float>(); };
+        k.l_color = f(0), k.l_variance = f(1), k.l_normal = f(2), k.l_depth = f(3), k.l_id = planes[4].as<uint32_t>();
+        k.normal = f(5), k.depth = f(6), k.alpha = f(7), k.id = planes[8].as<uint32_t>();
+        k.o_color = f(9), k.o_variance = f(10);
+        return hip_rc(rt::launch_upsample(k, nullptr), "rt_upsample");
+    });
+    if (rc == RT_OK && stats) timed_stats(*stats, call);
+    return rc;
+}
+
 } // namespace
 
 // ---- the preview session (include/rt_api.h; kernels in rt_preview.hip) ---------
@@ -372,6 +443,12 @@ struct rt_preview {
     float *acc_color = nullptr, *acc_variance = nullptr;
     // the filter's output and the levels' intermediate planes
     float *filtered = nullptr, *scratch = nullptr, *var_scratch = nullptr;
+    // an upscaled session (rt_preview_create_upscaled; up.size is 0 otherwise): the guides of the
+    // output size (the albedo under DEMODULATE only) and the upsampled image
+    rt_preview_upscale up{};
+    float *up_albedo = nullptr, *up_normal = nullptr, *up_depth = nullptr, *up_alpha = nullptr, *upsampled = nullptr;
+    uint32_t *up_id = nullptr;
+    bool up_written = false;       // a frame has written them
     uint32_t cur = 0;
     rt_camera prev_camera{};
     rt_preview_planes_t last{};    // last.frames: frames since creation or the last reset
@@ -445,6 +522,16 @@ size_t preview_carve(rt_preview &pv, char *base)
         take(pv.h[s].color, 3, temporal), take(pv.h[s].variance, 1, temporal), take(pv.h[s].history, 1, temporal);
     take(pv.acc_color, 3, feedback), take(pv.acc_variance, 1, feedback);
     take(pv.filtered, 3), take(pv.scratch, 3, between), take(pv.var_scratch, 2, between);
+    if (pv.up.size) {
+        const size_t n_out = static_cast<size_t>(pv.up.out_width) * pv.up.out_height;
+        auto take_out = [&](auto *&plane, size_t words, bool wanted = true) {
+            if (!wanted) return;
+            if (base) plane = reinterpret_cast<std::remove_reference_t<decltype(plane)>>(base + at);
+            at += (words * n_out * sizeof(float) + 255u) / 256u * 256u;
+        };
+        take_out(pv.up_albedo, 3, demod), take_out(pv.up_normal, 3), take_out(pv.up_depth, 1), take_out(pv.up_alpha, 1);
+        take_out(pv.up_id, 1), take_out(pv.upsampled, 3);
+    }
     return at;
 }
 
@@ -494,7 +581,25 @@ int preview_frame(rt_preview &pv, const rt_camera *camera, uint64_t seed, float 
     if (int rc = denoise_var_levels(P.denoise, db, vb, pv.terms, st, c1, v1); rc != RT_OK) return rc;
     // 5 merge
     const float *const filtered = feedback && P.denoise.levels == 1u ? c1 : pv.filtered;
-    RT_HIP(rt::launch_preview_merge({filtered, demod ? pv.albedo : nullptr, d_rgb, d_rgb8, P.width, P.height}, st));
+    if (!pv.up.size) {
+        RT_HIP(rt::launch_preview_merge({filtered, demod ? pv.albedo : nullptr, d_rgb, d_rgb8, P.width, P.height}, st));
+    } else {
+        // an upscaled session: the guides of the output size, the upsample, the merge at that size
+        const rt_preview_upscale &U = pv.up;
+        const rt_params gp{U.out_width, U.out_height, P.spp, P.max_depth, seed, 0u, 1u, 0u, 0u};
+        const rt_aov_buffers ga{static_cast<uint32_t>(sizeof(rt_aov_buffers)), U.guide_samples, pv.up_albedo, pv.up_normal,
+                                pv.up_depth, pv.up_alpha, pv.up_id};
+        if (int rc = rt_render_aov_device(pv.scene, camera, &gp, &ga, st); rc != RT_OK) return rc;
+        const rt_upsample_params upar{static_cast<uint32_t>(sizeof(rt_upsample_params)), U.out_width, U.out_height, P.width,
+                                      P.height, U.normal_tol, U.depth_tol, 0u};
+        const rt_upsample_buffers ub{static_cast<uint32_t>(sizeof(rt_upsample_buffers)), filtered, nullptr, g.normal, g.depth,
+                                     g.id, pv.up_normal, pv.up_depth, pv.up_alpha, pv.up_id, pv.upsampled, nullptr};
+        rt::KUpsample ku{};
+        if (int rc = check_upsample(&upar, &ub, who, &ku); rc != RT_OK) return rc;
+        RT_HIP(rt::launch_upsample(ku, st));
+        RT_HIP(rt::launch_preview_merge({pv.upsampled, demod ? pv.up_albedo : nullptr, d_rgb, d_rgb8, U.out_width, U.out_height}, st));
+        pv.up_written = true;
+    }
     // what the frame wrote, and what the next one reprojects
     rt_preview_planes_t &l = pv.last;
     l.frames += 1u;
@@ -513,6 +618,51 @@ int check_preview_side(uint32_t width, uint32_t height, const std::string &w)
 {
     if (!width || width > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "width must be 1..65536");
     if (!height || height > kDenoiseMaxSide) return fail(RT_ERR_INVALID, w + "height must be 1..65536");
+    return RT_OK;
+}
+
+// Every check of an upscaled session's second record, after check_preview has passed `p`.
+int check_preview_upscale(const rt_preview_params &p, const rt_preview_upscale *u)
+{
+    const std::string w = "rt_preview_create_upscaled: ";
+    if (!u) return fail(RT_ERR_INVALID, w + "null upscale record");
+    if (u->size != sizeof(rt_preview_upscale)) return fail(RT_ERR_INVALID, w + "upscale.size is not sizeof(rt_preview_upscale)");
+    if (u->out_width < p.width || u->out_width > kDenoiseMaxSide)
+        return fail(RT_ERR_INVALID, w + "out_width must be the session's width..65536");
+    if (u->out_height < p.height || u->out_height > kDenoiseMaxSide)
+        return fail(RT_ERR_INVALID, w + "out_height must be the session's height..65536");
+    if (static_cast<uint64_t>(u->out_width) * u->out_height >= (1ull << 31))
+        return fail(RT_ERR_INVALID, w + "out_width * out_height must be below 2^31 (one render call)");
+    if (u->guide_samples > p.spp) return fail(RT_ERR_INVALID, w + "guide_samples must be at most spp");
+    if (!std::isfinite(u->normal_tol) || u->normal_tol < 0.f) return fail(RT_ERR_INVALID, w + "normal_tol must be finite and not negative");
+    if (!std::isfinite(u->depth_tol) || u->depth_tol < 0.f) return fail(RT_ERR_INVALID, w + "depth_tol must be finite and not negative");
+    return RT_OK;
+}
+
+// A session of either kind (u null: an ordinary one): its params checked, its planes allocated.
+int preview_create(rt_scene *scene, const rt_preview_params *p, const rt_preview_upscale *u, const char *who,
+                   rt_preview **out)
+{
+    uint32_t terms = 0;
+    if (int rc = check_preview(p, &terms); rc != RT_OK) return rc;
+    if (!scene) return fail(RT_ERR_INVALID, std::string(who) + ": scene is null");
+    if (!out) return fail(RT_ERR_INVALID, std::string(who) + ": out is null");
+    rt_preview *pv = new rt_preview;
+    pv->scene = scene;
+    pv->device = scene_device(scene);
+    pv->p = *p;
+    if (u) pv->up = *u;
+    pv->terms = terms;
+    pv->last.size = static_cast<uint32_t>(sizeof(rt_preview_planes_t));
+    pv->bytes = preview_carve(*pv, nullptr);
+    hipError_t e = hipSetDevice(pv->device);
+    if (e == hipSuccess) e = hipMalloc(&pv->arena, pv->bytes);
+    if (e != hipSuccess) {
+        delete pv;
+        return fail(RT_ERR_DEVICE, std::string(who) + ": the session's planes: " + hipGetErrorString(e));
+    }
+    preview_carve(*pv, static_cast<char *>(pv->arena));
+    *out = pv;
     return RT_OK;
 }
 
@@ -537,27 +687,43 @@ int rt_preview_params_default(uint32_t width, uint32_t height, uint32_t spp, rt_
     return RT_OK;
 }
 
+int rt_preview_upscale_default(const rt_preview_params *p, uint32_t out_width, uint32_t out_height, rt_preview_upscale *out)
+{
+    if (!p || !out) return fail(RT_ERR_INVALID, "rt_preview_upscale_default: null argument");
+    if (out_width < p->width || out_height < p->height || !out_width || !out_height)
+        return fail(RT_ERR_INVALID, "rt_preview_upscale_default: the output is smaller than the session's frame");
+    rt_upsample_params up{};
+    if (int rc = rt_upsample_params_default(out_width, out_height, p->width, p->height, &up); rc != RT_OK) return rc;
+    *out = rt_preview_upscale{static_cast<uint32_t>(sizeof(rt_preview_upscale)), out_width, out_height, 0u, up.normal_tol,
+                              up.depth_tol};
+    return RT_OK;
+}
+
 int rt_preview_create(rt_scene *scene, const rt_preview_params *p, rt_preview **out)
+{
+    return preview_create(scene, p, nullptr, "rt_preview_create", out);
+}
+
+int rt_preview_create_upscaled(rt_scene *scene, const rt_preview_params *p, const rt_preview_upscale *u, rt_preview **out)
 {
     uint32_t terms = 0;
     if (int rc = check_preview(p, &terms); rc != RT_OK) return rc;
-    if (!scene) return fail(RT_ERR_INVALID, "rt_preview_create: scene is null");
-    if (!out) return fail(RT_ERR_INVALID, "rt_preview_create: out is null");
-    rt_preview *pv = new rt_preview;
-    pv->scene = scene;
-    pv->device = scene_device(scene);
-    pv->p = *p;
-    pv->terms = terms;
-    pv->last.size = static_cast<uint32_t>(sizeof(rt_preview_planes_t));
-    pv->bytes = preview_carve(*pv, nullptr);
-    hipError_t e = hipSetDevice(pv->device);
-    if (e == hipSuccess) e = hipMalloc(&pv->arena, pv->bytes);
-    if (e != hipSuccess) {
-        delete pv;
-        return fail(RT_ERR_DEVICE, std::string("rt_preview_create: the session's planes: ") + hipGetErrorString(e));
+    if (int rc = check_preview_upscale(*p, u); rc != RT_OK) return rc;
+    return preview_create(scene, p, u, "rt_preview_create_upscaled", out);
+}
+
+int rt_preview_output(rt_preview *pv, rt_preview_output_t *out)
+{
+    if (!pv || !out) return fail(RT_ERR_INVALID, "rt_preview_output: null argument");
+    if (!pv->up.size) return fail(RT_ERR_INVALID, "rt_preview_output: the session is not an upscaled one (rt_preview_create made it)");
+    rt_preview_output_t o{};
+    o.size = static_cast<uint32_t>(sizeof(rt_preview_output_t));
+    o.width = pv->up.out_width, o.height = pv->up.out_height;
+    if (pv->up_written) {
+        o.upsampled = pv->upsampled, o.albedo = pv->up_albedo, o.normal = pv->up_normal, o.depth = pv->up_depth;
+        o.alpha = pv->up_alpha, o.sphere_id = pv->up_id;
     }
-    preview_carve(*pv, static_cast<char *>(pv->arena));
-    *out = pv;
+    *out = o;
     return RT_OK;
 }
 
@@ -646,6 +812,28 @@ int rt_temporal(const rt_temporal_params *params, const rt_camera *camera, const
                 const rt_temporal_buffers *buffers, rt_stats *stats)
 {
     return temporal_host(params, camera, prev_camera, buffers, stats);
+}
+
+int rt_upsample_params_default(uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height, rt_upsample_params *out)
+{
+    if (!out) return fail(RT_ERR_INVALID, "rt_upsample_params_default: null argument");
+    if (!width || !height || !lo_width || !lo_height) return fail(RT_ERR_INVALID, "rt_upsample_params_default: a zero side");
+    *out = rt_upsample_params{static_cast<uint32_t>(sizeof(rt_upsample_params)), width, height, lo_width, lo_height,
+                              kUpNormalTol, kUpDepthTol, 0u};
+    return RT_OK;
+}
+
+int rt_upsample_device(const rt_upsample_params *params, const rt_upsample_buffers *buffers, void *stream)
+{
+    rt::KUpsample k{};
+    if (int rc = check_upsample(params, buffers, "rt_upsample_device", &k); rc != RT_OK) return rc;
+    RT_HIP(rt::launch_upsample(k, static_cast<hipStream_t>(stream)));
+    return RT_OK;
+}
+
+int rt_upsample(const rt_upsample_params *params, const rt_upsample_buffers *buffers, rt_stats *stats)
+{
+    return upsample_host(params, buffers, stats);
 }
 
 int rt_denoise_var_params_default(uint32_t width, uint32_t height, rt_denoise_params *params, rt_denoise_var_buffers *var)

@@ -40,6 +40,8 @@ hipError_t launch_denoise_var(const KDenoiseVar &k, uint32_t terms, hipStream_t 
 size_t denoise_tiled_lds(uint32_t terms, uint32_t step);
 // rt_temporal.hip
 hipError_t launch_temporal(const KTemporal &k, hipStream_t stream);
+// rt_upsample.hip
+hipError_t launch_upsample(const KUpsample &k, hipStream_t stream);
 // rt_preview.hip
 hipError_t launch_preview_split(const KPreviewSplit &k, hipStream_t stream);
 hipError_t launch_preview_merge(const KPreviewMerge &k, hipStream_t stream);
@@ -88,7 +90,7 @@ struct SyncSpec {
     const char *who;  // names the call where its last synchronise fails
     Plane *planes;    // in upload and download order
     size_t n_planes;
-    size_t n_px;      // pixels of every plane on the device
+    size_t n_px;      // pixels of every plane on the device that has no count of its own (Plane::n_px)
     SyncRows rows;
     const SyncScene *scene = nullptr;  // a render: the context holds this scene before the work
     bool counters = false;  // zero the device's work counters before the work, read them after it

@@ -382,6 +382,93 @@ def temporal(cur, prev, camera, prev_camera, params=None, stats=None, **fields):
     return out["out_color"], out["out_variance"], out["out_history"]
 
 
+def upsample_params(width, height, lo_width, lo_height, base=None, **fields):
+    """An rt_upsample_params record: the library defaults for the two image sizes
+    (or a copy of `base`) with `fields` set (normal_tol, depth_tol, flags)."""
+    p = abi.RtUpsampleParams()
+    if base is None:
+        check(lib().rt_upsample_params_default(width, height, lo_width, lo_height, C.byref(p)))
+    else:
+        C.memmove(C.byref(p), C.byref(base), C.sizeof(p))
+        p.width, p.height, p.lo_width, p.lo_height = width, height, lo_width, lo_height
+    for k, v in fields.items():
+        if k not in ("normal_tol", "depth_tol", "flags"):
+            raise KeyError(f"rt_upsample_params has no field {k!r} to set")
+        setattr(p, k, v)
+    return p
+
+
+def upsample_buffers(pointers):
+    """An rt_upsample_buffers record from a dict plane name (abi.UPSAMPLE_PLANES: lo_color,
+    lo_variance, lo_normal, lo_depth, lo_sphere_id; normal, depth, alpha, sphere_id; out_color,
+    out_variance) -> address (absent or 0: not given)."""
+    unknown = set(pointers) - set(abi.UPSAMPLE_PLANES)
+    if unknown:
+        raise KeyError(f"rt_upsample_buffers has no plane {sorted(unknown)!r}")
+    return abi.RtUpsampleBuffers(C.sizeof(abi.RtUpsampleBuffers), *(pointers.get(n) or None for n in abi.UPSAMPLE_PLANES))
+
+
+def upsample_device(pointers, params, stream=None):
+    """Enqueue rt_upsample_device on `stream`: `pointers` is a dict plane name -> device address on
+    the current device (upsample_buffers), `params` an rt_upsample_params record. One launch, no host
+    synchronisation."""
+    rec = upsample_buffers(pointers)
+    check(lib().rt_upsample_device(C.byref(params), C.byref(rec), C.c_void_p(stream or 0)))
+
+
+_UPSAMPLE_LO = ("color", "normal", "depth", "sphere_id")
+_UPSAMPLE_HI = ("normal", "depth", "alpha", "sphere_id")
+
+
+def upsample(lo, guides, params=None, stats=None, **fields):
+    """rt_upsample: a low-resolution image brought up to the size of `guides` by a
+    joint-bilateral upsample. lo: dict of the low-resolution planes (color float32 (lh, lw, 3);
+    normal, depth, sphere_id as render_aov returns them at that size; optionally variance (lh, lw));
+    guides: dict of the output-size planes normal, depth, alpha, sphere_id (render_aov at the output
+    size, same camera). Returns color float32 (h, w, 3), or (color, variance) when lo holds a
+    variance. params: an rt_upsample_params record (default: the library's); `fields` as
+    upsample_params takes them."""
+    with_var = "variance" in lo
+    if set(lo) - {"variance"} != set(_UPSAMPLE_LO):
+        raise KeyError(f"lo must hold the planes {_UPSAMPLE_LO} (and optionally variance), not {sorted(lo)}")
+    if set(guides) != set(_UPSAMPLE_HI):
+        raise KeyError(f"guides must hold exactly the planes {_UPSAMPLE_HI}, not {sorted(guides)}")
+    if np.ndim(lo["color"]) != 3 or np.shape(lo["color"])[2] != 3:
+        raise ValueError(f"lo color must be float32 (lh, lw, 3), not {np.shape(lo['color'])}")
+    if np.ndim(guides["normal"]) != 3 or np.shape(guides["normal"])[2] != 3:
+        raise ValueError(f"normal must be float32 (h, w, 3), not {np.shape(guides['normal'])}")
+    lh, lw = np.shape(lo["color"])[:2]
+    h, w = np.shape(guides["normal"])[:2]
+    host = {}
+    for n, a, (hh, ww) in ([("lo_" + n, lo[n], (lh, lw)) for n in lo] + [(n, guides[n], (h, w)) for n in _UPSAMPLE_HI]):
+        ch, dt = abi.UPSAMPLE_PLANES[n]
+        want = (hh, ww, 3) if ch == 3 else (hh, ww)
+        a = np.asarray(a)
+        if a.dtype != dt or a.shape != want:
+            raise ValueError(f"{n} must be {np.dtype(dt).name} {want}, not {a.dtype} {a.shape}")
+        host[n] = np.ascontiguousarray(a)
+    p = upsample_params(w, h, lw, lh, base=params, **fields)
+    out = {"out_color": np.zeros((h, w, 3), dtype=np.float32)}
+    if with_var:
+        out["out_variance"] = np.zeros((h, w), dtype=np.float32)
+    rec = upsample_buffers({n: a.ctypes.data for n, a in {**host, **out}.items()})
+    check(lib().rt_upsample(C.byref(p), C.byref(rec), C.byref(stats) if stats is not None else None))
+    return (out["out_color"], out["out_variance"]) if with_var else out["out_color"]
+
+
+def preview_upscale(params, out_width, out_height, **fields):
+    """An rt_preview_upscale record for a session of `params` (an rt_preview_params
+    record) shown at out_width x out_height: the library defaults with `fields` set (guide_samples,
+    normal_tol, depth_tol)."""
+    u = abi.RtPreviewUpscale()
+    check(lib().rt_preview_upscale_default(C.byref(params), out_width, out_height, C.byref(u)))
+    for k, v in fields.items():
+        if k not in ("guide_samples", "normal_tol", "depth_tol"):
+            raise KeyError(f"rt_preview_upscale has no field {k!r} to set")
+        setattr(u, k, v)
+    return u
+
+
 def preview_params(width, height, spp, base=None, demodulate=None, feedback=None, temporal=None, denoise=None,
                    **fields):
     """An rt_preview_params record: the library defaults for the frame (or a copy
@@ -416,15 +503,23 @@ def preview_params(width, height, spp, base=None, demodulate=None, feedback=None
 class Preview:
     """A preview session on a DeviceScene (rt_preview_create): the loop render ->
     feature buffers -> temporal accumulation -> variance-guided filter -> epilogue with every plane
-    and the history kept on the device, one call per frame. Close it before its scene."""
+    and the history kept on the device, one call per frame. Close it before its scene. upscale: an
+    rt_preview_upscale record (preview_upscale) makes it an upscaled session
+    (rt_preview_create_upscaled): the loop runs at `params`' size, and frame()
+    writes images of the record's output size."""
 
-    def __init__(self, device_scene, params):
+    def __init__(self, device_scene, params, upscale=None):
         h = C.c_void_p()
-        check(lib().rt_preview_create(device_scene.handle if device_scene is not None else None, C.byref(params),
-                                      C.byref(h)))
+        sc = device_scene.handle if device_scene is not None else None
+        if upscale is None:
+            check(lib().rt_preview_create(sc, C.byref(params), C.byref(h)))
+        else:
+            check(lib().rt_preview_create_upscaled(sc, C.byref(params), C.byref(upscale), C.byref(h)))
         self.handle = h
         self.scene = device_scene  # (kept alive as long as the session)
         self.width, self.height = params.width, params.height
+        self.out_width, self.out_height = ((params.width, params.height) if upscale is None
+                                           else (upscale.out_width, upscale.out_height))
 
     def frame(self, camera, seed, rgb_ptr=None, rgb8_ptr=None, stream=None):
         """Enqueue one frame on `stream`: the denoised linear image into device address rgb_ptr
@@ -443,6 +538,14 @@ class Preview:
         r = abi.RtPreviewPlanes()
         check(lib().rt_preview_planes(self.handle, C.byref(r)))
         return {"frames": r.frames, **{n: getattr(r, n) for n in abi.PREVIEW_PLANES}}
+
+    def output(self):
+        """rt_preview_output: what an upscaled session's last frame wrote at the output size, as a
+        dict plane name (abi.PREVIEW_OUTPUT_PLANES) -> device address (None: not there), and
+        'width', 'height'. An ordinary session raises RtError."""
+        r = abi.RtPreviewOutput()
+        check(lib().rt_preview_output(self.handle, C.byref(r)))
+        return {"width": r.width, "height": r.height, **{n: getattr(r, n) for n in abi.PREVIEW_OUTPUT_PLANES}}
 
     def usage(self):
         """rt_preview_usage: the bytes of the session's device allocation."""
@@ -624,9 +727,10 @@ class DeviceScene:
                                          C.c_void_p(rgb_ptr), C.c_void_p(var_ptr), C.c_void_p(stream or 0),
                                          C.c_void_p(segments) if segments else None))
 
-    def preview(self, params):
-        """A preview session on this scene (Preview; preview_params makes the record)."""
-        return Preview(self, params)
+    def preview(self, params, upscale=None):
+        """A preview session on this scene (Preview; preview_params makes the record, preview_upscale
+        the record of an upscaled one)."""
+        return Preview(self, params, upscale)
 
     def tile_order(self, camera, params, stream=None):
         """rt_tile_order_device: the pass's dealing order computed by the device's classification
