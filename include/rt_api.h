@@ -314,6 +314,40 @@ int rt_scene_create_ex(const rt_sphere *spheres, uint32_t n_spheres,
                        const rt_material *materials, uint32_t n_materials, int device,
                        const rt_options *options, rt_scene **out);
 int rt_scene_destroy(rt_scene *scene);
+/* ---- moving spheres: new records into a live scene -------------------------------
+ * Replaces the scene's records in place. n_spheres must equal the scene's count (ids are the link
+ * between frames; another count is RT_ERR_INVALID); n_materials may differ (materials are flattened
+ * per sphere). Every check rt_scene_create_ex makes on the records applies (material index, kind, null
+ * pointers), all before any HIP call, the message naming the field.
+ * The call is synchronous: it builds everything rt_scene_create_ex derives from the records on the
+ * host (both blobs with the clustering, the boxes, the shading records, kinds, dielectric constants
+ * and walk-shortcut words; the trap windows, under RT_DIAG_NO_TRAP_END too; the tile classes' geometry;
+ * the fast-range flag; the counts and offsets), waits until the scene's device is idle, grows any device
+ * buffer that is too small, uploads and swaps. The streams, events, workspaces, deep queues, permutation
+ * buffers and debug buffers are kept. What was keyed by the old geometry is dropped: the cached dealing
+ * orders (rt_scene_order_counts keeps counting), the deep-split record of cameras, and the occupancy
+ * caches that depend on a blob's size. On any failure the scene is exactly as it was.
+ * The contract: after rt_scene_update(sc, S, M) every call on sc behaves like the same call on a scene
+ * freshly created from (S, M) with sc's options: the same status, the same bits in the beauty, the
+ * variance, all five feature planes, the tile orders and counts, the same trap behaviour. A blob that no
+ * longer fits LDS is reported by the calls that would report it for a fresh scene.
+ * The scene keeps two device tables of n_spheres x 4 floats {cx, cy, cz, radius}, row i = sphere i of
+ * the caller's array: the current records, and the records before the most recent update (both the
+ * creation's records until then); an update swaps them and uploads the new one. They add 32 B per sphere
+ * to rt_scene_usage.device_bytes. geometry_epoch goes up by 1 on an update in which the bits of any
+ * centre or radius changed, appearance_epoch on one in which any sphere's flattened {kind, albedo, param}
+ * changed. An update whose records equal the current ones bit for bit returns RT_OK at once: no wait,
+ * the cached orders stay, both epochs stay.
+ * Not covered: an rt_multi context (its scenes are its own), and the cached context of the synchronous
+ * host-buffer renders, which rebuilds on a new scene as before.                                       */
+int rt_scene_update(rt_scene *scene, const rt_sphere *spheres, uint32_t n_spheres,
+                    const rt_material *materials, uint32_t n_materials);
+typedef struct rt_scene_motion_t {
+    uint32_t size, n_spheres;              /* sizeof(rt_scene_motion_t), filled by the call             */
+    const float *centres, *prev_centres;   /* device, [n_spheres][4]; valid until the next update      */
+    uint64_t geometry_epoch, appearance_epoch;
+} rt_scene_motion_t;
+int rt_scene_motion(rt_scene *scene, rt_scene_motion_t *out);
 /* Enqueue one render for `stream` (a hipStream_t, or NULL for the null stream).
  * d_rgb: device buffer laid out as rt_params says. d_segments: optional device u64[3]
  * that accumulates {segments, sphere tests, cluster box tests} (zero it first). No
@@ -637,6 +671,44 @@ int rt_temporal_device(const rt_temporal_params *params, const rt_camera *camera
  * context rt_release_cached frees). stats (optional): kernel_ms, wall_ms; the counters are 0.     */
 int rt_temporal(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
                 const rt_temporal_buffers *buffers, rt_stats *stats);
+
+/* ---- the temporal stage with object motion -----------------------------------
+ * rt_temporal_device for spheres that moved between the two frames. Spheres are rigid and uniformly
+ * coloured, so a sphere's motion is its centre's motion, and sphere_id names the sphere under each
+ * pixel: the stage takes two tables of n_spheres x 4 floats {cx, cy, cz, radius}, row i = sphere i of
+ * the caller's array, now (centres) and at the previous frame (prev_centres), and no motion-vector
+ * plane. Everything in rt_temporal_device's contract holds except step 3 for a surface pixel. With
+ * id = sphere_id(p):
+ *   id >= n_spheres: no history; neither table is read at that index
+ *   C = centres[id], C' = prev_centres[id]; if the bits of C.r and C'.r differ (compared as uint32): no
+ *   history (a resized sphere restarts)
+ *   m = C.xyz - C'.xyz, componentwise
+ *   q = ((o + depth(p) * d) - m) - o'
+ * every operation binary32, rounded on its own, in the order written. Sky and edge pixels, the
+ * projection, the four taps and their tests, the blend and the no-history copy are unchanged: the depth
+ * test compares ga with prev_depth (the previous frame saw the sphere at C', which is what q describes),
+ * and a translation keeps the normal and the id.
+ *   Equal tables give the static stage's bits: if the two tables hold the same bits, m = +0 and
+ *   x - (+0) = x for every x, so the output equals rt_temporal_device's bit for bit. The two pointers may
+ *   be the same pointer.
+ *   Scope of the motion: it is that of the first hit only. Reflections and shadows of a moving sphere on
+ *   other spheres lag; alpha_min bounds that lag, as in any SVGF loop.
+ * Every argument is checked before any HIP call; RT_ERR_INVALID names the field: every check
+ * rt_temporal_device makes, then a null record or a wrong size, n_spheres > 0 with a null table, a table
+ * that is not 16-byte aligned (a row is one 16-byte load), a table that is also an output plane. With
+ * the prev_ planes NULL the record is still checked and then unused. NaN or infinite table entries give
+ * unspecified output values; no read outside a plane or a table happens whatever the values are.       */
+typedef struct rt_temporal_motion_t {
+    uint32_t size, n_spheres;              /* sizeof(rt_temporal_motion_t); rows of either table        */
+    const float *centres, *prev_centres;   /* [n_spheres][4] {cx, cy, cz, r}: now, and at the previous frame */
+} rt_temporal_motion_t;
+/* Device pointers (the tables too); one launch on `stream`, no host synchronisation, no allocation. */
+int rt_temporal_motion_device(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                              const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, void *stream);
+/* Host pointers, synchronous, through the cached per-device context as rt_temporal (the tables are two
+ * more staged inputs, of any alignment).                                                              */
+int rt_temporal_motion(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                       const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, rt_stats *stats);
 
 /* ---- guided upsampling of a low-resolution frame ---------------------------------
  * The stage that brings a filtered image of lo_width x lo_height up to width x height: a joint-

@@ -161,6 +161,21 @@ class RtTemporalBuffers(C.Structure):
     _fields_ = [("size", C.c_uint32)] + [(n, C.c_void_p) for n in TEMPORAL_PLANES]
 
 
+class RtTemporalMotion(C.Structure):
+    """rt_temporal_motion_t (include/rt_api.h): the two sphere tables [n_spheres][4] {cx, cy, cz, r} of
+    the temporal stage with object motion, now and at the previous frame."""
+    _fields_ = [("size", C.c_uint32), ("n_spheres", C.c_uint32), ("centres", C.c_void_p), ("prev_centres", C.c_void_p)]
+
+
+class RtSceneMotion(C.Structure):
+    """rt_scene_motion_t (include/rt_api.h): a device scene's two sphere tables and its epochs."""
+    _fields_ = [("size", C.c_uint32), ("n_spheres", C.c_uint32), ("centres", C.c_void_p), ("prev_centres", C.c_void_p),
+                ("geometry_epoch", C.c_uint64), ("appearance_epoch", C.c_uint64)]
+
+
+assert C.sizeof(RtTemporalMotion) == 24 and C.sizeof(RtSceneMotion) == 40
+
+
 class RtUpsampleParams(C.Structure):
     """rt_upsample_params (include/rt_api.h): the guided upsample's two image sizes and tap tests."""
     _fields_ = [

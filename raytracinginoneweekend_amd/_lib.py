@@ -97,6 +97,12 @@ def _declare(L):
                                          P(abi.RtTemporalBuffers), C.c_void_p]),
         "rt_temporal": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera), P(abi.RtTemporalBuffers),
                                   P(abi.RtStats)]),
+        "rt_temporal_motion_device": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera),
+                                                P(abi.RtTemporalBuffers), P(abi.RtTemporalMotion), C.c_void_p]),
+        "rt_temporal_motion": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera),
+                                         P(abi.RtTemporalBuffers), P(abi.RtTemporalMotion), P(abi.RtStats)]),
+        "rt_scene_update": (C.c_int, [C.c_void_p, P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32]),
+        "rt_scene_motion": (C.c_int, [C.c_void_p, P(abi.RtSceneMotion)]),
         "rt_upsample_params_default": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                  P(abi.RtUpsampleParams)]),
         "rt_upsample_device": (C.c_int, [P(abi.RtUpsampleParams), P(abi.RtUpsampleBuffers), C.c_void_p]),

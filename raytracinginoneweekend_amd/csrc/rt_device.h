@@ -275,7 +275,10 @@ struct KDenoiseVar {
 // The temporal accumulation (rt_temporal.hip; rt_temporal_device): the current
 // frame's planes, the previous frame's (p_color null: no history, the launch copies), the outputs,
 // the current camera as the contract's {a, hor, ver, o} and the previous one as rt_reproject_basis's
-// record {A, B, G, o'}, both formed on the host.
+// record {A, B, G, o'}, both formed on the host. Object motion (rt_temporal_motion_device, DESIGN.md
+// §4.16): the two sphere tables, [n_spheres][4] {cx, cy, cz, r} now and at the previous frame
+// (centres null: the static stage). The motion's fields come last: the static instantiations read
+// the fields before them at the offsets they always had.
 struct KTemporal {
     const float *beauty, *variance, *normal, *depth, *alpha;
     const uint32_t *id;
@@ -286,6 +289,8 @@ struct KTemporal {
     float a[3], hor[3], ver[3], o[3];
     float basis[12];
     float alpha_min, max_history, normal_tol, depth_tol;
+    const float *centres, *p_centres;
+    uint32_t n_spheres;
 };
 
 // The preview session's own kernels (rt_preview.hip; rt_preview_frame_device).

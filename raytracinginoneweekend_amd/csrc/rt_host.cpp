@@ -195,6 +195,15 @@ struct rt_scene {
     static constexpr uint32_t kRing = 256;
     std::vector<hipEvent_t> ev_begin, ev_end;
     uint64_t calls = 0;
+    // Moving spheres (rt_scene_update). The bytes allocated behind blob[], trap and
+    // d_geom: an update whose clustering needs more grows them, one that needs less keeps them. The
+    // records the scene was last derived from, as an update compares them: {cx, cy, cz, r} per sphere
+    // and its flattened {kind, albedo, param}. The two device tables rt_scene_motion reports, [0] the
+    // current records and [1] those before the most recent update, and the two epochs.
+    size_t blob_cap[2] = {0, 0}, trap_cap = 0, geom_cap = 0;
+    std::vector<float> cur_table, cur_flat;
+    float *centres[2] = {nullptr, nullptr};
+    uint64_t geometry_epoch = 0, appearance_epoch = 0;
 };
 
 extern "C" {
@@ -373,6 +382,184 @@ int ensure(void **ptr, size_t *have, size_t want, bool *fresh = nullptr)
 // after the device is idle: the next render re-cuts them under max_workspace_bytes
 int free_workspaces(rt_scene *sc);
 
+// ---- what a scene derives from its records (rt_scene_create_ex and rt_scene_update) -----------
+// The checks of the records, before any HIP call (who: the entry point's name).
+int check_records(const char *who, const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
+                  uint32_t n_materials)
+{
+    const std::string w(who);
+    for (uint32_t i = 0; i < n_spheres; ++i)
+        if (spheres[i].material >= n_materials)
+            return fail(RT_ERR_INVALID, w + ": sphere " + std::to_string(i) + " has material index " +
+                                            std::to_string(spheres[i].material) + " >= " + std::to_string(n_materials));
+    for (uint32_t i = 0; i < n_materials; ++i)
+        if (materials[i].kind > RT_DIELECTRIC)
+            return fail(RT_ERR_INVALID, w + ": material " + std::to_string(i) + " has unknown kind");
+    return RT_OK;
+}
+
+// Everything derived from the records, on the host: the one derivation both entry points install.
+struct SceneDerived {
+    blob_t blobs[2];             // with the shading records, kinds, dielectric constants, shortcut words
+    std::vector<float> trap;     // the windows, then the empty set
+    scene_geom geom;             // the tile classes' geometry, and as classify_tiles_kernel reads it
+    bool has_geom = false;
+    std::vector<float> geom_words;
+    bool in_fast_range = true;
+    std::vector<float> table;    // [n][4] {cx, cy, cz, r}
+    std::vector<float> flat;     // [n][5] {kind bits, albedo, param}
+};
+
+void derive_scene(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, const rt_options &opt,
+                  SceneDerived &d)
+{
+    std::vector<float> hit(static_cast<size_t>(std::max(n_spheres, 1u)) * 12, 0.f);
+    d.table.resize(4 * static_cast<size_t>(n_spheres));
+    d.flat.resize(5 * static_cast<size_t>(n_spheres));
+    for (uint32_t i = 0; i < n_spheres; ++i) {
+        const rt_sphere &sp = spheres[i];
+        const rt_material &mt = materials[sp.material];
+        float *h = hit.data() + 12 * static_cast<size_t>(i);
+        h[0] = sp.center[0]; h[1] = sp.center[1]; h[2] = sp.center[2]; h[3] = sp.radius;
+        h[4] = mt.albedo[0]; h[5] = mt.albedo[1]; h[6] = mt.albedo[2]; h[7] = mt.param;
+        std::memcpy(h + 8, &mt.kind, 4);
+        std::memcpy(d.table.data() + 4 * static_cast<size_t>(i), h, 16);
+        float *f = d.flat.data() + 5 * static_cast<size_t>(i);
+        std::memcpy(f, &mt.kind, 4);
+        std::memcpy(f + 1, h + 4, 16);
+    }
+    d.blobs[0] = build_blob(spheres, n_spheres, false, opt.cluster_size);
+    d.blobs[1] = build_blob(spheres, n_spheres, true, opt.cluster_size);
+    const std::vector<uint32_t> shortcut =
+        shortcut_words(spheres, n_spheres, materials, d.blobs[1], (opt.diag & RT_DIAG_NO_NEIGHBOURS) != 0);
+    // shading records join each blob (so they sit in LDS next to the geometry): per original
+    // sphere index {c, r}, {albedo, param}, then the material kinds as bytes, 16-B padded
+    for (blob_t &b : d.blobs) {
+        b.shade_offset = static_cast<uint32_t>(b.data.size() / 4);
+        for (uint32_t i = 0; i < n_spheres; ++i) b.data.insert(b.data.end(), hit.data() + 12 * static_cast<size_t>(i), hit.data() + 12 * static_cast<size_t>(i) + 8);
+        std::vector<uint8_t> kinds((n_spheres + 15u) / 16u * 16u, 0);
+        for (uint32_t i = 0; i < n_spheres; ++i) kinds[i] = static_cast<uint8_t>(materials[spheres[i].material].kind);
+        const size_t at = b.data.size();
+        b.data.resize(at + kinds.size() / 4);
+        std::memcpy(b.data.data() + at, kinds.data(), kinds.size());
+        // dielectric constants per sphere index (raytracer.hxx:166-174 and the Schlick ratio
+        // :47): {1 / ior, (1 - ior) / (1 + ior), (1 - 1/ior) / (1 + 1/ior), shortcut}, the same
+        // binary32 operations the kernel would run (this file is built with -ffp-contract=off);
+        // and the sphere's walk-shortcut word (shortcut_words; as raw bits)
+        for (uint32_t i = 0; i < n_spheres; ++i) {
+            const rt_material &mt = materials[spheres[i].material];
+            float dc[4] = {0.f, 0.f, 0.f, 0.f};
+            if (mt.kind == RT_DIELECTRIC) {
+                const float ior = mt.param, inv = 1.f / ior;
+                dc[0] = inv;
+                dc[1] = (1.f - ior) / (1.f + ior);
+                dc[2] = (1.f - inv) / (1.f + inv);
+                std::memcpy(&dc[3], &shortcut[i], 4);
+            }
+            b.data.insert(b.data.end(), dc, dc + 4);
+        }
+    }
+    d.geom = scene_geometry(spheres, d.blobs[1]);
+    d.has_geom = d.blobs[1].n_clusters != 0u;
+    d.in_fast_range = true;
+    for (uint32_t i = 0; i < n_spheres; ++i) {
+        for (float v : {spheres[i].center[0], spheres[i].center[1], spheres[i].center[2], spheres[i].radius})
+            if (!(std::fabs(v) <= 0x1p19f)) d.in_fast_range = false;
+        // the hit normal's short division by r (rt_kernel.hip div3_short) needs |r| >= 2^-40
+        if (!(std::fabs(spheres[i].radius) >= 0x1p-40f)) d.in_fast_range = false;
+    }
+    // the windows, then the empty set; a scene without spheres keeps one empty window
+    d.trap = trap_windows(spheres, n_spheres, materials);
+    const size_t nw = std::max<size_t>(n_spheres, 1u);
+    d.trap.resize(4 * nw);
+    for (size_t i = (opt.diag & RT_DIAG_NO_TRAP_END) ? 0 : nw; i < 2 * nw; ++i) {
+        d.trap[2 * i] = 1.f;
+        d.trap[2 * i + 1] = 0.f;
+    }
+    if (n_spheres == 0) { d.trap[0] = 1.f; d.trap[1] = 0.f; }
+    // the culled scene's geometry as classify_tiles_kernel reads it (rt_tiles.h KTiles::geom)
+    const scene_geom &g = d.geom;
+    d.geom_words.assign(g.root, g.root + 6);
+    d.geom_words.insert(d.geom_words.end(), g.boxes.begin(), g.boxes.end());
+    static_assert(sizeof(rt_sphere) == 5 * sizeof(float), "rt_sphere records follow the boxes as words");
+    const size_t at = d.geom_words.size();
+    d.geom_words.resize(at + 5u * g.always.size());
+    if (!g.always.empty()) std::memcpy(d.geom_words.data() + at, g.always.data(), g.always.size() * sizeof(rt_sphere));
+}
+
+// Puts a derivation on the device and into the scene's fields. Every buffer that is too small (all
+// of them at creation) is allocated first, then everything is uploaded, then the scene's pointers
+// and counts are swapped: an allocation that fails leaves the scene as it was. The device is idle
+// (an update has waited for it; at creation nothing runs yet). `first`: the creation, which also
+// makes the two sphere tables, both with the records; an update swaps them and writes the current one.
+int install_scene(rt_scene *sc, SceneDerived &d, bool first)
+{
+    struct Buf { void **ptr; size_t *cap; const void *src; size_t bytes; void *fresh; };
+    Buf bufs[4] = {{(void **)&sc->blob[0], &sc->blob_cap[0], d.blobs[0].data.data(), d.blobs[0].data.size() * 4, nullptr},
+                   {(void **)&sc->blob[1], &sc->blob_cap[1], d.blobs[1].data.data(), d.blobs[1].data.size() * 4, nullptr},
+                   {(void **)&sc->trap, &sc->trap_cap, d.trap.data(), d.trap.size() * sizeof(float), nullptr},
+                   {(void **)&sc->d_geom, &sc->geom_cap, d.geom_words.data(), d.geom_words.size() * sizeof(float), nullptr}};
+    const size_t table_bytes = d.table.size() * sizeof(float);
+    void *tables[2] = {nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (Buf &b : bufs)
+        if (e == hipSuccess && (!*b.ptr || *b.cap < b.bytes)) e = hipMalloc(&b.fresh, std::max<size_t>(b.bytes, 256));
+    for (int t = 0; first && t < 2 && e == hipSuccess; ++t) e = hipMalloc(&tables[t], std::max<size_t>(table_bytes, 256));
+    for (Buf &b : bufs)
+        if (e == hipSuccess && b.bytes) e = hipMemcpy(b.fresh ? b.fresh : *b.ptr, b.src, b.bytes, hipMemcpyHostToDevice);
+    // (the table an update writes is the older one: it becomes the current one below)
+    float *const write_table = first ? static_cast<float *>(tables[0]) : sc->centres[1];
+    if (e == hipSuccess && table_bytes) e = hipMemcpy(write_table, d.table.data(), table_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && first && table_bytes) e = hipMemcpy(tables[1], d.table.data(), table_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        for (Buf &b : bufs)
+            if (b.fresh) (void)hipFree(b.fresh);
+        for (void *t : tables)
+            if (t) (void)hipFree(t);
+        return fail(RT_ERR_DEVICE, std::string("scene upload: ") + hipGetErrorString(e));
+    }
+    for (Buf &b : bufs)
+        if (b.fresh) {
+            if (*b.ptr) (void)hipFree(*b.ptr);
+            *b.ptr = b.fresh;
+            *b.cap = std::max<size_t>(b.bytes, 256);
+        }
+    if (first) sc->centres[0] = static_cast<float *>(tables[0]), sc->centres[1] = static_cast<float *>(tables[1]);
+    else std::swap(sc->centres[0], sc->centres[1]);
+    for (int b = 0; b < 2; ++b) {
+        const blob_t &bl = d.blobs[b];
+        sc->blob_units[b] = static_cast<uint32_t>(bl.data.size() / 4);
+        sc->n_geo[b] = bl.n_geo;
+        sc->n_always[b] = bl.n_always;
+        sc->n_clusters[b] = bl.n_clusters;
+        sc->clus_offset[b] = bl.clus_offset;
+        sc->clus_pad[b] = bl.clus_pad;
+        sc->n_supers[b] = bl.n_supers;
+        sc->supers_offset[b] = bl.supers_offset;
+        sc->shade_offset[b] = bl.shade_offset;
+    }
+    sc->geom_boxes = static_cast<uint32_t>(d.geom.boxes.size() / 6u);
+    sc->geom_always = static_cast<uint32_t>(d.geom.always.size());
+    sc->geom_root = d.geom.has_root;
+    sc->geom_pad = d.geom.clus_pad;
+    sc->has_geom = d.has_geom;
+    sc->geom = d.has_geom ? std::move(d.geom) : scene_geom{};
+    sc->in_fast_range = d.in_fast_range;
+    sc->cur_table.swap(d.table);
+    sc->cur_flat.swap(d.flat);
+    return RT_OK;
+}
+
+// The caches keyed by a blob's size, as a fresh scene has them: unknown.
+void reset_occupancy(rt_scene *sc)
+{
+    for (auto &r : sc->occ) for (auto &x : r) x[0] = x[1] = -1;
+    for (auto &r : sc->occ_pairs) r[0] = r[1] = -1;
+    for (int &x : sc->occ_deep_wide) x = -1;
+    for (auto &r : sc->occ_aov) r[0] = r[1] = -1;
+    sc->occ_wave[0] = sc->occ_wave[1] = -1;
+}
+
 } // namespace
 
 extern "C" {
@@ -397,7 +584,8 @@ int rt_scene_destroy(rt_scene *sc)
     }
     if (sc->ev_tail) (void)hipEventDestroy(sc->ev_tail);
     if (sc->ev_sky) (void)hipEventDestroy(sc->ev_sky);
-    for (void *p : {(void *)sc->blob[0], (void *)sc->blob[1], (void *)sc->dbg, (void *)sc->acc, (void *)sc->mom, (void *)sc->queue_ctr, sc->wq, (void *)sc->trap})
+    for (void *p : {(void *)sc->blob[0], (void *)sc->blob[1], (void *)sc->dbg, (void *)sc->acc, (void *)sc->mom, (void *)sc->queue_ctr, sc->wq, (void *)sc->trap,
+                    (void *)sc->centres[0], (void *)sc->centres[1]})
         if (p) (void)hipFree(p);
     for (float *p : sc->slots)
         if (p) (void)hipFree(p);
@@ -442,121 +630,21 @@ int rt_scene_create_ex(const rt_sphere *spheres, uint32_t n_spheres, const rt_ma
     } else if (int rc = default_options(opt); rc) {
         return rc;
     }
-    for (uint32_t i = 0; i < n_spheres; ++i)
-        if (spheres[i].material >= n_materials)
-            return fail(RT_ERR_INVALID, "rt_scene_create: sphere " + std::to_string(i) + " has material index " +
-                                            std::to_string(spheres[i].material) + " >= " + std::to_string(n_materials));
-    for (uint32_t i = 0; i < n_materials; ++i)
-        if (materials[i].kind > RT_DIELECTRIC)
-            return fail(RT_ERR_INVALID, "rt_scene_create: material " + std::to_string(i) + " has unknown kind");
+    if (int rc = check_records("rt_scene_create", spheres, n_spheres, materials, n_materials); rc != RT_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RT_ERR_DEVICE, "rt_scene_create: no HIP device");
     if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "rt_scene_create: bad device index");
     RT_HIP(hipSetDevice(device));
 
-    std::vector<float> hit(static_cast<size_t>(std::max(n_spheres, 1u)) * 12, 0.f);
-    for (uint32_t i = 0; i < n_spheres; ++i) {
-        const rt_sphere &sp = spheres[i];
-        const rt_material &mt = materials[sp.material];
-        float *h = hit.data() + 12 * static_cast<size_t>(i);
-        h[0] = sp.center[0]; h[1] = sp.center[1]; h[2] = sp.center[2]; h[3] = sp.radius;
-        h[4] = mt.albedo[0]; h[5] = mt.albedo[1]; h[6] = mt.albedo[2]; h[7] = mt.param;
-        std::memcpy(h + 8, &mt.kind, 4);
-    }
-    blob_t blobs[2] = {build_blob(spheres, n_spheres, false, opt.cluster_size),
-                       build_blob(spheres, n_spheres, true, opt.cluster_size)};
-    const std::vector<uint32_t> shortcut =
-        shortcut_words(spheres, n_spheres, materials, blobs[1], (opt.diag & RT_DIAG_NO_NEIGHBOURS) != 0);
-    // shading records join each blob (so they sit in LDS next to the geometry): per original
-    // sphere index {c, r}, {albedo, param}, then the material kinds as bytes, 16-B padded
-    for (blob_t &b : blobs) {
-        b.shade_offset = static_cast<uint32_t>(b.data.size() / 4);
-        for (uint32_t i = 0; i < n_spheres; ++i) b.data.insert(b.data.end(), hit.data() + 12 * static_cast<size_t>(i), hit.data() + 12 * static_cast<size_t>(i) + 8);
-        std::vector<uint8_t> kinds((n_spheres + 15u) / 16u * 16u, 0);
-        for (uint32_t i = 0; i < n_spheres; ++i) kinds[i] = static_cast<uint8_t>(materials[spheres[i].material].kind);
-        const size_t at = b.data.size();
-        b.data.resize(at + kinds.size() / 4);
-        std::memcpy(b.data.data() + at, kinds.data(), kinds.size());
-        // dielectric constants per sphere index (raytracer.hxx:166-174 and the Schlick ratio
-        // :47): {1 / ior, (1 - ior) / (1 + ior), (1 - 1/ior) / (1 + 1/ior), shortcut}, the same
-        // binary32 operations the kernel would run (this file is built with -ffp-contract=off);
-        // and the sphere's walk-shortcut word (shortcut_words; as raw bits)
-        for (uint32_t i = 0; i < n_spheres; ++i) {
-            const rt_material &mt = materials[spheres[i].material];
-            float dc[4] = {0.f, 0.f, 0.f, 0.f};
-            if (mt.kind == RT_DIELECTRIC) {
-                const float ior = mt.param, inv = 1.f / ior;
-                dc[0] = inv;
-                dc[1] = (1.f - ior) / (1.f + ior);
-                dc[2] = (1.f - inv) / (1.f + inv);
-                std::memcpy(&dc[3], &shortcut[i], 4);
-            }
-            b.data.insert(b.data.end(), dc, dc + 4);
-        }
-    }
+    SceneDerived derived;
+    derive_scene(spheres, n_spheres, materials, opt, derived);
     rt_scene *sc = new rt_scene();
     sc->opt = opt;
-    if (blobs[1].n_clusters) {
-        sc->geom = scene_geometry(spheres, blobs[1]);
-        sc->has_geom = true;
-    }
-    for (auto &r : sc->occ) for (auto &x : r) x[0] = x[1] = -1;
-    for (auto &r : sc->occ_pairs) r[0] = r[1] = -1;
-    sc->in_fast_range = true;
-    for (uint32_t i = 0; i < n_spheres; ++i) {
-        for (float v : {spheres[i].center[0], spheres[i].center[1], spheres[i].center[2], spheres[i].radius})
-            if (!(std::fabs(v) <= 0x1p19f)) sc->in_fast_range = false;
-        // the hit normal's short division by r (rt_kernel.hip div3_short) needs |r| >= 2^-40
-        if (!(std::fabs(spheres[i].radius) >= 0x1p-40f)) sc->in_fast_range = false;
-    }
+    reset_occupancy(sc);
     sc->device = device;
     sc->n_spheres = n_spheres;
     sc->n_materials = n_materials;
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        RT_HIP(hipMalloc(dst, bytes));
-        RT_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return RT_OK;
-    };
-    int rc = RT_OK;
-    for (int b = 0; b < 2 && rc == RT_OK; ++b) {
-        rc = up((void **)&sc->blob[b], blobs[b].data.data(), blobs[b].data.size() * 4);
-        sc->blob_units[b] = static_cast<uint32_t>(blobs[b].data.size() / 4);
-        sc->n_geo[b] = blobs[b].n_geo;
-        sc->n_always[b] = blobs[b].n_always;
-        sc->n_clusters[b] = blobs[b].n_clusters;
-        sc->clus_offset[b] = blobs[b].clus_offset;
-        sc->clus_pad[b] = blobs[b].clus_pad;
-        sc->n_supers[b] = blobs[b].n_supers;
-        sc->supers_offset[b] = blobs[b].supers_offset;
-        sc->shade_offset[b] = blobs[b].shade_offset;
-    }
-    if (rc == RT_OK) {
-        // the windows, then the empty set; a scene without spheres keeps one empty window
-        std::vector<float> trap = trap_windows(spheres, n_spheres, materials);
-        const size_t nw = std::max<size_t>(n_spheres, 1u);
-        trap.resize(4 * nw);
-        for (size_t i = (opt.diag & RT_DIAG_NO_TRAP_END) ? 0 : nw; i < 2 * nw; ++i) {
-            trap[2 * i] = 1.f;
-            trap[2 * i + 1] = 0.f;
-        }
-        if (n_spheres == 0) { trap[0] = 1.f; trap[1] = 0.f; }
-        rc = up((void **)&sc->trap, trap.data(), trap.size() * sizeof(float));
-    }
-    if (rc == RT_OK) {
-        // the culled scene's geometry as classify_tiles_kernel reads it (rt_tiles.h KTiles::geom)
-        const scene_geom g = scene_geometry(spheres, blobs[1]);
-        std::vector<float> words(g.root, g.root + 6);
-        words.insert(words.end(), g.boxes.begin(), g.boxes.end());
-        static_assert(sizeof(rt_sphere) == 5 * sizeof(float), "rt_sphere records follow the boxes as words");
-        const size_t at = words.size();
-        words.resize(at + 5u * g.always.size());
-        if (!g.always.empty()) std::memcpy(words.data() + at, g.always.data(), g.always.size() * sizeof(rt_sphere));
-        sc->geom_boxes = static_cast<uint32_t>(g.boxes.size() / 6u);
-        sc->geom_always = static_cast<uint32_t>(g.always.size());
-        sc->geom_root = g.has_root;
-        sc->geom_pad = g.clus_pad;
-        rc = up((void **)&sc->d_geom, words.data(), words.size() * sizeof(float));
-    }
+    int rc = install_scene(sc, derived, true);
     if (rc == RT_OK) {
         hipError_t e = hipMalloc((void **)&sc->queue_ctr, kCtrWords * sizeof(uint32_t));
         if (e != hipSuccess) rc = fail(RT_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
@@ -1806,6 +1894,7 @@ int rt_scene_usage_get(const rt_scene *sc, rt_scene_usage *out)
     uint64_t fixed = kCtrWords * sizeof(uint32_t) + (sc->dbg ? rt::kDbgWords * sizeof(unsigned long long) : 0u);
     for (int b = 0; b < 2; ++b) fixed += static_cast<uint64_t>(sc->blob_units[b]) * 16u;
     fixed += static_cast<uint64_t>(std::max(sc->n_spheres, 1u)) * 16u;  // the trap windows
+    fixed += static_cast<uint64_t>(sc->n_spheres) * 32u;                // the two sphere tables (rt_scene_motion)
     u.device_bytes = ws + fixed;
     u.workspace_bytes = ws;
     u.render_streams = sc->used_streams;
@@ -1819,6 +1908,78 @@ int rt_scene_usage_get(const rt_scene *sc, rt_scene_usage *out)
     u.static_lds_bytes = static_cast<uint32_t>(sc->static_lds[1]);
     u.max_lds_bytes = static_cast<uint32_t>(sc->max_lds);
     *out = u;
+    return RT_OK;
+}
+
+// New records into a live scene (include/rt_api.h): the checks, the comparison
+// with the current records, the derivation on the host, then the one wait for the device, the
+// upload and the swap, and at the end what was keyed by the old geometry is dropped.
+int rt_scene_update(rt_scene *sc, const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
+                    uint32_t n_materials)
+{
+    const char *const who = "rt_scene_update";
+    if (n_spheres && !spheres) return fail(RT_ERR_INVALID, "rt_scene_update: spheres is null");
+    if (!materials) return fail(RT_ERR_INVALID, "rt_scene_update: materials is null");
+    if (!n_materials) return fail(RT_ERR_INVALID, "rt_scene_update: n_materials is 0");
+    if (int rc = check_records(who, spheres, n_spheres, materials, n_materials); rc != RT_OK) return rc;
+    if (!sc) return fail(RT_ERR_INVALID, "rt_scene_update: scene is null");
+    if (n_spheres != sc->n_spheres)
+        return fail(RT_ERR_INVALID, "rt_scene_update: n_spheres is " + std::to_string(n_spheres) + ", the scene has " +
+                                        std::to_string(sc->n_spheres) + " (ids link the frames: the count is fixed)");
+    // what changed, by the bits
+    bool geometry = false, appearance = false;
+    for (uint32_t i = 0; i < n_spheres; ++i) {
+        const rt_material &mt = materials[spheres[i].material];
+        float row[4] = {spheres[i].center[0], spheres[i].center[1], spheres[i].center[2], spheres[i].radius}, flat[5];
+        std::memcpy(flat, &mt.kind, 4);
+        std::memcpy(flat + 1, mt.albedo, 12);
+        flat[4] = mt.param;
+        geometry = geometry || std::memcmp(row, sc->cur_table.data() + 4 * static_cast<size_t>(i), 16) != 0;
+        appearance = appearance || std::memcmp(flat, sc->cur_flat.data() + 5 * static_cast<size_t>(i), 20) != 0;
+    }
+    if (!geometry && !appearance) {
+        sc->n_materials = n_materials;
+        return RT_OK;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    SceneDerived derived;
+    derive_scene(spheres, n_spheres, materials, sc->opt, derived);
+    const auto t1 = std::chrono::steady_clock::now();
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    RT_HIP(hipSetDevice(sc->device));
+    // renders in flight read the blobs, the windows and the permutations: the device goes idle once
+    RT_HIP(hipDeviceSynchronize());
+    const auto t2 = std::chrono::steady_clock::now();
+    if (int rc = install_scene(sc, derived, false); rc != RT_OK) {
+        (void)hipSetDevice(prev);
+        return rc;
+    }
+    sc->n_materials = n_materials;
+    // the orders of the old geometry leave; a pool slot is free again (nothing reads it: the device is idle)
+    for (auto &o : sc->orders)
+        if (o.d_perm && o.slot < 0) (void)hipFree(o.d_perm);
+    sc->orders.clear();
+    for (auto &s : sc->perm_pool) s.read_valid = false;
+    sc->deep_off.clear();
+    reset_occupancy(sc);
+    if (geometry) ++sc->geometry_epoch;
+    if (appearance) ++sc->appearance_epoch;
+    (void)hipSetDevice(prev);
+    if (sc->opt.diag & RT_DIAG_VERBOSE) {
+        const auto t3 = std::chrono::steady_clock::now();
+        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        std::fprintf(stderr, "rt_scene_update: derive %.3f ms, device wait %.3f ms, upload and swap %.3f ms\n", ms(t0, t1),
+                     ms(t1, t2), ms(t2, t3));
+    }
+    return RT_OK;
+}
+
+int rt_scene_motion(rt_scene *sc, rt_scene_motion_t *out)
+{
+    if (!sc || !out) return fail(RT_ERR_INVALID, "rt_scene_motion: null argument");
+    *out = rt_scene_motion_t{static_cast<uint32_t>(sizeof(rt_scene_motion_t)), sc->n_spheres, sc->centres[0], sc->centres[1],
+                             sc->geometry_epoch, sc->appearance_epoch};
     return RT_OK;
 }
 

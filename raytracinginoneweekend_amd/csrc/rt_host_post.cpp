@@ -322,28 +322,60 @@ int check_temporal(const rt_temporal_params *p, const rt_camera *cam, const rt_c
     return RT_OK;
 }
 
-// Synchronous temporal accumulation of host planes: the current planes, the previous ones, then
-// the outputs.
-int temporal_host(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
-                  const rt_temporal_buffers *buffers, rt_stats *stats)
+// The motion record's checks, after check_temporal's and before any HIP call; adds the tables to
+// the kernel's record (null tables of a scene without spheres: a pointer that is never read,
+// so that the launch still takes the motion kernel, in which every id is out of range).
+int check_temporal_motion(const rt_temporal_motion_t *m, const rt_temporal_buffers *b, bool device_call, const char *who,
+                          rt::KTemporal *k)
 {
+    const std::string w = std::string(who) + ": ";
+    if (!m) return fail(RT_ERR_INVALID, w + "motion is null");
+    if (m->size != sizeof(rt_temporal_motion_t)) return fail(RT_ERR_INVALID, w + "motion.size is not sizeof(rt_temporal_motion_t)");
+    if (m->n_spheres && !m->centres) return fail(RT_ERR_INVALID, w + "motion.centres is null with n_spheres > 0");
+    if (m->n_spheres && !m->prev_centres) return fail(RT_ERR_INVALID, w + "motion.prev_centres is null with n_spheres > 0");
+    if (device_call && m->n_spheres && ((reinterpret_cast<uintptr_t>(m->centres) | reinterpret_cast<uintptr_t>(m->prev_centres)) & 15u))
+        return fail(RT_ERR_INVALID, w + "motion.centres and motion.prev_centres must be 16-byte aligned");
+    const struct { const char *name; const void *ptr; } out[3] = {{"out_color", b->out_color}, {"out_variance", b->out_variance},
+                                                                 {"out_history", b->out_history}};
+    for (const auto &o : out) {
+        if (m->n_spheres && o.ptr == m->centres) return fail(RT_ERR_INVALID, w + "motion.centres is also the output plane " + o.name);
+        if (m->n_spheres && o.ptr == m->prev_centres) return fail(RT_ERR_INVALID, w + "motion.prev_centres is also the output plane " + o.name);
+    }
+    k->centres = m->n_spheres ? m->centres : k->beauty;
+    k->p_centres = m->n_spheres ? m->prev_centres : k->beauty;
+    k->n_spheres = m->n_spheres;
+    return RT_OK;
+}
+
+// Synchronous temporal accumulation of host planes: the current planes, the previous ones, the
+// outputs, then the two sphere tables of the stage with object motion (motion null: the static one).
+int temporal_host(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                  const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, bool with_motion, rt_stats *stats)
+{
+    const char *const who = with_motion ? "rt_temporal_motion" : "rt_temporal";
     rt::KTemporal k{};
-    if (int rc = check_temporal(params, camera, prev_camera, buffers, "rt_temporal", &k); rc != RT_OK) return rc;
+    if (int rc = check_temporal(params, camera, prev_camera, buffers, who, &k); rc != RT_OK) return rc;
+    if (with_motion)
+        if (int rc = check_temporal_motion(motion, buffers, false, who, &k); rc != RT_OK) return rc;
     const size_t n = static_cast<size_t>(params->width) * params->height;
     const rt_temporal_buffers &b = *buffers;
-    Plane planes[15] = {plane_in(b.beauty, 12),     plane_in(b.variance, 4),      plane_in(b.normal, 12),
+    const uint32_t n_sph = with_motion ? motion->n_spheres : 0u;
+    Plane planes[17] = {plane_in(b.beauty, 12),     plane_in(b.variance, 4),      plane_in(b.normal, 12),
                         plane_in(b.depth, 4),       plane_in(b.alpha, 4),         plane_in(b.sphere_id, 4),
                         plane_in(b.prev_color, 12), plane_in(b.prev_variance, 4), plane_in(b.prev_history, 4),
                         plane_in(b.prev_normal, 12), plane_in(b.prev_depth, 4),   plane_in(b.prev_sphere_id, 4),
-                        plane_out(b.out_color, 12), plane_out(b.out_variance, 4), plane_out(b.out_history, 4)};
+                        plane_out(b.out_color, 12), plane_out(b.out_variance, 4), plane_out(b.out_history, 4),
+                        plane_in(n_sph ? motion->centres : nullptr, 16), plane_in(n_sph ? motion->prev_centres : nullptr, 16)};
+    planes[15].n_px = planes[16].n_px = n_sph;
     SyncCall call;
-    const int rc = call.run({"rt_temporal", planes, 15, n, {n, 1}}, [&] {
+    const int rc = call.run({who, planes, 17, n, {n, 1}}, [&] {
         auto f = [&](int i) { return planes[i].as<float>(); };
         k.beauty = f(0), k.variance = f(1), k.normal = f(2), k.depth = f(3), k.alpha = f(4), k.id = planes[5].as<uint32_t>();
         k.p_color = f(6), k.p_variance = f(7), k.p_history = f(8), k.p_normal = f(9), k.p_depth = f(10);
         k.p_id = planes[11].as<uint32_t>();
         k.o_color = f(12), k.o_variance = f(13), k.o_history = f(14);
-        return hip_rc(rt::launch_temporal(k, nullptr), "rt_temporal");
+        if (with_motion) k.centres = n_sph ? f(15) : f(0), k.p_centres = n_sph ? f(16) : f(0);
+        return hip_rc(rt::launch_temporal(k, nullptr), who);
     });
     if (rc == RT_OK && stats) timed_stats(*stats, call);
     return rc;
@@ -451,6 +483,8 @@ struct rt_preview {
     bool up_written = false;       // a frame has written them
     uint32_t cur = 0;
     rt_camera prev_camera{};
+    // the scene's epochs at the session's last frame (rt_scene_motion)
+    uint64_t geometry_epoch = 0, appearance_epoch = 0;
     rt_preview_planes_t last{};    // last.frames: frames since creation or the last reset
 };
 
@@ -545,6 +579,14 @@ int preview_frame(rt_preview &pv, const rt_camera *camera, uint64_t seed, float 
     const bool demod = (P.flags & RT_PREVIEW_DEMODULATE) != 0u;
     const uint32_t c = pv.cur, o = c ^ 1u;
     const rt_preview::Guides &g = pv.g[c];
+    // The scene since the session's last frame (rt_scene_update): other colours, or more than one
+    // step of the geometry, and the frame has no history, as after rt_preview_reset; one step of the
+    // geometry and the temporal stage takes the scene's two tables.
+    rt_scene_motion_t sm{};
+    if (int rc = rt_scene_motion(pv.scene, &sm); rc != RT_OK) return rc;
+    const bool restart = pv.last.frames != 0u && (sm.appearance_epoch != pv.appearance_epoch ||
+                                                 sm.geometry_epoch - pv.geometry_epoch > 1u);
+    const bool moved = !restart && pv.last.frames != 0u && sm.geometry_epoch != pv.geometry_epoch;
     // 1 render
     const rt_params rp{P.width, P.height, P.spp, P.max_depth, seed, 0u, 1u, 0u, 0u};
     if (int rc = rt_render_var_device(pv.scene, camera, &rp, pv.beauty, pv.variance, st, nullptr); rc != RT_OK) return rc;
@@ -558,7 +600,7 @@ int preview_frame(rt_preview &pv, const rt_camera *camera, uint64_t seed, float 
     }
     // 3 temporal
     if (temporal) {
-        const bool prev = pv.last.frames != 0u;
+        const bool prev = pv.last.frames != 0u && !restart;
         const rt_preview::History &hp = pv.h[o];
         const rt_preview::Guides &gp = pv.g[o];
         float *const out_c = feedback ? pv.acc_color : pv.h[c].color, *const out_v = feedback ? pv.acc_variance : pv.h[c].variance;
@@ -569,6 +611,11 @@ int preview_frame(rt_preview &pv, const rt_camera *camera, uint64_t seed, float 
                                      out_c, out_v, pv.h[c].history};
         rt::KTemporal k{};
         if (int rc = check_temporal(&P.temporal, camera, prev ? &pv.prev_camera : nullptr, &tb, who, &k); rc != RT_OK) return rc;
+        if (moved) {
+            const rt_temporal_motion_t tm{static_cast<uint32_t>(sizeof(rt_temporal_motion_t)), sm.n_spheres, sm.centres,
+                                          sm.prev_centres};
+            if (int rc = check_temporal_motion(&tm, &tb, true, who, &k); rc != RT_OK) return rc;
+        }
         RT_HIP(rt::launch_temporal(k, st));
         color = out_c, variance = out_v;
     }
@@ -602,7 +649,8 @@ int preview_frame(rt_preview &pv, const rt_camera *camera, uint64_t seed, float 
     }
     // what the frame wrote, and what the next one reprojects
     rt_preview_planes_t &l = pv.last;
-    l.frames += 1u;
+    l.frames = restart ? 1u : l.frames + 1u;
+    pv.geometry_epoch = sm.geometry_epoch, pv.appearance_epoch = sm.appearance_epoch;
     l.out_color = color, l.out_variance = variance, l.out_history = temporal ? pv.h[c].history : nullptr;
     l.albedo = pv.albedo, l.normal = g.normal, l.depth = g.depth, l.alpha = pv.alpha, l.sphere_id = g.id;
     if (temporal) {
@@ -811,7 +859,23 @@ int rt_temporal_device(const rt_temporal_params *params, const rt_camera *camera
 int rt_temporal(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
                 const rt_temporal_buffers *buffers, rt_stats *stats)
 {
-    return temporal_host(params, camera, prev_camera, buffers, stats);
+    return temporal_host(params, camera, prev_camera, buffers, nullptr, false, stats);
+}
+
+int rt_temporal_motion_device(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                              const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, void *stream)
+{
+    rt::KTemporal k{};
+    if (int rc = check_temporal(params, camera, prev_camera, buffers, "rt_temporal_motion_device", &k); rc != RT_OK) return rc;
+    if (int rc = check_temporal_motion(motion, buffers, true, "rt_temporal_motion_device", &k); rc != RT_OK) return rc;
+    RT_HIP(rt::launch_temporal(k, static_cast<hipStream_t>(stream)));
+    return RT_OK;
+}
+
+int rt_temporal_motion(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                       const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, rt_stats *stats)
+{
+    return temporal_host(params, camera, prev_camera, buffers, motion, true, stats);
 }
 
 int rt_upsample_params_default(uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height, rt_upsample_params *out)

@@ -9,6 +9,14 @@
 // not known before the projection is done. include/rt_api.h states the arithmetic; every operation
 // below is a separate binary32 operation, in the contract's order. HISTORY = false is the frame
 // without history: a copy.
+//
+// MOTION (rt_temporal_motion_device): a surface pixel's first hit is carried back by
+// its sphere's motion m = C - C' before it is projected: the two table rows of the pixel's id are read
+// from global memory, one 16-byte load each (the tables are small and stay in cache). A form whose
+// workgroup first staged {m, same-radius flag} of every sphere in LDS was measured and was slower
+// (31.5 against 23.4 us at 1280x720 with 486 spheres: every workgroup pays for the whole table, and 32
+// KiB of LDS cost occupancy; profiles/motion/lds_form.diff keeps it). MOTION = false is the static stage:
+// its machine code is what it was before the parameter existed.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -22,7 +30,7 @@ __device__ __forceinline__ float tp_dot(const float *a, float x, float y, float 
     return (a[0] * x + a[1] * y) + a[2] * z;
 }
 
-template <bool HISTORY>
+template <bool HISTORY, bool MOTION>
 __global__ __launch_bounds__(256) void temporal_accumulate(const KTemporal k)
 {
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
@@ -44,16 +52,33 @@ __global__ __launch_bounds__(256) void temporal_accumulate(const KTemporal k)
             const float dy = (k.a[1] + k.hor[1] * u) + k.ver[1] * m;
             const float dz = (k.a[2] + k.hor[2] * u) + k.ver[2] * m;
             float qx = dx, qy = dy, qz = dz;
+            bool moved_ok = true;  // MOTION: the sphere is in the tables and kept its radius
             if (surface) {
                 const float t = k.depth[p];
-                qx = (k.o[0] + t * dx) - k.basis[9];
-                qy = (k.o[1] + t * dy) - k.basis[10];
-                qz = (k.o[2] + t * dz) - k.basis[11];
+                if (MOTION) {
+                    // an id outside the tables reads neither; a resized sphere restarts
+                    const uint32_t sid = k.id[p];
+                    float mx = 0.f, my = 0.f, mz = 0.f;
+                    moved_ok = sid < k.n_spheres;
+                    if (moved_ok) {
+                        const float4 c = reinterpret_cast<const float4 *>(k.centres)[sid];
+                        const float4 b = reinterpret_cast<const float4 *>(k.p_centres)[sid];
+                        mx = c.x - b.x, my = c.y - b.y, mz = c.z - b.z;
+                        moved_ok = __float_as_uint(c.w) == __float_as_uint(b.w);
+                    }
+                    qx = ((k.o[0] + t * dx) - mx) - k.basis[9];
+                    qy = ((k.o[1] + t * dy) - my) - k.basis[10];
+                    qz = ((k.o[2] + t * dz) - mz) - k.basis[11];
+                } else {
+                    qx = (k.o[0] + t * dx) - k.basis[9];
+                    qy = (k.o[1] + t * dy) - k.basis[10];
+                    qz = (k.o[2] + t * dz) - k.basis[11];
+                }
             }
             const float pa = tp_dot(k.basis, qx, qy, qz);
             const float pb = tp_dot(k.basis + 3, qx, qy, qz);
             const float ga = tp_dot(k.basis + 6, qx, qy, qz);
-            if (ga > 0.0f) {
+            if (ga > 0.0f && (!MOTION || moved_ok)) {
                 const float px = (pa / ga) * fw - 0.5f;
                 const float py = (1.0f - pb / ga) * fh - 0.5f;
                 if (px > -1.0f && px < fw && py > -1.0f && py < fh) {
@@ -111,8 +136,10 @@ hipError_t launch_temporal(const KTemporal &k, hipStream_t stream)
 {
     void *args[] = {const_cast<KTemporal *>(&k)};
     const dim3 grid((k.W + 63) / 64, (k.H + 3) / 4);
-    const void *fn = k.p_color ? reinterpret_cast<const void *>(&temporal_accumulate<true>)
-                               : reinterpret_cast<const void *>(&temporal_accumulate<false>);
+    // the motion kernel from a table pointer
+    const void *fn = !k.p_color ? reinterpret_cast<const void *>(&temporal_accumulate<false, false>)
+                     : k.centres ? reinterpret_cast<const void *>(&temporal_accumulate<true, true>)
+                                 : reinterpret_cast<const void *>(&temporal_accumulate<true, false>);
     return hipLaunchKernel(fn, grid, dim3(64, 4), args, 0, stream);
 }
 

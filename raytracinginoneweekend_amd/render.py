@@ -334,29 +334,51 @@ def reproject_basis(camera):
     return out
 
 
-def temporal_device(pointers, params, camera, prev_camera, stream=None):
+def sphere_table(scene):
+    """The [n][4] float32 array {cx, cy, cz, radius} of a scene's spheres, row i = sphere i: what
+    rt_temporal_motion takes as `centres` / `prev_centres` and a DeviceScene keeps."""
+    s, _ = _scene_arrays(scene)
+    t = np.empty((len(s), 4), dtype=np.float32)
+    t[:, :3] = s["center"]
+    t[:, 3] = s["radius"]
+    return t
+
+
+def temporal_motion_record(centres, prev_centres, n_spheres):
+    """An rt_temporal_motion_t record from two table addresses (0 or None: not given)."""
+    return abi.RtTemporalMotion(C.sizeof(abi.RtTemporalMotion), n_spheres, centres or None, prev_centres or None)
+
+
+def temporal_device(pointers, params, camera, prev_camera, stream=None, motion=None):
     """Enqueue rt_temporal_device on `stream`: `pointers` is a dict plane name -> device address on
     the current device (temporal_buffers; the prev_ planes all absent: no history yet), `params` an
     rt_temporal_params record, `camera` and `prev_camera` the two frames' cameras (prev_camera may be
-    None without history). One launch, no host synchronisation."""
+    None without history). One launch, no host synchronisation. motion: (centres address,
+    prev_centres address, n_spheres) of two device tables: rt_temporal_motion_device, the stage with
+    object motion."""
     rec = temporal_buffers(pointers)
-    check(lib().rt_temporal_device(C.byref(params), C.byref(_cam_record(camera)),
-                                   C.byref(_cam_record(prev_camera)) if prev_camera is not None else None,
-                                   C.byref(rec), C.c_void_p(stream or 0)))
+    cams = (C.byref(_cam_record(camera)), C.byref(_cam_record(prev_camera)) if prev_camera is not None else None)
+    if motion is not None:
+        m = temporal_motion_record(*motion)
+        check(lib().rt_temporal_motion_device(C.byref(params), *cams, C.byref(rec), C.byref(m), C.c_void_p(stream or 0)))
+        return
+    check(lib().rt_temporal_device(C.byref(params), *cams, C.byref(rec), C.c_void_p(stream or 0)))
 
 
 _TEMPORAL_CUR = ("beauty", "variance", "normal", "depth", "alpha", "sphere_id")
 _TEMPORAL_PREV = ("color", "variance", "history", "normal", "depth", "sphere_id")
 
 
-def temporal(cur, prev, camera, prev_camera, params=None, stats=None, **fields):
+def temporal(cur, prev, camera, prev_camera, params=None, stats=None, motion=None, **fields):
     """rt_temporal: the previous frame's history reprojected into the current
     frame and blended. cur: dict of the current frame's planes (beauty and variance as render_var
     returns them; normal, depth, alpha, sphere_id as render_aov does); prev: dict of the previous
     frame's (color, variance, history as this call returned them, or color after a filter level;
     normal, depth, sphere_id of that frame), or None: no history yet. Returns (color float32 (h, w,
     3), variance float32 (h, w), history float32 (h, w)). params: an rt_temporal_params record
-    (default: the library's for this size); `fields` as temporal_params takes them."""
+    (default: the library's for this size); `fields` as temporal_params takes them. motion:
+    (centres, prev_centres), two float32 (n, 4) tables as sphere_table makes them: rt_temporal_motion,
+    the stage with object motion."""
     if set(cur) != set(_TEMPORAL_CUR):
         raise KeyError(f"cur must hold exactly the planes {_TEMPORAL_CUR}, not {sorted(cur)}")
     if prev is not None and set(prev) != set(_TEMPORAL_PREV):
@@ -376,9 +398,17 @@ def temporal(cur, prev, camera, prev_camera, params=None, stats=None, **fields):
     out = {n: np.zeros((h, w, 3) if abi.TEMPORAL_PLANES[n][0] == 3 else (h, w), dtype=np.float32)
            for n in ("out_color", "out_variance", "out_history")}
     rec = temporal_buffers({n: a.ctypes.data for n, a in {**host, **out}.items()})
-    check(lib().rt_temporal(C.byref(p), C.byref(_cam_record(camera)),
-                            C.byref(_cam_record(prev_camera)) if prev_camera is not None else None, C.byref(rec),
-                            C.byref(stats) if stats is not None else None))
+    cams = (C.byref(_cam_record(camera)), C.byref(_cam_record(prev_camera)) if prev_camera is not None else None)
+    st = C.byref(stats) if stats is not None else None
+    if motion is not None:
+        tabs = [np.ascontiguousarray(t) for t in motion]
+        if len(tabs) != 2 or any(t.dtype != np.float32 or t.ndim != 2 or t.shape != (len(tabs[0]), 4) for t in tabs):
+            raise ValueError("motion must be two float32 (n, 4) tables of one length")
+        m = temporal_motion_record(tabs[0].ctypes.data if len(tabs[0]) else None,
+                                   tabs[1].ctypes.data if len(tabs[1]) else None, len(tabs[0]))
+        check(lib().rt_temporal_motion(C.byref(p), *cams, C.byref(rec), C.byref(m), st))
+    else:
+        check(lib().rt_temporal(C.byref(p), *cams, C.byref(rec), st))
     return out["out_color"], out["out_variance"], out["out_history"]
 
 
@@ -703,6 +733,22 @@ class DeviceScene:
                                        C.byref(options) if options is not None else None, C.byref(h)))
         self.handle = h
         self.device = device
+
+    def update(self, scene):
+        """rt_scene_update: new records into the live scene (the same number of spheres), in place;
+        its streams, workspaces and sessions stay. Synchronous."""
+        s, m = _scene_arrays(scene)
+        check(lib().rt_scene_update(self.handle, abi.ptr(s, C.POINTER(abi.RtSphere)), len(s),
+                                    abi.ptr(m, C.POINTER(abi.RtMaterial)), len(m)))
+        self.n_materials = len(m)
+
+    def motion(self):
+        """rt_scene_motion as a dict: n_spheres, the device addresses centres and prev_centres of the
+        two [n][4] tables (valid until the next update), geometry_epoch, appearance_epoch."""
+        r = abi.RtSceneMotion()
+        check(lib().rt_scene_motion(self.handle, C.byref(r)))
+        return {"n_spheres": r.n_spheres, "centres": r.centres or 0, "prev_centres": r.prev_centres or 0,
+                "geometry_epoch": r.geometry_epoch, "appearance_epoch": r.appearance_epoch}
 
     def render(self, camera, params, d_rgb, stream=None, d_segments=None):
         """Enqueue a render into device pointer d_rgb (int address) on `stream` (int handle).
