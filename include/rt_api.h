@@ -86,7 +86,12 @@ typedef struct rt_camera {
  * max_depth: bounce limit (raytracer::data::bounces_number = 64, src/raytracer.hxx:20).
  * seed: RNG seed. Each (pixel, sample) owns two PCG32 streams keyed by
  *       key = (y*width + x)*spp + s — data stream seq 2*seed, camera stream seq 2*seed+1 —
- *       so any row partition renders the same bits.
+ *       so any row partition renders the same bits. All 64 bits of the key
+ *       count (width*height < 2^32, so a key reaches 2^32 * spp). Of the seed, the low 62 bits
+ *       count: the streams' increments are ((2*seed) << 1) | 1 and ((2*seed + 1) << 1) | 1
+ *       modulo 2^64, which drops the seed's top two bits, so seeds s and s + 2^62 (and s + 2^63)
+ *       render the same bits. With RT_FLAG_CUDA_COMPAT only the low 32 bits of the seed count
+ *       (the variant's engine state x + y*width + seed is 32 bits wide and wraps).
  * Rows rendered: y_i = row_offset + i*row_stride for i in [0, num_rows). num_rows = 0
  *       means "all rows of the stride pattern below height".
  * Output layout: row-major RGB f32, 3 floats per pixel. With RT_FLAG_FULL_FRAME the

@@ -18,8 +18,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 REF = os.path.join(REPO, "oracle", "_ref")
 
-# (name, harness args, kind). Renders use the per-sample PCG engine (the GPU contract)
-# unless marked "mt" (the reference's verbatim shared mt19937 streams).
+# (name, harness args, kind[, seed]). Renders use the per-sample PCG engine (the GPU contract)
+# unless marked "mt" (the reference's verbatim shared mt19937 streams). seed: 1234 unless given.
+SEED = 1234
+WIDE_SEED = 1234 + 2 ** 32  # a high word in both stream increments
 RENDERS = [
     # config 1: simple scene 200x100 @1spp (the reference's CPU case)
     ("c1_simple_200x100_s1", ["--scene", "simple", "--w", "200", "--h", "100", "--spp", "1"], "pcg"),
@@ -42,6 +44,11 @@ RENDERS = [
                                         "--row0", "1133", "--rows", "1"], "pcg"),
     ("c5_huge_1280x720_row377_s1024", ["--scene", "@huge", "--w", "1280", "--h", "720", "--spp", "1024",
                                        "--row0", "377", "--rows", "1"], "pcg"),
+    # 64-bit words (tests/tools/wide_cases.py): a seed above 2^32 on the small frame, and one row of a
+    # frame of 2^32 - 65536 pixels with it: pixel index 2^31.7, stream keys 2^34.0
+    ("huge_64x36_s4_seedhi", ["--scene", "@huge", "--w", "64", "--h", "36", "--spp", "4"], "pcg", WIDE_SEED),
+    ("wide_huge_4096x1048560_row838848_s5_seedhi", ["--scene", "@huge", "--w", "4096", "--h", "1048560", "--spp", "5",
+                                                    "--row0", "838848", "--rows", "1"], "pcg", WIDE_SEED),
 ]
 # renders whose u8 frame is also written by the reference's own PPM writer (app::save_to_file)
 PPM = {"c1_simple_200x100_s1"}
@@ -69,13 +76,14 @@ def main():
     subprocess.run([pcg, "--scene", "simple", "--dump-scene", simple, "--w", "1", "--h", "1"], check=True)
     manifest["scenes"]["huge"] = {"file": "scene_huge_1234.bin", "seed": 1234, "sha256": sha(huge)}
     manifest["scenes"]["simple"] = {"file": "scene_simple.bin", "sha256": sha(simple)}
-    for name, args, kind in RENDERS:
+    for name, args, kind, *rest in RENDERS:
+        seed = rest[0] if rest else SEED
         args = [huge if a == "@huge" else a for a in args]
         f32 = os.path.join(HERE, name + ".f32")
         u8 = os.path.join(HERE, name + ".u8")
         exe = pcg if kind == "pcg" else mt
         ppm = os.path.join(HERE, name + ".ppm") if name in PPM else None
-        subprocess.run([exe] + args + ["--seed", "1234", "--threads", "8", "--out-f32", f32,
+        subprocess.run([exe] + args + ["--seed", str(seed), "--threads", "8", "--out-f32", f32,
                                        "--out-u8", u8] + (["--out-ppm", ppm] if ppm else []), check=True)
         a = dict(zip(args[::2], args[1::2]))
         scene = "huge" if a["--scene"] == huge else "simple"
@@ -85,7 +93,7 @@ def main():
         manifest["renders"][name] = {
             "scene": scene, "width": W, "height": H, "spp": int(a["--spp"]),
             "depth": int(a.get("--depth", 64)), "camera": a.get("--camera", "reference"),
-            "row_offset": row0, "row_stride": step, "num_rows": rows, "rng": kind, "seed": 1234,
+            "row_offset": row0, "row_stride": step, "num_rows": rows, "rng": kind, "seed": seed,
             "f32": name + ".f32", "u8": name + ".u8", "sha256_f32": sha(f32), "sha256_u8": sha(u8)}
         if ppm:
             manifest["renders"][name].update({"ppm": name + ".ppm", "sha256_ppm": sha(ppm)})
