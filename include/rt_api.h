@@ -715,6 +715,50 @@ int rt_temporal_motion_device(const rt_temporal_params *params, const rt_camera 
 int rt_temporal_motion(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
                        const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, rt_stats *stats);
 
+/* ---- the temporal stage with the history clamped to the frame's own colours ----
+ * rt_temporal_device (motion NULL: a static scene) or rt_temporal_motion_device (motion given) with
+ * history rectification ("variance clipping", Salvi 2016): the resampled history colour is pulled into
+ * the box mean +- gamma standard deviations of the current frame's colours in a (2 radius + 1)^2 window
+ * around the pixel, taken over the taps on the pixel's own sphere. Everything in the underlying stage's
+ * contract holds; one step is new, between the resample (step 5) and the blend (step 6), and it applies
+ * only to a pixel whose history exists (sumw >= 0.01f). All arithmetic is binary32, every operation
+ * rounded on its own, in the order written; sqrtf is the correctly rounded square root.
+ *   5b window With b = beauty(p) and id = sphere_id(p), from n = 0, m1[3] = 0, m2[3] = 0: the taps
+ *             q = (x + i, y + j), j = -radius..radius (outer loop), i = -radius..radius (inner loop). A
+ *             tap is skipped (nothing is added) when it lies outside the image or sphere_id(q) != id.
+ *             Otherwise n = n + 1.0f and per channel d = beauty(q)[c] - b[c];  m1[c] = m1[c] + d;
+ *             m2[c] = m2[c] + d * d. (The data are shifted by the centre, as §4.10's L_0, so that a flat
+ *             region does not cancel; the centre tap always counts, so n >= 1.)
+ *      box    per channel: mean = m1[c] / n;  ex2 = m2[c] / n;  s2 = fmaxf(0.0f, ex2 - mean * mean)
+ *             half = gamma * sqrtf(s2);  mu = b[c] + mean;  lo = mu - half;  hi = mu + half
+ *      clamp  C_h[c] = fminf(fmaxf(C_h[c], lo), hi), with C_h[c] = sum[c] / sumw of step 6
+ * The blend of step 6 uses this C_h. V_h, N_h, k and the outputs' layout are unchanged: a clamped
+ * history keeps its length and its variance (left out). The window reads beauty and
+ * sphere_id of the current frame only; no texel is read outside the image.
+ *
+ * Every argument is checked before any HIP call; RT_ERR_INVALID names the field: every check of the
+ * underlying stage (rt_temporal_motion_device's when motion is not NULL), then a null clip record or a
+ * wrong size, a radius outside 1..3, a negative or non-finite gamma, nonzero flags. With the prev_
+ * planes NULL the record is still checked and then unused: the call is rt_temporal_device's copy.     */
+typedef struct rt_temporal_clip_t {
+    uint32_t size;    /* sizeof(rt_temporal_clip_t)                                        */
+    uint32_t radius;  /* 1..3: the window is (2 radius + 1)^2 pixels of the current frame   */
+    float gamma;      /* >= 0, finite: half-width of the box in standard deviations         */
+    uint32_t flags;   /* none defined: must be 0                                            */
+} rt_temporal_clip_t;
+/* The defaults (DESIGN.md §4.17 records the sweep that chose them).                                  */
+int rt_temporal_clip_default(rt_temporal_clip_t *out);
+/* Device pointers (the tables of `motion` too); one launch on `stream`, no host synchronisation, no
+ * allocation. motion NULL: a static scene.                                                           */
+int rt_temporal_clip_device(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                            const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion,
+                            const rt_temporal_clip_t *clip, void *stream);
+/* Host pointers, synchronous, through the cached per-device context as rt_temporal and
+ * rt_temporal_motion: the window reads planes those calls already stage.                             */
+int rt_temporal_clip(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                     const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion,
+                     const rt_temporal_clip_t *clip, rt_stats *stats);
+
 /* ---- guided upsampling of a low-resolution frame ---------------------------------
  * The stage that brings a filtered image of lo_width x lo_height up to width x height: a joint-
  * bilateral upsample (Kopf et al. 2007) whose four bilinear taps are tested against first-hit guides
@@ -874,6 +918,15 @@ int rt_preview_frame_device(rt_preview *pv, const rt_camera *camera, uint64_t se
                             void *stream);
 /* The next frame has no history (as the first one). Nothing is enqueued.                          */
 int rt_preview_reset(rt_preview *pv);
+/* The history clamp of rt_temporal_clip_device as a switch of the session: from the
+ * next frame on, step 3 is rt_temporal_clip_device's launch with `clip` (a copy is kept) in the place of
+ * rt_temporal_device's, over the same planes (under RT_PREVIEW_DEMODULATE the window is taken over the
+ * illumination I, which is what the stage sees as its beauty) and, after one step of the scene's
+ * geometry, with the scene's two tables as today. clip NULL: off, as after creation. Ordinary and
+ * upscaled sessions alike. Nothing is enqueued and the history is kept. RT_ERR_INVALID: a null
+ * session, a session with RT_PREVIEW_NO_TEMPORAL (it has no temporal stage), and the record's own
+ * checks as rt_temporal_clip_device makes them (the session is then left as it was).              */
+int rt_preview_set_clip(rt_preview *pv, const rt_temporal_clip_t *clip);
 int rt_preview_planes(rt_preview *pv, rt_preview_planes_t *out);
 /* The bytes of the session's device allocation (the scene's own workspaces: rt_scene_usage_get). */
 int rt_preview_usage(const rt_preview *pv, uint64_t *bytes);

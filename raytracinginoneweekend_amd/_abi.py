@@ -176,6 +176,15 @@ class RtSceneMotion(C.Structure):
 assert C.sizeof(RtTemporalMotion) == 24 and C.sizeof(RtSceneMotion) == 40
 
 
+class RtTemporalClip(C.Structure):
+    """rt_temporal_clip_t (include/rt_api.h): the window and the box width of the temporal stage's
+    history clamp."""
+    _fields_ = [("size", C.c_uint32), ("radius", C.c_uint32), ("gamma", C.c_float), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(RtTemporalClip) == 16
+
+
 class RtUpsampleParams(C.Structure):
     """rt_upsample_params (include/rt_api.h): the guided upsample's two image sizes and tap tests."""
     _fields_ = [

@@ -101,6 +101,14 @@ def _declare(L):
                                                 P(abi.RtTemporalBuffers), P(abi.RtTemporalMotion), C.c_void_p]),
         "rt_temporal_motion": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera),
                                          P(abi.RtTemporalBuffers), P(abi.RtTemporalMotion), P(abi.RtStats)]),
+        "rt_temporal_clip_default": (C.c_int, [P(abi.RtTemporalClip)]),
+        "rt_temporal_clip_device": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera),
+                                              P(abi.RtTemporalBuffers), P(abi.RtTemporalMotion), P(abi.RtTemporalClip),
+                                              C.c_void_p]),
+        "rt_temporal_clip": (C.c_int, [P(abi.RtTemporalParams), P(abi.RtCamera), P(abi.RtCamera),
+                                       P(abi.RtTemporalBuffers), P(abi.RtTemporalMotion), P(abi.RtTemporalClip),
+                                       P(abi.RtStats)]),
+        "rt_preview_set_clip": (C.c_int, [C.c_void_p, P(abi.RtTemporalClip)]),
         "rt_scene_update": (C.c_int, [C.c_void_p, P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32]),
         "rt_scene_motion": (C.c_int, [C.c_void_p, P(abi.RtSceneMotion)]),
         "rt_upsample_params_default": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -278,7 +278,8 @@ struct KDenoiseVar {
 // record {A, B, G, o'}, both formed on the host. Object motion (rt_temporal_motion_device, DESIGN.md
 // §4.16): the two sphere tables, [n_spheres][4] {cx, cy, cz, r} now and at the previous frame
 // (centres null: the static stage). The motion's fields come last: the static instantiations read
-// the fields before them at the offsets they always had.
+// the fields before them at the offsets they always had. The history clamp (rt_temporal_clip_device,
+// DESIGN.md §4.17): the window's radius (0: no clamp) and gamma, after the motion's for the same reason.
 struct KTemporal {
     const float *beauty, *variance, *normal, *depth, *alpha;
     const uint32_t *id;
@@ -291,6 +292,8 @@ struct KTemporal {
     float alpha_min, max_history, normal_tol, depth_tol;
     const float *centres, *p_centres;
     uint32_t n_spheres;
+    uint32_t clip_radius;
+    float clip_gamma;
 };
 
 // The preview session's own kernels (rt_preview.hip; rt_preview_frame_device).

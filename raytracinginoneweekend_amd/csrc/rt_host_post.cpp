@@ -347,16 +347,38 @@ int check_temporal_motion(const rt_temporal_motion_t *m, const rt_temporal_buffe
     return RT_OK;
 }
 
+// rt_temporal_clip_default: the values scripts/clip_sweep.py chose
+constexpr uint32_t kClipRadius = 1;
+constexpr float kClipGamma = 0.5f;
+
+// The clip record's checks, after every check of the underlying stage and before any HIP call; adds
+// the window to the kernel's record (k null: the checks alone).
+int check_temporal_clip(const rt_temporal_clip_t *c, const char *who, rt::KTemporal *k)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!c) return fail(RT_ERR_INVALID, w + "clip is null");
+    if (c->size != sizeof(rt_temporal_clip_t)) return fail(RT_ERR_INVALID, w + "clip.size is not sizeof(rt_temporal_clip_t)");
+    if (c->radius < 1u || c->radius > 3u) return fail(RT_ERR_INVALID, w + "clip.radius must be 1..3");
+    if (!std::isfinite(c->gamma) || c->gamma < 0.f) return fail(RT_ERR_INVALID, w + "clip.gamma must be finite and not negative");
+    if (c->flags) return fail(RT_ERR_INVALID, w + "clip.flags must be 0 (none is defined)");
+    if (k) k->clip_radius = c->radius, k->clip_gamma = c->gamma;
+    return RT_OK;
+}
+
 // Synchronous temporal accumulation of host planes: the current planes, the previous ones, the
 // outputs, then the two sphere tables of the stage with object motion (motion null: the static one).
+// with_clip: rt_temporal_clip (its motion is optional); the window reads planes staged anyway.
 int temporal_host(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
-                  const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, bool with_motion, rt_stats *stats)
+                  const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, bool with_motion, rt_stats *stats,
+                  const rt_temporal_clip_t *clip = nullptr, bool with_clip = false)
 {
-    const char *const who = with_motion ? "rt_temporal_motion" : "rt_temporal";
+    const char *const who = with_clip ? "rt_temporal_clip" : with_motion ? "rt_temporal_motion" : "rt_temporal";
     rt::KTemporal k{};
     if (int rc = check_temporal(params, camera, prev_camera, buffers, who, &k); rc != RT_OK) return rc;
     if (with_motion)
         if (int rc = check_temporal_motion(motion, buffers, false, who, &k); rc != RT_OK) return rc;
+    if (with_clip)
+        if (int rc = check_temporal_clip(clip, who, &k); rc != RT_OK) return rc;
     const size_t n = static_cast<size_t>(params->width) * params->height;
     const rt_temporal_buffers &b = *buffers;
     const uint32_t n_sph = with_motion ? motion->n_spheres : 0u;
@@ -483,6 +505,8 @@ struct rt_preview {
     bool up_written = false;       // a frame has written them
     uint32_t cur = 0;
     rt_camera prev_camera{};
+    // rt_preview_set_clip's record (clip.size is 0: the temporal stage runs without the clamp)
+    rt_temporal_clip_t clip{};
     // the scene's epochs at the session's last frame (rt_scene_motion)
     uint64_t geometry_epoch = 0, appearance_epoch = 0;
     rt_preview_planes_t last{};    // last.frames: frames since creation or the last reset
@@ -616,6 +640,8 @@ int preview_frame(rt_preview &pv, const rt_camera *camera, uint64_t seed, float 
                                           sm.prev_centres};
             if (int rc = check_temporal_motion(&tm, &tb, true, who, &k); rc != RT_OK) return rc;
         }
+        if (pv.clip.size)
+            if (int rc = check_temporal_clip(&pv.clip, who, &k); rc != RT_OK) return rc;
         RT_HIP(rt::launch_temporal(k, st));
         color = out_c, variance = out_v;
     }
@@ -791,6 +817,20 @@ int rt_preview_reset(rt_preview *pv)
     return RT_OK;
 }
 
+int rt_preview_set_clip(rt_preview *pv, const rt_temporal_clip_t *clip)
+{
+    if (!pv) return fail(RT_ERR_INVALID, "rt_preview_set_clip: null session");
+    if (pv->p.flags & RT_PREVIEW_NO_TEMPORAL)
+        return fail(RT_ERR_INVALID, "rt_preview_set_clip: the session has no temporal stage (RT_PREVIEW_NO_TEMPORAL is set)");
+    if (!clip) {
+        pv->clip = rt_temporal_clip_t{};
+        return RT_OK;
+    }
+    if (int rc = check_temporal_clip(clip, "rt_preview_set_clip", nullptr); rc != RT_OK) return rc;
+    pv->clip = *clip;
+    return RT_OK;
+}
+
 int rt_preview_planes(rt_preview *pv, rt_preview_planes_t *out)
 {
     if (!pv || !out) return fail(RT_ERR_INVALID, "rt_preview_planes: null argument");
@@ -876,6 +916,34 @@ int rt_temporal_motion(const rt_temporal_params *params, const rt_camera *camera
                        const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, rt_stats *stats)
 {
     return temporal_host(params, camera, prev_camera, buffers, motion, true, stats);
+}
+
+int rt_temporal_clip_default(rt_temporal_clip_t *out)
+{
+    if (!out) return fail(RT_ERR_INVALID, "rt_temporal_clip_default: null argument");
+    *out = rt_temporal_clip_t{static_cast<uint32_t>(sizeof(rt_temporal_clip_t)), kClipRadius, kClipGamma, 0u};
+    return RT_OK;
+}
+
+int rt_temporal_clip_device(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                            const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion,
+                            const rt_temporal_clip_t *clip, void *stream)
+{
+    const char *const who = "rt_temporal_clip_device";
+    rt::KTemporal k{};
+    if (int rc = check_temporal(params, camera, prev_camera, buffers, who, &k); rc != RT_OK) return rc;
+    if (motion)
+        if (int rc = check_temporal_motion(motion, buffers, true, who, &k); rc != RT_OK) return rc;
+    if (int rc = check_temporal_clip(clip, who, &k); rc != RT_OK) return rc;
+    RT_HIP(rt::launch_temporal(k, static_cast<hipStream_t>(stream)));
+    return RT_OK;
+}
+
+int rt_temporal_clip(const rt_temporal_params *params, const rt_camera *camera, const rt_camera *prev_camera,
+                     const rt_temporal_buffers *buffers, const rt_temporal_motion_t *motion, const rt_temporal_clip_t *clip,
+                     rt_stats *stats)
+{
+    return temporal_host(params, camera, prev_camera, buffers, motion, motion != nullptr, stats, clip, true);
 }
 
 int rt_upsample_params_default(uint32_t width, uint32_t height, uint32_t lo_width, uint32_t lo_height, rt_upsample_params *out)

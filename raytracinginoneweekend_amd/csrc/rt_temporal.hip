@@ -17,6 +17,17 @@
 // (31.5 against 23.4 us at 1280x720 with 486 spheres: every workgroup pays for the whole table, and 32
 // KiB of LDS cost occupancy; profiles/motion/lds_form.diff keeps it). MOTION = false is the static stage:
 // its machine code is what it was before the parameter existed.
+//
+// CLIP (rt_temporal_clip_device): the resampled history colour is clamped to the box
+// mean +- gamma standard deviations of the current frame's colours around the pixel. Unlike the history
+// taps, that window is a fixed rectangle of the current frame, so the workgroup stages its tile of
+// {beauty, sphere_id} plus a halo of `radius` texels in LDS (one float4 per texel, the id's bits in w:
+// a lane's tap reads the id and, if it is the pixel's, the colour of one 16-byte texel, and the lanes of a
+// wave read consecutive texels), and every lane takes its window from there. Lanes outside the image help
+// to stage and reach the barrier before they leave; halo texels outside the image are not read from memory
+// (zeros are staged) and a lane skips them by their coordinates. CLIP = false is the stage without the
+// clamp: its machine code is what it was before the parameter existed (no LDS, no barrier, the early
+// return first), and it does not name the tile.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -30,11 +41,87 @@ __device__ __forceinline__ float tp_dot(const float *a, float x, float y, float 
     return (a[0] * x + a[1] * y) + a[2] * z;
 }
 
-template <bool HISTORY, bool MOTION>
+// The clip kernel's workgroup: RT_CLIP_BW x (256 / RT_CLIP_BW) lanes. 64 x 4 as the plain kernel; -DRT_CLIP_BW=32
+// builds the 32 x 8 form, which reads a smaller halo (DESIGN.md §4.17 keeps both forms' figures).
+#ifndef RT_CLIP_BW
+#define RT_CLIP_BW 64
+#endif
+constexpr int kClipBW = RT_CLIP_BW, kClipBH = 256 / RT_CLIP_BW, kClipMaxRadius = 3;
+constexpr int kClipTexels = (kClipBW + 2 * kClipMaxRadius) * (kClipBH + 2 * kClipMaxRadius);
+static_assert(kClipBW * kClipBH == 256 && kClipBW % 32 == 0, "the clip kernel's workgroup is 256 lanes in whole half-waves");
+// the staged tile at the largest radius (70 x 10 texels at 64 x 4: 11200 bytes); only the CLIP kernels name it
+__shared__ float4 g_clip_tile[kClipTexels];
+
+// The workgroup's tile of {beauty, id} and its halo of R texels into LDS, row-major, (kClipBW + 2 R) texels a
+// row (a compile-time width: the texel's row and column cost no division). A texel outside the image is
+// not read: zeros are staged.
+template <int R>
+__device__ __forceinline__ void stage_tile(float4 *tile, const float *beauty, const uint32_t *id, int W, int H)
+{
+    constexpr int TW = kClipBW + 2 * R, texels = TW * (kClipBH + 2 * R);
+    const int x0 = (int)blockIdx.x * kClipBW - R, y0 = (int)blockIdx.y * kClipBH - R;
+    for (int t = (int)threadIdx.y * kClipBW + (int)threadIdx.x; t < texels; t += 256) {
+        const int ty = t / TW, gx = x0 + (t - ty * TW), gy = y0 + ty;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t g = (size_t)gy * W + gx;
+            v = make_float4(beauty[3u * g], beauty[3u * g + 1u], beauty[3u * g + 2u], __uint_as_float(id[g]));
+        }
+        tile[t] = v;
+    }
+}
+
+// Step 5b of the contract for the lane at (lx, ly) of the workgroup, pixel (x, y): the history colour
+// (c0, c1, c2) clamped to the box of the (2 R + 1)^2 window, read from the staged tile.
+template <int R>
+__device__ __forceinline__ void clip_history(const float4 *tile, int lx, int ly, int x, int y, int W, int H, float br,
+                                             float bg, float bb, uint32_t id, float gamma, float &c0, float &c1, float &c2)
+{
+    constexpr int TW = kClipBW + 2 * R;
+    float n = 0.f, a0 = 0.f, a1 = 0.f, a2 = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = -R; j <= R; ++j) {
+        const bool row = y + j >= 0 && y + j < H;
+#pragma unroll
+        for (int i = -R; i <= R; ++i) {
+            // (A form without these branches, a skipped tap adding +0.0f, lets the compiler issue the whole
+            // window's LDS loads together: 226 VGPRs, 2 waves per SIMD, twice the time. DESIGN.md §4.17.)
+            if (!row || x + i < 0 || x + i >= W) continue;  // skipped: nothing is added
+            const float4 t = tile[(ly + R + j) * TW + (lx + R + i)];
+            if (__float_as_uint(t.w) != id) continue;
+            n = n + 1.0f;
+            const float d0 = t.x - br, d1 = t.y - bg, d2 = t.z - bb;
+            a0 = a0 + d0, a1 = a1 + d1, a2 = a2 + d2;
+            s0 = s0 + d0 * d0, s1 = s1 + d1 * d1, s2 = s2 + d2 * d2;
+        }
+    }
+    auto clamp = [&](float c, float b, float m1, float m2) {
+        const float mean = m1 / n, ex2 = m2 / n;
+        const float var = fmaxf(0.0f, ex2 - mean * mean);
+        const float half = gamma * sqrtf(var);
+        const float mu = b + mean;
+        const float lo = mu - half, hi = mu + half;
+        return fminf(fmaxf(c, lo), hi);
+    };
+    c0 = clamp(c0, br, a0, s0), c1 = clamp(c1, bg, a1, s1), c2 = clamp(c2, bb, a2, s2);
+}
+
+template <bool HISTORY, bool MOTION, bool CLIP>
 __global__ __launch_bounds__(256) void temporal_accumulate(const KTemporal k)
 {
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    constexpr int BW = CLIP ? kClipBW : 64, BH = CLIP ? kClipBH : 4;
+    const int x = blockIdx.x * BW + threadIdx.x, y = blockIdx.y * BH + threadIdx.y;
     const int W = k.W, H = k.H;
+    if constexpr (CLIP) {  // (discarded, the tile's name with it, when CLIP is false)
+        // every lane, also one outside the image (the host checks radius <= 3: any other value stages
+        // and reads the radius-3 tile, so the tile's size holds whatever the record says)
+        switch (k.clip_radius) {  // uniform over the grid
+        case 1: stage_tile<1>(g_clip_tile, k.beauty, k.id, W, H); break;
+        case 2: stage_tile<2>(g_clip_tile, k.beauty, k.id, W, H); break;
+        default: stage_tile<3>(g_clip_tile, k.beauty, k.id, W, H); break;
+        }
+        __syncthreads();
+    }
     if (x >= W || y >= H) return;
     const size_t p = (size_t)y * W + x;
     const float br = k.beauty[3u * p], bg = k.beauty[3u * p + 1u], bb = k.beauty[3u * p + 2u];
@@ -115,9 +202,23 @@ __global__ __launch_bounds__(256) void temporal_accumulate(const KTemporal k)
                     if (sumw >= 0.01f) {
                         const float n = fminf(sumn / sumw + 1.0f, k.max_history);
                         const float kk = fmaxf(1.0f / n, k.alpha_min), rest = 1.0f - kk;
-                        o0 = kk * br + rest * (sr / sumw);
-                        o1 = kk * bg + rest * (sg / sumw);
-                        o2 = kk * bb + rest * (sb / sumw);
+                        if constexpr (CLIP) {
+                            float c0 = sr / sumw, c1 = sg / sumw, c2 = sb / sumw;
+                            const int lx = threadIdx.x, ly = threadIdx.y;
+                            const float4 *const tile = g_clip_tile;
+                            switch (k.clip_radius) {  // uniform over the grid
+                            case 1: clip_history<1>(tile, lx, ly, x, y, W, H, br, bg, bb, id, k.clip_gamma, c0, c1, c2); break;
+                            case 2: clip_history<2>(tile, lx, ly, x, y, W, H, br, bg, bb, id, k.clip_gamma, c0, c1, c2); break;
+                            default: clip_history<3>(tile, lx, ly, x, y, W, H, br, bg, bb, id, k.clip_gamma, c0, c1, c2); break;
+                            }
+                            o0 = kk * br + rest * c0;
+                            o1 = kk * bg + rest * c1;
+                            o2 = kk * bb + rest * c2;
+                        } else {  // (the statements as they were: the order of the divisions is part of the machine code)
+                            o0 = kk * br + rest * (sr / sumw);
+                            o1 = kk * bg + rest * (sg / sumw);
+                            o2 = kk * bb + rest * (sb / sumw);
+                        }
                         ov = (kk * kk) * var + (rest * rest) * (sumv / (sumw * sumw));
                         on = n;
                     }
@@ -135,11 +236,17 @@ __global__ __launch_bounds__(256) void temporal_accumulate(const KTemporal k)
 hipError_t launch_temporal(const KTemporal &k, hipStream_t stream)
 {
     void *args[] = {const_cast<KTemporal *>(&k)};
+    // the motion kernel from a table pointer, the clip kernel from a radius (without history: the copy)
+    if (k.p_color && k.clip_radius) {
+        const dim3 grid((k.W + kClipBW - 1) / kClipBW, (k.H + kClipBH - 1) / kClipBH);
+        const void *fn = k.centres ? reinterpret_cast<const void *>(&temporal_accumulate<true, true, true>)
+                                   : reinterpret_cast<const void *>(&temporal_accumulate<true, false, true>);
+        return hipLaunchKernel(fn, grid, dim3(kClipBW, kClipBH), args, 0, stream);
+    }
     const dim3 grid((k.W + 63) / 64, (k.H + 3) / 4);
-    // the motion kernel from a table pointer
-    const void *fn = !k.p_color ? reinterpret_cast<const void *>(&temporal_accumulate<false, false>)
-                     : k.centres ? reinterpret_cast<const void *>(&temporal_accumulate<true, true>)
-                                 : reinterpret_cast<const void *>(&temporal_accumulate<true, false>);
+    const void *fn = !k.p_color ? reinterpret_cast<const void *>(&temporal_accumulate<false, false, false>)
+                     : k.centres ? reinterpret_cast<const void *>(&temporal_accumulate<true, true, false>)
+                                 : reinterpret_cast<const void *>(&temporal_accumulate<true, false, false>);
     return hipLaunchKernel(fn, grid, dim3(64, 4), args, 0, stream);
 }
 

@@ -349,15 +349,36 @@ def temporal_motion_record(centres, prev_centres, n_spheres):
     return abi.RtTemporalMotion(C.sizeof(abi.RtTemporalMotion), n_spheres, centres or None, prev_centres or None)
 
 
-def temporal_device(pointers, params, camera, prev_camera, stream=None, motion=None):
+def temporal_clip(radius=None, gamma=None, **fields):
+    """An rt_temporal_clip_t record: the library defaults with radius, gamma and
+    `fields` (flags) set."""
+    c = abi.RtTemporalClip()
+    check(lib().rt_temporal_clip_default(C.byref(c)))
+    for k, v in dict(radius=radius, gamma=gamma).items():
+        if v is not None:
+            setattr(c, k, v)
+    for k, v in fields.items():
+        if k != "flags":
+            raise KeyError(f"rt_temporal_clip_t has no field {k!r} to set")
+        setattr(c, k, v)
+    return c
+
+
+def temporal_device(pointers, params, camera, prev_camera, stream=None, motion=None, clip=None):
     """Enqueue rt_temporal_device on `stream`: `pointers` is a dict plane name -> device address on
     the current device (temporal_buffers; the prev_ planes all absent: no history yet), `params` an
     rt_temporal_params record, `camera` and `prev_camera` the two frames' cameras (prev_camera may be
     None without history). One launch, no host synchronisation. motion: (centres address,
     prev_centres address, n_spheres) of two device tables: rt_temporal_motion_device, the stage with
-    object motion."""
+    object motion. clip: an rt_temporal_clip_t record (temporal_clip):
+    rt_temporal_clip_device, the stage with the history clamp, with or without motion."""
     rec = temporal_buffers(pointers)
     cams = (C.byref(_cam_record(camera)), C.byref(_cam_record(prev_camera)) if prev_camera is not None else None)
+    if clip is not None:
+        m = temporal_motion_record(*motion) if motion is not None else None
+        check(lib().rt_temporal_clip_device(C.byref(params), *cams, C.byref(rec), C.byref(m) if m is not None else None,
+                                            C.byref(clip), C.c_void_p(stream or 0)))
+        return
     if motion is not None:
         m = temporal_motion_record(*motion)
         check(lib().rt_temporal_motion_device(C.byref(params), *cams, C.byref(rec), C.byref(m), C.c_void_p(stream or 0)))
@@ -369,7 +390,7 @@ _TEMPORAL_CUR = ("beauty", "variance", "normal", "depth", "alpha", "sphere_id")
 _TEMPORAL_PREV = ("color", "variance", "history", "normal", "depth", "sphere_id")
 
 
-def temporal(cur, prev, camera, prev_camera, params=None, stats=None, motion=None, **fields):
+def temporal(cur, prev, camera, prev_camera, params=None, stats=None, motion=None, clip=None, **fields):
     """rt_temporal: the previous frame's history reprojected into the current
     frame and blended. cur: dict of the current frame's planes (beauty and variance as render_var
     returns them; normal, depth, alpha, sphere_id as render_aov does); prev: dict of the previous
@@ -378,7 +399,8 @@ def temporal(cur, prev, camera, prev_camera, params=None, stats=None, motion=Non
     3), variance float32 (h, w), history float32 (h, w)). params: an rt_temporal_params record
     (default: the library's for this size); `fields` as temporal_params takes them. motion:
     (centres, prev_centres), two float32 (n, 4) tables as sphere_table makes them: rt_temporal_motion,
-    the stage with object motion."""
+    the stage with object motion. clip: an rt_temporal_clip_t record (temporal_clip):
+    rt_temporal_clip, the stage with the history clamp, with or without motion."""
     if set(cur) != set(_TEMPORAL_CUR):
         raise KeyError(f"cur must hold exactly the planes {_TEMPORAL_CUR}, not {sorted(cur)}")
     if prev is not None and set(prev) != set(_TEMPORAL_PREV):
@@ -400,12 +422,17 @@ def temporal(cur, prev, camera, prev_camera, params=None, stats=None, motion=Non
     rec = temporal_buffers({n: a.ctypes.data for n, a in {**host, **out}.items()})
     cams = (C.byref(_cam_record(camera)), C.byref(_cam_record(prev_camera)) if prev_camera is not None else None)
     st = C.byref(stats) if stats is not None else None
+    m = None
     if motion is not None:
         tabs = [np.ascontiguousarray(t) for t in motion]
         if len(tabs) != 2 or any(t.dtype != np.float32 or t.ndim != 2 or t.shape != (len(tabs[0]), 4) for t in tabs):
             raise ValueError("motion must be two float32 (n, 4) tables of one length")
         m = temporal_motion_record(tabs[0].ctypes.data if len(tabs[0]) else None,
                                    tabs[1].ctypes.data if len(tabs[1]) else None, len(tabs[0]))
+    if clip is not None:
+        check(lib().rt_temporal_clip(C.byref(p), *cams, C.byref(rec), C.byref(m) if m is not None else None,
+                                     C.byref(clip), st))
+    elif m is not None:
         check(lib().rt_temporal_motion(C.byref(p), *cams, C.byref(rec), C.byref(m), st))
     else:
         check(lib().rt_temporal(C.byref(p), *cams, C.byref(rec), st))
@@ -561,6 +588,11 @@ class Preview:
     def reset(self):
         """The next frame has no history."""
         check(lib().rt_preview_reset(self.handle))
+
+    def set_clip(self, clip):
+        """rt_preview_set_clip: from the next frame on the temporal stage clamps the history with
+        `clip` (an rt_temporal_clip_t record, temporal_clip); None turns it off."""
+        check(lib().rt_preview_set_clip(self.handle, C.byref(clip) if clip is not None else None))
 
     def planes(self):
         """rt_preview_planes: what the last enqueued frame wrote, as a dict plane name
