@@ -1,7 +1,7 @@
 // rt_aov.hip — first-hit feature buffers (rt_render_aov_device): per pixel the
 // albedo, normal, depth and coverage of its samples' primary hits and the sphere of sample 0,
-// for a denoiser or compositor. A translation unit of its own, so that the render kernels'
-// machine code (rt_kernel.hip) does not depend on it; the device functions are rt_kernel.hip's.
+// for a denoiser or compositor. A translation unit of its own, as every kernel family is; the device
+// functions are rt_trace.h's.
 //
 // Sample s of a pixel is the beauty render's sample s (main.cxx:192-200): the same streams, the
 // same jitter and lens draws, camera::ray (camera.hxx:46-57) and hit_world (raytracer.hxx:94-118)
@@ -14,8 +14,7 @@
 // and a pixel's value of each is the samples' blocked sum of main.cxx:205 (libstdc++ reduce:
 // ((c0 + c1) + (c2 + c3)) per block of 4 added to the running sum, then the tail one by one)
 // divided by float(samples).
-#define RT_DEVICE_FUNCTIONS_ONLY 1
-#include "rt_kernel.hip"
+#include "rt_trace.h"
 
 namespace rt {
 

@@ -1,5 +1,5 @@
 // rt_device.h — parameters shared by the host launcher (rt_host.cpp) and the HIP kernels
-// (rt_kernel.hip). Plain POD records (HIP vector types only), included by both sides.
+// (the rt_*.hip units). Plain POD records (HIP vector types only), included by both sides.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -109,9 +109,9 @@ struct KParams {
     uint32_t n_geo, n_always, n_clusters, clus_offset;
     uint32_t n_supers, supers_offset;  // level 2: groups of kSuperClusters (8) consecutive clusters, 2 float4 each
     uint32_t use_root;       // level 3: one box over all clusters at supers_offset + 2 n_supers
-    uint32_t iso;            // isolated-sphere shortcut of the walk (rt_kernel.hip hint_candidate)
+    uint32_t iso;            // isolated-sphere shortcut of the walk (rt_trace.h hint_candidate)
     uint32_t transpose_max;  // clusters requested by at most this many lanes (<= 16) are tested transposed
-    uint32_t fast_roots;     // scene and camera within 2^19 of the origin: short exact root forms (rt_kernel.hip RayDiv)
+    uint32_t fast_roots;     // scene and camera within 2^19 of the origin: short exact root forms (rt_trace.h RayDiv)
     float clus_pad;          // max over clusters of 1e-3 * (|C|_1 + |e|_1) + 1e-6 (per-ray pad adds 1e-3 |o|_1)
     // shading records in the blob at shade_offset, indexed by original sphere index:
     // {cx, cy, cz, r}, {albedo rgb, param} x n_spheres, then n_spheres kind bytes (16-B padded)

@@ -465,7 +465,7 @@ void derive_scene(const rt_sphere *spheres, uint32_t n_spheres, const rt_materia
     for (uint32_t i = 0; i < n_spheres; ++i) {
         for (float v : {spheres[i].center[0], spheres[i].center[1], spheres[i].center[2], spheres[i].radius})
             if (!(std::fabs(v) <= 0x1p19f)) d.in_fast_range = false;
-        // the hit normal's short division by r (rt_kernel.hip div3_short) needs |r| >= 2^-40
+        // the hit normal's short division by r (rt_trace.h div3_short) needs |r| >= 2^-40
         if (!(std::fabs(spheres[i].radius) >= 0x1p-40f)) d.in_fast_range = false;
     }
     // the windows, then the empty set; a scene without spheres keeps one empty window

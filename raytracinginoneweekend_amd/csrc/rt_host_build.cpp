@@ -389,7 +389,7 @@ namespace rthost {
 
 // ---- scene blob: always-tested list + spatial clusters -------------------
 
-constexpr float kPadRel = 1e-3f;      // must match RT_PAD_REL in rt_kernel.hip
+constexpr float kPadRel = 1e-3f;      // must match RT_PAD_REL in rt_trace.h
 
 // recursive median splits into clusters of at most cluster_max spheres (rt_options.cluster_size,
 // 16 by default: two blocks of 8; 8 / 12 / 20 / 24 measured slower, profiles/r03/ab/knobs2_s3.txt)
@@ -591,7 +591,7 @@ blob_t build_blob(const rt_sphere *s, uint32_t n, bool clustered, uint32_t clust
     return b;
 }
 
-// The walk shortcut of dielectric spheres (rt_kernel.hip hint_candidate): a lane whose last hit
+// The walk shortcut of dielectric spheres (rt_trace.h hint_candidate): a lane whose last hit
 // was such a sphere S, whose next segment (0, 1.002 t] up to S's candidate t lies in the ball
 // B(C, R_k) (R_k^2 = fl(fl(r r) kIsoR2Grow), the kernel's check of both ends), tests S's
 // neighbours instead of walking the clusters. The neighbours N(S) are the clustered spheres

@@ -18,18 +18,23 @@
 #include "rt_tiles.h"
 
 namespace rt {
+// rt_kernel.hip
 hipError_t launch_render(int variant, int cull, const KParams &p, uint32_t grid, hipStream_t stream, int wpb = 4);
 hipError_t deep_occupancy(int variant, int wpb, size_t lds, int *blocks_per_cu, size_t *static_lds);
 hipError_t occupancy_render(int variant, int cull, int *blocks_per_cu, size_t lds, bool pairs = false);
 hipError_t static_lds_render(int variant, int cull, size_t *bytes, bool pairs = false);
+// rt_sky.hip
+hipError_t launch_sky(const KSky &k, hipStream_t stream);
+// rt_accum.hip
 hipError_t launch_accumulate(const KAccum &k, hipStream_t stream);
+hipError_t launch_epilogue(const float *in, uint8_t *out, uint64_t n, hipStream_t stream);
+// rt_compat.hip
 hipError_t launch_compat(const KCompat &k, uint32_t grid, hipStream_t stream);
+hipError_t occupancy_compat(int *blocks_per_cu);
+// rt_wavefront.hip
 hipError_t launch_wave_gen(const KWave &w, hipStream_t stream);
 hipError_t launch_wave_bounce(int cull, const KWave &w, uint32_t grid, hipStream_t stream);
 hipError_t occupancy_wave_bounce(int cull, int *blocks_per_cu, size_t lds);
-hipError_t occupancy_compat(int *blocks_per_cu);
-hipError_t launch_epilogue(const float *in, uint8_t *out, uint64_t n, hipStream_t stream);
-hipError_t launch_sky(const KSky &k, hipStream_t stream);
 // rt_aov.hip
 hipError_t launch_aov(int cull, const KAov &k, uint32_t grid, hipStream_t stream);
 hipError_t occupancy_aov(int cull, int *blocks_per_cu, size_t lds);

@@ -1,5 +1,5 @@
 // rt_texel.h — the gamma/u8 texel of a linear f32 value, shared by the kernels that store rgb8:
-// epilogue_rgb8_kernel (rt_kernel.hip, rt_epilogue_rgb8_device) and preview_merge (rt_preview.hip).
+// epilogue_rgb8_kernel (rt_accum.hip, rt_epilogue_rgb8_device) and preview_merge (rt_preview.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

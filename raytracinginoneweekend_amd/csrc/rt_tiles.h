@@ -86,7 +86,7 @@ RT_TILE_FN bool beam_misses(const iv o[3], const iv d[3], const double lo[3], co
 }
 
 // No ray of the beam gets a candidate from sphere S in the kernel's binary32 test
-// (raytracer.hxx:52-92 as rt_kernel.hip test_block8 evaluates it), proven in exact arithmetic
+// (raytracer.hxx:52-92 as rt_trace.h test_block8 evaluates it), proven in exact arithmetic
 // with margins of 1e-5 of the terms' magnitudes, where the binary32 evaluation errs by < 2^-21:
 // either the discriminant b^2 - a c is negative for every ray, or every ray starts outside S
 // (c > 0) moving away from it (b > 0) with b 2^-22 < kMIN a / 2, so that both roots are negative
@@ -149,7 +149,7 @@ RT_TILE_FN uint8_t classify_tile(const rt_camera &cam, const pass_view &p, const
         d[k] = grow(dk, 1e-5 * m + 1e-30);
     }
     const double o1 = mag(o[0]) + mag(o[1]) + mag(o[2]);
-    // twice the kernel's per-ray pad (rt_kernel.hip closest_hit: 1e-3 |o|_1 + clus_pad)
+    // twice the kernel's per-ray pad (rt_trace.h closest_hit: 1e-3 |o|_1 + clus_pad)
     const double pad = 2.0 * (1e-3 * o1 + g.clus_pad) + 1e-6;
     bool sky = !g.root || box_missed(o, d, pad, g.root);
     for (uint32_t i = 0; sky && i < g.n_always; ++i) sky = sphere_missed(o, d, g.always[i]);

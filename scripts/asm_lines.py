@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Static instruction counts of one render_kernel instantiation per source line (VALU / SALU /
-other), from a -gline-tables-only build of rt_kernel.hip: where the code of the hot loop sits.
+other), from a -gline-tables-only build of rt_kernel.hip: where the code of the hot loop sits,
+in rt_kernel.hip itself or in the headers it includes (rt_trace.h).
 U = VALU issue units by the gfx950 cost classes measured with scripts/ubench_int.hip (1: f32
 add/sub/mul/fma, add/sub/and/or/xor/not/lshr u32, moves of VGPRs and literals; 2: every other
 VALU op and any VALU op that reads an SGPR; 4: transcendental), G = VALU ops reading an SGPR.
-    python scripts/asm_lines.py [--kernel _ZN2rt13render_kernelILi0ELi7ELb0EEEvNS_7KParamsE] [--min 6]
+    python scripts/asm_lines.py [--kernel _ZN2rt13render_kernelILi0ELi7ELb0ELb0ELb0EEEvNS_7KParamsE] [--min 6]
 """
 import argparse
 import collections
@@ -15,7 +16,7 @@ import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
-ap.add_argument("--kernel", default="_ZN2rt13render_kernelILi0ELi7ELb0EEEvNS_7KParamsE")
+ap.add_argument("--kernel", default="_ZN2rt13render_kernelILi0ELi7ELb0ELb0ELb0EEEvNS_7KParamsE")
 ap.add_argument("--min", type=int, default=6)
 ap.add_argument("--flags", default="")
 a = ap.parse_args()
@@ -62,7 +63,7 @@ for line in s[i:j].split("\n"):
         u, sg = valu_cost(line)
         cnt[cur]["U"] += u
         cnt[cur]["G"] += sg
-text = open(os.path.join(src_dir, "rt_kernel.hip")).read().split("\n")
+text = {f: open(os.path.join(src_dir, f)).read().split("\n") for f in os.listdir(src_dir) if f.endswith((".hip", ".h"))}
 tot = collections.Counter()
 for k in sorted(cnt, key=lambda k: (k or ("", 0))):
     c = cnt[k]
@@ -70,6 +71,6 @@ for k in sorted(cnt, key=lambda k: (k or ("", 0))):
     if sum(c.values()) < a.min:
         continue
     f, ln = k if k else ("?", 0)
-    t = text[ln - 1].strip()[:72] if f == "rt_kernel.hip" and ln > 0 else ""
+    t = text[f][ln - 1].strip()[:72] if f in text and 0 < ln <= len(text[f]) else ""
     print(f"{f}:{ln:<5d} V{c['V']:5d} U{c['U']:5d} G{c['G']:4d} S{c['S']:5d} M{c['M']:4d}  {t}")
 print("total", dict(tot))

@@ -8,7 +8,8 @@ import subprocess
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "raytracinginoneweekend_amd", "csrc")
-K = "rt_kernel.hip"
+K = "rt_kernel.hip"   # the unit that is rebuilt; a patch goes to whichever of its files holds the anchor
+FILES = (K, "rt_trace.h")
 PATCHES = {
     "reject": ("            const f3 r = random_in_unit_sphere_capped<STATS>(st, inc, got, dbg);\n",
                "            {\n"
@@ -111,14 +112,14 @@ for name, (anchor, extra) in PATCHES.items():
     src = os.path.join(out, "src")
     shutil.rmtree(out, ignore_errors=True)
     os.makedirs(src)
-    for f in ("rt_kernel.hip", "rt_device.h", "rt_consts.h"):
+    for f in (K, "rt_trace.h", "rt_device.h", "rt_consts.h"):
         shutil.copy(os.path.join(SRC, f), src)
     os.makedirs(os.path.join(out, "include"), exist_ok=True)
-    text = open(os.path.join(src, K)).read()
-    assert text.count(anchor) >= 1, name
-    # the render loop's copy (the first occurrence; the wavefront kernel has its own)
+    holder, = [f for f in FILES if anchor in open(os.path.join(src, f)).read()]
+    text = open(os.path.join(src, holder)).read()
+    # the first occurrence; only rt_kernel.hip is rebuilt, so the other units' kernels keep their code
     text = text.replace(anchor, anchor + extra if name != "ground" else extra + anchor, 1)
-    open(os.path.join(src, K), "w").write(text)
+    open(os.path.join(src, holder), "w").write(text)
     inc = ["-I", os.path.join(REPO, "include")]
     r = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *inc, "-Rpass-analysis=kernel-resource-usage", "-c",
                         os.path.join(src, K), "-o", os.path.join(out, "k.o")], check=True, capture_output=True, text=True)
@@ -126,9 +127,10 @@ for name, (anchor, extra) in PATCHES.items():
     i = next(j for j, line in enumerate(lines) if "render_kernelILi0ELi7ELb0ELb0E" in line)
     print(name, " ".join(x.split(":")[-1].strip().split(" [")[0] for x in lines[i + 1:i + 9]
                          if "GPRs" in x or "Occupancy" in x))
-    # the host side is unchanged: the product build's object (make -C raytracinginoneweekend_amd/csrc)
+    # every other unit is unchanged: the product build's objects (make -C raytracinginoneweekend_amd/csrc)
+    others = sorted(os.path.join(SRC, "_obj", f) for f in os.listdir(os.path.join(SRC, "_obj"))
+                    if f.endswith(".o") and f != "rt_kernel.o")
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o",
-                    os.path.join(out, "librt_mi355x.so"), os.path.join(out, "k.o"), os.path.join(SRC, "_obj", "rt_host.o"),
-                    os.path.join(SRC, "_obj", "rt_host_build.o"), "-Wl,--no-undefined"], check=True)
+                    os.path.join(out, "librt_mi355x.so"), os.path.join(out, "k.o"), *others, "-Wl,--no-undefined"], check=True)
     shutil.rmtree(src)
     print("built", out)

@@ -1,4 +1,4 @@
-// Exhaustive check of sqrt_scaled (rt_kernel.hip: the compiler's IEEE sqrt expansion — hardware
+// Exhaustive check of sqrt_scaled (rt_trace.h: the compiler's IEEE sqrt expansion — hardware
 // v_sqrt_f32, then the one-ulp neighbours tested by FMA residuals — on x * 2^32, scaled back) for
 // every binary32 x in (0, 2^96): that it is the correctly rounded root, and how often gfx950's
 // hardware result already is that root, one ulp below, or one ulp above it (a neighbour that
@@ -8,7 +8,7 @@
 #include <cstdio>
 #include <cstdint>
 
-// sqrt_scaled of rt_kernel.hip: the expansion run on x * 2^32 and scaled back by 2^-16
+// sqrt_scaled of rt_trace.h: the expansion run on x * 2^32 and scaled back by 2^-16
 __device__ float sqrt_scaled(float x, int &d)
 {
     const float xs = x * 0x1p32f;

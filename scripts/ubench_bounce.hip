@@ -6,7 +6,7 @@
 // and reports shader cycles per iteration for the full bounce and for its parts.
 //   hipcc -std=c++17 -O3 -fno-slp-vectorize --offload-arch=gfx950 -ffp-contract=off -fno-fast-math
 //         -I raytracinginoneweekend_amd/csrc scripts/ubench_bounce.hip -o /tmp/ubench_bounce
-#include "../raytracinginoneweekend_amd/csrc/rt_kernel.hip"
+#include "../raytracinginoneweekend_amd/csrc/rt_trace.h"
 
 #include <cstdio>
 #include <vector>
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(64) void bounce(const UParams P)
         float t = 0.5f;
         if (MODE & 1) {
             bool inside;
-            Hit h{hint_candidate<false>(true, S, 1u | kShortcut, 0u, geo, sidx, o, d, rd, 1u, inside)};
+            Hit h{hint_candidate<false, false>(true, S, 1u | kShortcut, 0u, geo, sidx, o, d, rd, 1u, inside, 2u, 0u, nullptr)};
             if (nalw == 1u) test_block8<false, false, 1>(geo, sidx, 0, o, d, rd, h, dbg);
             t = h.t();
             if (!(t < 1e30f)) t = 0.5f;  // keep the loop going for lanes that left the ball

@@ -189,6 +189,60 @@ def test_timed_kernel_code_hash():
     assert bench.kernel_sha256("no_such_kernel") is None
 
 
+def _gfx950_kernels():
+    """The kernel symbols (function symbols with a .kd twin) of each gfx950 code object of the
+    built library, found the way bench.kernel_sha256 finds them."""
+    import struct
+    import bench
+    from raytracinginoneweekend_amd import _lib
+    so = open(_lib.LIB_PATH, "rb").read()
+    h = bench._elf_sections(so)[0][".hip_fatbin"]
+    fat = so[h[4]:h[4] + h[5]]
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    objects, pos = [], fat.find(magic)
+    while pos >= 0:
+        n, = struct.unpack_from("<Q", fat, pos + 24)
+        q = pos + 32
+        for _ in range(n):
+            off, size, tlen = struct.unpack_from("<QQQ", fat, q)
+            triple = fat[q + 24:q + 24 + tlen].decode()
+            q += 24 + tlen
+            if "gfx950" not in triple:
+                continue
+            co = fat[pos + off:pos + off + size]
+            cs, _ = bench._elf_sections(co)
+            sym, stra = cs[".symtab"], cs[".strtab"][4]
+            funcs, names = set(), set()
+            for i in range(sym[5] // 24):
+                name_off, info, _, shndx, _, _ = struct.unpack_from("<IBBHQQ", co, sym[4] + 24 * i)
+                name = co[stra + name_off:co.index(b"\0", stra + name_off)].decode()
+                if shndx:  # defined here
+                    names.add(name)
+                    if info & 0xf == 2:  # STT_FUNC
+                        funcs.add(name)
+            objects.append({f for f in funcs if f + ".kd" in names})
+        pos = fat.find(magic, pos + 1)
+    return objects
+
+
+def test_every_kernel_in_one_code_object():
+    """One translation unit per kernel family: a kernel (a template instantiated by accident in a
+    second unit links without complaint, and bench.kernel_sha256 would hash both copies) is defined
+    in exactly one code object, the timed kernels are among them, and the code object of the main
+    render kernel holds render kernels alone."""
+    import bench
+    objects = _gfx950_kernels()
+    every = [k for o in objects for k in o]
+    assert len(every) >= 36
+    twice = sorted({k for k in every if every.count(k) > 1})
+    assert not twice, twice
+    assert set(bench.TIMED_KERNEL) <= set(every)
+    home, = [o for o in objects if bench.TIMED_KERNEL[0] in o]
+    others = ("compat_kernel", "wave_", "sky_kernel", "accumulate_kernel", "epilogue_rgb8_kernel")
+    strangers = sorted(k for k in home if any(x in k for x in others))
+    assert not strangers, strangers
+
+
 # ---- rt_options: the library's only tuning surface besides GPU_MAX_HW_QUEUES and RT_OPTIONS ----
 def test_options_defaults_and_parse():
     o = rt.options()

@@ -4,7 +4,7 @@
 * every case's frame is finite and not flat;
 * the range census: which cases send part of their primaries outside a = |d|^2 in [2^-40, 2^40]
   while the host's camera_in_fast_range holds, so that the kernels' per-wave fallback from the
-  short root forms (rt_kernel.hip ray_div) runs with KParams::fast_roots on;
+  short root forms (rt_trace.h ray_div) runs with KParams::fast_roots on;
 * the material census: every extreme parameter of the `materials` case is hit by primaries;
 * the sky proof of rt_tile_order under these cameras, and that enough cases reach the sky kernel.
 

@@ -3,7 +3,7 @@ against the CPU restatement, bit for bit.
 
 The kernels' shortcuts hold under conditions on the camera or the materials that the other GPU
 suites never flip: the short root and division forms need every active lane's a = |d|^2 in
-[2^-40, 2^40] (rt_kernel.hip ray_div: the per-wave fallback with KParams::fast_roots on runs only
+[2^-40, 2^40] (rt_trace.h ray_div: the per-wave fallback with KParams::fast_roots on runs only
 where part of a wave is outside, the tiny_* and wide_* cases; in the subnormal_* cases a itself
 is below 2^-126 for half the primaries, where the short forms do give other bits), the sky kernel
 and the sky blocks of aov_kernel rely on rt_tile_order's proof, the always-tested-sphere gate is a function of a, and

@@ -20,7 +20,7 @@ RENDERS = sorted(n for n, m in G.manifest()["renders"].items() if m["rng"] == "p
 # clustered0: the same two-level walk with every cluster's members tested per lane (never
 # transposed, rt_options.transpose_max = 0)
 # ieee_roots: the IEEE sqrt/division sequences for the roots instead of their short exact forms
-# (RT_DIAG_IEEE_ROOTS; rt_kernel.hip RayDiv)
+# (RT_DIAG_IEEE_ROOTS; rt_trace.h RayDiv)
 VARIANTS = {"clustered": {}, "clustered0": {"_opts": {"transpose_max": 0}}, "brute": {"brute_force": True},
             "scalar": {"scalar_scene": True}, "ieee_roots": {"_opts": {"ieee_roots": True}}}
 

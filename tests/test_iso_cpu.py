@@ -1,4 +1,4 @@
-"""The walk shortcut of dielectric spheres (rt_kernel.hip hint_candidate, rt_host.cpp
+"""The walk shortcut of dielectric spheres (rt_trace.h hint_candidate, rt_host.cpp
 shortcut_words), checked as a geometric claim on the CPU with the reference's own binary32
 arithmetic.
 

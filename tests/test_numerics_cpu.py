@@ -1,4 +1,4 @@
-"""Exhaustive checks of the exact rewrites the kernel relies on (rt_kernel.hip):
+"""Exhaustive checks of the exact rewrites the kernels rely on (rt_trace.h):
 with a correctly rounded sqrt (IEEE on x86 and the hipcc sequence on gfx950),
   sqrtf(n) > 1   <=>  n > 0x1.000002p+0f   (random_in_unit_sphere, raytracer.hxx:41)
   sqrtf(n) > 0   <=>  n > 0                (length(refracted) > 0, raytracer.hxx:180)
