@@ -254,6 +254,20 @@ int rt_tile_order(const rt_sphere *spheres, uint32_t n_spheres, const rt_materia
                   uint32_t n_materials, const rt_camera *camera, const rt_params *params,
                   uint32_t *perm, uint32_t cap, uint32_t *n_blocks, uint32_t *n_lead, uint32_t *n_sky);
 
+/* The ground blocks of that pass: the positions [n_lead, n_lead + n_ground) of
+ * rt_tile_order's perm, tiles whose every primary ray is proven to miss every cluster's padded
+ * box, which a render under the default options gives to the ground kernel in every pass that is
+ * split (every pass issued beside other renders, and a pass issued alone of at
+ * least rt_options.deep_min_items samples; an unsplit pass keeps them in its main launch, so a
+ * small lone frame renders none through the kernel whatever this returns). 0 when the scene
+ * (no box over the clusters, or an always-tested list that is not 1 to 8 lambert spheres) or the
+ * pass (max_depth < 2, brute force / scalar / wavefront / compat flags, no sky tile, or the
+ * default options' natural_order, no_sky, no_root_box, pairs) keeps them in the main launch.
+ * Host-only.                                                                                  */
+int rt_tile_ground(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
+                   uint32_t n_materials, const rt_camera *camera, const rt_params *params,
+                   uint32_t *n_ground);
+
 /* The trap windows of a scene's spheres: out[2 i], out[2 i + 1] = sphere i's
  * {cos_lo, cos_hi}. A path that reflects totally inside sphere i with its cosine in the window
  * is proven to stay in that ball until max_depth (<= 64) and is ended there with colour 0; {1, 0}
@@ -394,6 +408,10 @@ int rt_tile_order_device(rt_scene *scene, const rt_camera *camera, const rt_para
  * multiple of 8) counts as a host order under either setting.                                   */
 int rt_scene_order_counts(rt_scene *scene, uint64_t *host_orders, uint64_t *device_orders,
                           uint64_t *hits);
+/* The ground kernel's share of the scene's last frame that used it: the samples
+ * of its ground tiles, and how many of them the kernel punted to the redo launch. Both 0 before
+ * any such frame. Waits for the device. Each pointer may be NULL.                               */
+int rt_scene_ground_counts(rt_scene *scene, uint64_t *ground_samples, uint64_t *redone_samples);
 /* ---- the render with the variance of each pixel's mean luminance ----
  * d_rgb receives the bits rt_render_device writes for the same arguments; d_var receives one float
  * per pixel, laid out as the one-channel feature planes below (row * width + x; packed rows or

@@ -10,7 +10,7 @@ from .render import (DeviceScene, MultiContext, default_options, default_options
                      epilogue_rgb8_device, make_params, options, parse_options, render_aov, render_cuda_impl, render_f32,
                      release_cached, render_multi_f32, render_multi_rgb8, render_rgb8, save_ppm,
                      reproject_basis, set_default_options, temporal, temporal_buffers, temporal_clip, temporal_device,
-                     temporal_params, tile_order, trap_windows, Preview, preview_merge_device,
+                     temporal_params, tile_ground, tile_order, trap_windows, Preview, preview_merge_device,
                      preview_params, preview_split_device, preview_upscale, upsample, upsample_buffers,
                      upsample_device, upsample_params, sphere_table)
 from .scene import (Dielectric, Lambert, Metal, RaytracerData, Sphere, cuda_scene_arrays, huge_scene,  # noqa: F401

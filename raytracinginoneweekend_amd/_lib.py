@@ -45,6 +45,8 @@ def _declare(L):
         "rt_tile_order": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, P(abi.RtCamera),
                                     P(abi.RtParams), P(C.c_uint32), C.c_uint32, P(C.c_uint32), P(C.c_uint32),
                                     P(C.c_uint32)]),
+        "rt_tile_ground": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, P(abi.RtCamera),
+                                     P(abi.RtParams), P(C.c_uint32)]),
         "rt_trap_windows": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, P(C.c_float)]),
         "rt_render_f32": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32,
                                     P(abi.RtCamera), P(abi.RtParams), P(C.c_float), P(abi.RtStats)]),
@@ -147,6 +149,7 @@ def _declare(L):
         "rt_tile_order_device": (C.c_int, [C.c_void_p, P(abi.RtCamera), P(abi.RtParams), C.c_void_p, C.c_uint32,
                                            P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), C.c_void_p]),
         "rt_scene_order_counts": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)]),
+        "rt_scene_ground_counts": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]),
         "rt_multi_create_ex": (C.c_int, [P(abi.RtSphere), C.c_uint32, P(abi.RtMaterial), C.c_uint32, P(C.c_int),
                                          C.c_int, P(abi.RtOptions), P(C.c_void_p)]),
     }

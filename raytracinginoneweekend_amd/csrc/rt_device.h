@@ -144,7 +144,9 @@ struct KParams {
     // the sky tiles. Group g's grp_items[g] items (sample-major over its positions, item J =
     // sample J / ng, position grp_pix[g] + J % ng) are dealt from 8 queues, queue q owning the q-th
     // eighth of its grp_blocks[g] blocks of 64; every wave deals group g from every queue before it
-    // takes group g + 1. One group (natural order): item J = slot J.
+    // takes group g + 1. One group (natural order): item J = slot J. With a ground kernel (DESIGN.md
+    // §4.7a) the ground range [grp_pix[1], grp_pix[2]) is a group without items between the lead
+    // tiles and the untiled blocks (n_groups 3), or the lead group stands alone (n_groups 1).
     const uint32_t *block_perm;
     uint32_t n_groups;          // 1: natural order, 3: tile classes
     uint32_t grp_pix[4];
@@ -160,7 +162,7 @@ struct KParams {
 constexpr uint32_t kDbgError = 15;
 enum BoundsCode : uint32_t {
     BC_NONE = 0, BC_HINT_NB = 1, BC_SHADE = 2, BC_SLOT = 3, BC_DEEP_APPEND = 4, BC_DEEP_ITEM = 5,
-    BC_DEEP_HINT = 6, BC_MEMBERS = 7, BC_DEEP_PX = 8
+    BC_DEEP_HINT = 6, BC_MEMBERS = 7, BC_DEEP_PX = 8, BC_REDO_APPEND = 9, BC_REDO_ITEM = 10
 };
 
 struct KAccum {
@@ -228,6 +230,49 @@ struct KSky {
     uint32_t pos0, n_pix;          // the sky positions [pos0, pos0 + n_pix) of the enumeration
     float *sums;
     unsigned long long *segments;  // optional: adds n_pix * spp segments (no sphere test)
+};
+
+// The redo list of a pass: the item words (= slot indices) of the samples
+// ground_kernel punted, count words in the workspace's queue-counter block (zeroed with it):
+// ctr[kRedoCount] = items appended, ctr[kRedoDeal] = the redo launch's dealing counter (chunks of 64).
+// stat (optional): the redo launch adds the pass's count to it (rt_scene_ground_counts).
+struct RedoList {
+    uint32_t *items;
+    uint32_t *ctr;
+    uint32_t cap;
+    uint32_t *stat;
+};
+constexpr uint32_t kRedoCount = 8;       // word of queue 0's line
+constexpr uint32_t kRedoDeal = 64 + 8;   // word of queue 1's line (kQueueStride + 8)
+
+// The redo launch's record (render_list_kernel): the pass's KParams first, at the offsets the
+// render loop reads them, then the list.
+struct KList {
+    KParams p;
+    RedoList redo;
+};
+
+// The ground kernel: the pass's samples of the pixels of the ground tiles (tiled
+// blocks whose beam misses every cluster box: the primary's closest hit is the always-tested list
+// alone), one thread per pixel. A sample that ends as sky, or as ground -> lambert scatter -> sky
+// with the second ray failing the root gate, gets its colour in its slot [sample][position]; any
+// other is appended to the redo list and rendered by the general kernel.
+struct KGround {
+    FrameConsts fc;                // the pass (fc.sample_begin: its first sample)
+    const uint32_t *block_perm;
+    uint32_t pos0, n_pix;          // the ground positions [pos0, pos0 + n_pix) of the enumeration
+    uint32_t n_samp;               // samples of the pass
+    uint32_t spt, n_wg;            // a thread takes spt consecutive samples of its pixel; workgroup b renders
+                                   // pixels 64 (b % n_wg) .., samples spt (b / n_wg) ..
+    float *slots;                  // the pass's slots, [sample][position][3]
+    uint32_t n_slots;
+    // scene (KParams): the always-tested list, the root box and the shading records, from global memory
+    const float4 *blob;
+    uint32_t n_geo, n_always, n_supers, supers_offset, shade_offset, n_spheres, fast_roots;
+    float clus_pad;
+    RedoList redo;
+    unsigned long long *segments;  // optional [3]: the non-punted samples' segments, sphere tests, box tests
+    unsigned long long *dbg;       // the instrumented build: kDbgError
 };
 
 // The first-hit feature buffers (aov_kernel, rt_aov.hip): one wave per 64-pixel

@@ -151,6 +151,20 @@ struct rt_scene {
     // the last render's cut (rt_scene_usage_get)
     uint32_t used_streams = 0, used_ws = 0, used_pass = 0, used_deep = 0, used_pairs = 0, used_split = 0;
     uint32_t used_lead = 0, used_sky = 0;  // the last pass's tile classes
+    // The ground kernel. ground_ok: the culled scene has a root box and 1 to 8
+    // always-tested spheres, all lambert. Per workspace the pass's redo list (4 B per ground
+    // sample; beside the planner's cut, like the orders' buffers). redo_stat: the samples redone per
+    // call, by the call's ring slot; ground_samples / ground_ring: the last frame's ground samples
+    // and its slot (rt_scene_ground_counts). ev_gpre / ev_ground: before and after the ground
+    // kernel of a pass issued alone, which runs on another stream.
+    bool ground_ok = false;
+    uint32_t *redo[kMaxWs] = {};
+    size_t redo_bytes[kMaxWs] = {};
+    uint32_t *redo_stat = nullptr;
+    uint64_t ground_samples = 0;
+    uint32_t ground_ring = 0;
+    uint64_t ground_call = 0;  // sc->calls of the frame ground_samples and ground_ring belong to
+    hipEvent_t ev_gpre = nullptr, ev_ground = nullptr;
     // the culled scene's geometry for the tile classes of a pass, and the
     // dealing orders computed from it, per camera and rows (a pure function of those and the
     // scene, kept for the kOrders most recently used), each with its block permutation on the device
@@ -404,6 +418,7 @@ struct SceneDerived {
     std::vector<float> trap;     // the windows, then the empty set
     scene_geom geom;             // the tile classes' geometry, and as classify_tiles_kernel reads it
     bool has_geom = false;
+    bool ground_ok = false;      // a root box and 1 to 8 always-tested spheres, all lambert
     std::vector<float> geom_words;
     bool in_fast_range = true;
     std::vector<float> table;    // [n][4] {cx, cy, cz, r}
@@ -461,6 +476,7 @@ void derive_scene(const rt_sphere *spheres, uint32_t n_spheres, const rt_materia
     }
     d.geom = scene_geometry(spheres, d.blobs[1]);
     d.has_geom = d.blobs[1].n_clusters != 0u;
+    d.ground_ok = d.has_geom && ground_scene_ok(spheres, materials, d.blobs[1], d.geom);
     d.in_fast_range = true;
     for (uint32_t i = 0; i < n_spheres; ++i) {
         for (float v : {spheres[i].center[0], spheres[i].center[1], spheres[i].center[2], spheres[i].radius})
@@ -543,6 +559,7 @@ int install_scene(rt_scene *sc, SceneDerived &d, bool first)
     sc->geom_root = d.geom.has_root;
     sc->geom_pad = d.geom.clus_pad;
     sc->has_geom = d.has_geom;
+    sc->ground_ok = d.ground_ok;
     sc->geom = d.has_geom ? std::move(d.geom) : scene_geom{};
     sc->in_fast_range = d.in_fast_range;
     sc->cur_table.swap(d.table);
@@ -584,6 +601,11 @@ int rt_scene_destroy(rt_scene *sc)
     }
     if (sc->ev_tail) (void)hipEventDestroy(sc->ev_tail);
     if (sc->ev_sky) (void)hipEventDestroy(sc->ev_sky);
+    if (sc->ev_gpre) (void)hipEventDestroy(sc->ev_gpre);
+    if (sc->ev_ground) (void)hipEventDestroy(sc->ev_ground);
+    for (uint32_t *p : sc->redo)
+        if (p) (void)hipFree(p);
+    if (sc->redo_stat) (void)hipFree(sc->redo_stat);
     for (void *p : {(void *)sc->blob[0], (void *)sc->blob[1], (void *)sc->dbg, (void *)sc->acc, (void *)sc->mom, (void *)sc->queue_ctr, sc->wq, (void *)sc->trap,
                     (void *)sc->centres[0], (void *)sc->centres[1]})
         if (p) (void)hipFree(p);
@@ -902,6 +924,9 @@ int free_workspaces(rt_scene *sc)
         RT_HIP(drop(sp, sc->slots_bytes[w]));
         sc->slots[w] = nullptr;
         RT_HIP(drop(sc->deep[w], sc->deep_bytes[w]));
+        void *rp = sc->redo[w];
+        RT_HIP(drop(rp, sc->redo_bytes[w]));
+        sc->redo[w] = nullptr;
         sc->deep_clean[w] = 0;
         sc->deep_meet_at[w] = 0;
     }
@@ -1253,6 +1278,11 @@ struct Frame {
     const rt_scene::Order *ord;  // the frame's dealing order, if any
     bool sky_kernel;             // the proven-sky tiles are rendered by sky_kernel at the last pass
     uint32_t sky_pos0;           // the first pixel position of those tiles (n_pixels: none)
+    // the ground tiles (the tiled blocks of the order's middle class, which come
+    // before its untiled blocks) are rendered by ground_kernel pass by pass, the samples it punts
+    // by the redo launch; positions [ground_pos0, ground_pos1)
+    bool ground;
+    uint32_t ground_pos0, ground_pos1;
     uint32_t ring;               // the call's slot in the timing events' ring
     // more than one render stream: passes rotate over sc->xs and the ring's workspaces
     bool pipe() const { return pl.streams > 1; }
@@ -1269,6 +1299,8 @@ struct Pass {
     uint32_t grid;    // workgroups of the main launch
     bool two_part;    // the accumulation in two parts, the first beside the deep launch
     bool sky_aside;   // the sky kernel on another stream (then the accumulation waits for ev_sky)
+    bool ground;      // its ground tiles go to ground_kernel (single samples, dealt by tile classes)
+    bool ground_aside;  // ... on another stream (then the redo launch waits for ev_ground)
     uint32_t stats_waves;  // the instrumented build: waves of the launch the counters cover
 };
 
@@ -1312,6 +1344,15 @@ int begin_pass(const Frame &f, Pass &p, rt::KParams &k)
     return RT_OK;
 }
 
+// Whether a pass is split (bind_deep_queue): a pass of fewer than rt_options.deep_min_items samples
+// issued alone is not, nor a lone pass dealt by tile classes under the lone_unsplit diagnostic.
+bool pass_is_split(const Frame &f, const Pass &p, uint64_t n_samples)
+{
+    const rt_options &O = f.sc->opt;
+    return f.pl.in.may_split && (n_samples >= O.deep_min_items || p.in_flight) &&
+           (p.in_flight || !p.ordered || !(O.diag & RT_DIAG_LONE_UNSPLIT));
+}
+
 // The pass's items, its main launch's grid and its dealing groups: lead tiles
 // first, then the others (then the proven sky tiles, unless the sky kernel renders them) in
 // single-sample passes of the culled LDS kernels, else the natural order.
@@ -1327,7 +1368,13 @@ void deal_groups(const Frame &f, Pass &p, rt::KParams &k)
     // kernel, the positions before the sky tiles'
     const uint64_t n_samples = n_pixels * (s1 - s0);
     const uint64_t rows = f.pl.slot_rows(s0, s1, p.pass_pairs);
-    k.n_items = static_cast<uint32_t>((p.ordered && f.sky_kernel ? f.sky_pos0 : n_pixels) * rows);
+    // The ground kernel for split passes only: the few punted samples that meet a glass ball are
+    // chains of up to max_depth segments, which a split pass hands to its deep launch; in an
+    // unsplit one they would run in the redo launch, a serial tail behind the main launch (config
+    // 3's 8-way share alone: 0.90-0.91 ms against 0.65-0.68)
+    p.ground = f.ground && p.ordered && pass_is_split(f, p, n_pixels * (s1 - s0));
+    const uint64_t ground_px = p.ground ? f.ground_pos1 - f.ground_pos0 : 0u;
+    k.n_items = static_cast<uint32_t>(((p.ordered && f.sky_kernel ? f.sky_pos0 : n_pixels) - ground_px) * rows);
     k.n_slots = static_cast<uint32_t>(n_pixels * rows);
     int wg_cu = grid_wg_per_cu(p.pass_pairs ? f.c.occ_pr : f.c.occ, p.in_flight, f.pl.streams, n_samples);
     // A lone pass whose sky kernel runs beside it: the main launch's workgroups fill every
@@ -1336,8 +1383,9 @@ void deal_groups(const Frame &f, Pass &p, rt::KParams &k)
     // sky's share of the pixels (config 3, 73% sky: 2 of 7 workgroups per CU; lone frame
     // 2.466-2.474 ms vs 2.528-2.547 with none, 2.474-2.495 with 1; period unchanged;
     // profiles/r06/ab/sky_room.txt). RT_LONE_SKY_ROOM >= 0 (A/B build switch) fixes it.
+    // (with a ground kernel, which then runs beside it too: the share of both)
     if (!p.in_flight && f.sky_kernel && p.ordered && s1 == f.P.spp && f.pipe() && !(sc->opt.diag & RT_DIAG_SKY_SERIAL)) {
-        const double sky_frac = 1.0 - static_cast<double>(f.sky_pos0) / static_cast<double>(n_pixels);
+        const double sky_frac = 1.0 - static_cast<double>(f.sky_pos0 - ground_px) / static_cast<double>(n_pixels);
         const int room = RT_LONE_SKY_ROOM >= 0 ? RT_LONE_SKY_ROOM : static_cast<int>(wg_cu * sky_frac * 0.4 + 0.5);
         wg_cu = std::max(1, wg_cu - room);
     }
@@ -1367,6 +1415,20 @@ void deal_groups(const Frame &f, Pass &p, rt::KParams &k)
             k.grp_blocks[g] = static_cast<uint32_t>(nbl[g] * S);  // nbl[g] blocks per sample
             k.div_grp[g] = make_udiv(static_cast<uint32_t>(std::max<uint64_t>(64u * nbl[g], 1u)));
         }
+        if (p.ground) {
+            // lead, (ground: no item), the untiled blocks; without untiled blocks the lead group alone
+            const uint64_t n_ground = ground_px / 64u, n_rest = nbl[1] - n_ground;
+            const uint64_t nb3[3] = {t.n_lead, 0u, n_rest};
+            k.n_groups = n_rest ? 3 : 1;
+            k.grp_pix[1] = f.ground_pos0;
+            k.grp_pix[2] = f.ground_pos1;
+            k.grp_pix[3] = f.sky_pos0;
+            for (int g = 1; g < 3; ++g) {
+                k.grp_items[g] = static_cast<uint32_t>(64u * nb3[g] * S);
+                k.grp_blocks[g] = static_cast<uint32_t>(nb3[g] * S);
+                k.div_grp[g] = make_udiv(static_cast<uint32_t>(std::max<uint64_t>(64u * nb3[g], 1u)));
+            }
+        }
         sc->used_lead = t.n_lead;
         sc->used_sky = f.sky_kernel ? t.n_sky : 0u;
     } else {
@@ -1379,7 +1441,6 @@ void deal_groups(const Frame &f, Pass &p, rt::KParams &k)
 int bind_deep_queue(const Frame &f, Pass &p, rt::KParams &k)
 {
     rt_scene *sc = f.sc;
-    const rt_options &O = sc->opt;
     const uint64_t n_pixels = k.n_pixels, n_samples = n_pixels * (p.s1 - p.s0);
     const uint32_t wb = p.wb;
     k.deep_depth = 0;
@@ -1387,9 +1448,7 @@ int bind_deep_queue(const Frame &f, Pass &p, rt::KParams &k)
     p.two_part = false;
     // (diag lone_unsplit: a lone pass dealt by tile classes is not split, its trapped paths
     // starting in its first items; slower, the accumulation then waits for the whole launch)
-    if (!(f.pl.in.may_split && (n_samples >= O.deep_min_items || p.in_flight) &&
-          (p.in_flight || !p.ordered || !(O.diag & RT_DIAG_LONE_UNSPLIT))))
-        return RT_OK;
+    if (!pass_is_split(f, p, n_samples)) return RT_OK;
     const uint32_t rcap = deep_region_cap(n_samples), cap = 8u * rcap;
     const size_t px_bytes = deep_px_bytes(n_pixels);
     bool fresh = false;
@@ -1458,6 +1517,96 @@ int launch_main(const Frame &f, Pass &p, const rt::KParams &k)
     rt_scene *sc = f.sc;
     RT_HIP(rt::launch_render(f.c.variant, f.c.cull_mode, k, p.grid, p.xst));
     p.stats_waves = p.grid * 4u;
+    if (p.two_part && !p.ground) {  // (with a ground kernel: after the redo launch)
+        if (!sc->ev_main[p.wb]) RT_HIP(hipEventCreateWithFlags(&sc->ev_main[p.wb], hipEventDisableTiming));
+        RT_HIP(hipEventRecord(sc->ev_main[p.wb], p.xst));
+    }
+    return RT_OK;
+}
+
+// The ground kernel of a pass: the pass's samples of the ground tiles' pixels into
+// their slots, the punted ones into the workspace's redo list (sized for every ground sample of
+// the pass; its count words are the queue-counter block's, zeroed with it). Beside other renders
+// it runs on the pass's stream before the main launch; a pass issued alone runs it on another
+// render stream, beside the main launch (which leaves room for it and the sky kernel), after the
+// pass's counters are zeroed (ev_gpre), and the redo launch waits for it (ev_ground).
+#ifndef RT_GROUND_SPT
+#define RT_GROUND_SPT 32u  // samples per thread of the ground kernel (A/B build switch)
+#endif
+#ifndef RT_GROUND_ASIDE
+#define RT_GROUND_ASIDE 1  // A/B build switch: 0 runs the lone pass's ground kernel before its main launch
+#endif
+int launch_ground_tiles(const Frame &f, Pass &p, const rt::KParams &k, rt::RedoList &redo)
+{
+    rt_scene *sc = f.sc;
+    const uint32_t wb = p.wb, n_pix = f.ground_pos1 - f.ground_pos0, S = p.s1 - p.s0;
+    const uint64_t n_samples = static_cast<uint64_t>(n_pix) * S;
+    if (int rc = ensure((void **)&sc->redo[wb], &sc->redo_bytes[wb], n_samples * sizeof(uint32_t)); rc) return rc;
+    if (!sc->redo_stat) {
+        RT_HIP(hipMalloc((void **)&sc->redo_stat, rt_scene::kRing * sizeof(uint32_t)));
+        RT_HIP(hipMemset(sc->redo_stat, 0, rt_scene::kRing * sizeof(uint32_t)));
+    }
+    if (sc->ground_call != sc->calls) {
+        // the frame's first pass with a ground kernel (calls is the frame's own number, from 1):
+        // the frame's slot of redo_stat; the slot half a ring ahead is zeroed for the frame that will
+        // take it. Its last writer is 128 ground frames back, and at most kMaxWs passes are ever in
+        // flight (begin_pass waits for the workspace's ev_free, recorded behind every earlier pass's
+        // accumulation on the caller's stream), so that writer has long ended.
+        sc->ground_call = sc->calls;
+        sc->ground_ring = (sc->ground_ring + 1u) % rt_scene::kRing;
+        sc->ground_samples = 0;
+        RT_HIP(hipMemsetAsync(sc->redo_stat + (sc->ground_ring + rt_scene::kRing / 2u) % rt_scene::kRing, 0, sizeof(uint32_t), p.xst));
+    }
+    sc->ground_samples += n_samples;
+    redo = rt::RedoList{sc->redo[wb], k.queue_ctr, static_cast<uint32_t>(n_samples), sc->redo_stat + sc->ground_ring};
+    rt::KGround g{};
+    g.fc = k.fc;
+    g.block_perm = k.block_perm;
+    g.pos0 = f.ground_pos0;
+    g.n_pix = n_pix;
+    g.n_samp = S;
+    g.spt = RT_GROUND_SPT;
+    g.n_wg = (n_pix + 63u) / 64u;
+    g.slots = k.slots;
+    g.n_slots = k.n_slots;
+    g.blob = k.blob;
+    g.n_geo = k.n_geo;
+    g.n_always = k.n_always;
+    g.n_supers = k.n_supers;
+    g.supers_offset = k.supers_offset;
+    g.shade_offset = k.shade_offset;
+    g.n_spheres = k.n_spheres;
+    g.fast_roots = k.fast_roots;
+    g.clus_pad = k.clus_pad;
+    g.redo = redo;
+    g.segments = k.segments;
+    g.dbg = k.dbg;
+    p.ground_aside = RT_GROUND_ASIDE && f.pipe() && f.pl.streams >= 3u && !p.in_flight && !(sc->opt.diag & RT_DIAG_SKY_SERIAL);
+    if (!p.ground_aside) {
+        RT_HIP(rt::launch_ground(f.c.variant, g, p.xst));
+        return RT_OK;
+    }
+    if (!sc->ev_gpre) RT_HIP(hipEventCreateWithFlags(&sc->ev_gpre, hipEventDisableTiming));
+    if (!sc->ev_ground) RT_HIP(hipEventCreateWithFlags(&sc->ev_ground, hipEventDisableTiming));
+    // (the stream after the sky kernel's: consecutive render streams sit on different queues)
+    hipStream_t g_st = sc->xs[(wb % f.pl.streams + 2u) % f.pl.streams];
+    RT_HIP(hipEventRecord(sc->ev_gpre, p.xst));
+    RT_HIP(hipStreamWaitEvent(g_st, sc->ev_gpre, 0));
+    RT_HIP(rt::launch_ground(f.c.variant, g, g_st));
+    RT_HIP(hipEventRecord(sc->ev_ground, g_st));
+    return RT_OK;
+}
+
+// The redo launch of a pass with a ground kernel: the punted samples from scratch through the
+// general kernel's list instantiation, a fixed grid of one workgroup per CU (the count is on the
+// device); its paths reach the deep queue like the main launch's.
+int launch_redo(const Frame &f, const Pass &p, const rt::KParams &k, const rt::RedoList &redo)
+{
+    if (p.ground_aside) RT_HIP(hipStreamWaitEvent(p.xst, f.sc->ev_ground, 0));
+    const rt::KList kl{k, redo};
+    rt_scene *sc = f.sc;
+    RT_HIP(rt::launch_render_list(f.c.variant, kl, static_cast<uint32_t>(std::max(1, sc->cu_count)), p.xst));
+    // the first part of the accumulation reads the ground tiles' slots too: ev_main after this launch
     if (p.two_part) {
         if (!sc->ev_main[p.wb]) RT_HIP(hipEventCreateWithFlags(&sc->ev_main[p.wb], hipEventDisableTiming));
         RT_HIP(hipEventRecord(sc->ev_main[p.wb], p.xst));
@@ -1686,6 +1835,19 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     // (max_depth 0: every sample's colour is 0, main.cxx:74, not the sky's)
     f.sky_kernel = f.ord && f.ord->d_perm && f.ord->t.n_sky && P.max_depth > 0 && !(O.diag & RT_DIAG_NO_SKY) && !moments;
     f.sky_pos0 = f.sky_kernel ? static_cast<uint32_t>(64u * static_cast<uint64_t>(f.ord->n_blocks - f.ord->t.n_sky)) : k.n_pixels;
+    // the ground tiles: the order's middle class is its tiled blocks of class 1,
+    // in ascending order, then the untiled blocks (class 1 too, numbered after every tile)
+    f.ground = false;
+    f.ground_pos0 = f.ground_pos1 = f.sky_pos0;
+#ifndef RT_NO_GROUND  // A/B build switch: every pass as before the ground kernel
+    // (f.sky_kernel: a culled LDS kernel dealt by tile classes, single samples, no moments, no_sky unset)
+    if (f.sky_kernel && sc->ground_ok && ground_pass_ok(O, P)) {
+        const uint32_t n_ground = ground_blocks(f.ord->n_blocks, f.ord->t.n_lead, f.ord->t.n_sky, k.W, k.num_rows, k.tile_lw);
+        f.ground = n_ground != 0u;
+        f.ground_pos0 = 64u * f.ord->t.n_lead;
+        f.ground_pos1 = f.ground_pos0 + 64u * n_ground;
+    }
+#endif
     f.ring = static_cast<uint32_t>(sc->calls % rt_scene::kRing);
     ++sc->calls;
 
@@ -1709,7 +1871,12 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
         if (c.wave) {
             if (int rc = launch_wavefront(f, p, k, wq); rc) return rc;
         } else {
+            rt::RedoList redo{};
+            if (p.ground)
+                if (int rc = launch_ground_tiles(f, p, k, redo); rc) return rc;
             if (int rc = launch_main(f, p, k); rc) return rc;
+            if (p.ground)
+                if (int rc = launch_redo(f, p, k, redo); rc) return rc;
             if (k.deep_depth)
                 if (int rc = launch_deep(f, p, k); rc) return rc;
         }
@@ -1895,6 +2062,10 @@ int rt_scene_usage_get(const rt_scene *sc, rt_scene_usage *out)
     for (int b = 0; b < 2; ++b) fixed += static_cast<uint64_t>(sc->blob_units[b]) * 16u;
     fixed += static_cast<uint64_t>(std::max(sc->n_spheres, 1u)) * 16u;  // the trap windows
     fixed += static_cast<uint64_t>(sc->n_spheres) * 32u;                // the two sphere tables (rt_scene_motion)
+    // the ground kernel's redo lists and counts: beside the planner's cut, so in
+    // device_bytes, not in workspace_bytes
+    for (uint32_t w = 0; w < kMaxWs; ++w) fixed += sc->redo_bytes[w];
+    if (sc->redo_stat) fixed += rt_scene::kRing * sizeof(uint32_t);
     u.device_bytes = ws + fixed;
     u.workspace_bytes = ws;
     u.render_streams = sc->used_streams;
@@ -1908,6 +2079,20 @@ int rt_scene_usage_get(const rt_scene *sc, rt_scene_usage *out)
     u.static_lds_bytes = static_cast<uint32_t>(sc->static_lds[1]);
     u.max_lds_bytes = static_cast<uint32_t>(sc->max_lds);
     *out = u;
+    return RT_OK;
+}
+
+int rt_scene_ground_counts(rt_scene *sc, uint64_t *ground_samples, uint64_t *redone_samples)
+{
+    if (!sc) return fail(RT_ERR_INVALID, "rt_scene_ground_counts: null scene");
+    uint32_t redone = 0;
+    if (sc->redo_stat) {
+        RT_HIP(hipSetDevice(sc->device));
+        RT_HIP(hipDeviceSynchronize());
+        RT_HIP(hipMemcpy(&redone, sc->redo_stat + sc->ground_ring, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    if (ground_samples) *ground_samples = sc->ground_samples;
+    if (redone_samples) *redone_samples = redone;
     return RT_OK;
 }
 

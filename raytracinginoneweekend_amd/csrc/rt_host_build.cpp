@@ -802,6 +802,32 @@ tile_order classify_tiles(const rt_camera &cam, uint32_t W, uint32_t H, uint32_t
     return out;
 }
 
+// ---- the ground class ---------------------------------------------------
+bool ground_scene_ok(const rt_sphere *s, const rt_material *m, const blob_t &b, const scene_geom &g)
+{
+    if (!g.has_root || b.always.empty() || b.always.size() > 8u) return false;
+    for (uint32_t i : b.always)
+        if (m[s[i].material].kind != RT_LAMBERT) return false;
+    return true;
+}
+
+bool ground_pass_ok(const rt_options &o, const rt_params &p)
+{
+    if (p.max_depth < 2u) return false;
+    if (p.flags & (RT_FLAG_BRUTE_FORCE | RT_FLAG_SCALAR_SCENE | RT_FLAG_WAVEFRONT | RT_FLAG_CUDA_COMPAT)) return false;
+    return !(o.diag & (RT_DIAG_NO_ROOT_BOX | RT_DIAG_NATURAL_ORDER | RT_DIAG_NO_SKY | RT_DIAG_PAIRS));
+}
+
+uint32_t ground_blocks(uint32_t n_blocks, uint32_t n_lead, uint32_t n_sky, uint32_t W, uint32_t num_rows, uint32_t tile_lw)
+{
+    // the pass's tiles as classify_tiles counts them; the other blocks are untiled
+    const uint32_t tw = 1u << tile_lw, th = 64u >> tile_lw;
+    const uint32_t n_tiles = W % tw == 0u ? (W / tw) * (num_rows / th) : 0u;
+    if (n_tiles > n_blocks || n_lead + n_sky > n_blocks) return 0u;
+    const uint32_t n_mid = n_blocks - n_lead - n_sky, n_untiled = n_blocks - n_tiles;
+    return n_mid > n_untiled ? n_mid - n_untiled : 0u;
+}
+
 rt::UDiv make_udiv(uint32_t d)
 {
     rt::UDiv r{0, 0, 0};
@@ -907,6 +933,30 @@ int rt_tile_order(const rt_sphere *spheres, uint32_t n_spheres, const rt_materia
     *n_sky = t.n_sky;
     if (t.perm.size() > cap) return cap ? fail(RT_ERR_CAPACITY, "rt_tile_order: perm buffer too small") : RT_OK;
     std::copy(t.perm.begin(), t.perm.end(), perm);
+    return RT_OK;
+}
+
+// The ground blocks a render of this scene under the default options takes out of that pass's
+// main launch: rt_tile_order's classes, then the rules of the scene and the pass.
+int rt_tile_ground(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, uint32_t n_materials,
+                   const rt_camera *camera, const rt_params *params, uint32_t *n_ground)
+{
+    if ((n_spheres && !spheres) || !materials || !n_materials || !camera || !params || !n_ground)
+        return fail(RT_ERR_INVALID, "rt_tile_ground: null argument or no materials");
+    *n_ground = 0;
+    for (uint32_t i = 0; i < n_spheres; ++i)
+        if (spheres[i].material >= n_materials) return fail(RT_ERR_INVALID, "rt_tile_ground: bad material index");
+    rt_options opt;
+    if (int rc = default_options(opt); rc) return rc;
+    const blob_t b = build_blob(spheres, n_spheres, true, opt.cluster_size);
+    const scene_geom g = scene_geometry(spheres, b);
+    if (!b.n_clusters || !ground_scene_ok(spheres, materials, b, g) || !ground_pass_ok(opt, *params)) return RT_OK;
+    const uint32_t st = params->row_stride ? params->row_stride : 1u;
+    const uint32_t rows = params->num_rows ? params->num_rows
+                          : params->row_offset >= params->height ? 0u
+                                                                 : (params->height - params->row_offset + st - 1u) / st;
+    const tile_order t = classify_tiles(*camera, params->width, params->height, params->row_offset, st, rows, 3u, g);
+    if (t.n_sky) *n_ground = ground_blocks(static_cast<uint32_t>(t.perm.size()), t.n_lead, t.n_sky, params->width, rows, 3u);
     return RT_OK;
 }
 

@@ -67,6 +67,19 @@ struct tile_order {
 tile_order classify_tiles(const rt_camera &cam, uint32_t W, uint32_t H, uint32_t row_offset, uint32_t row_stride,
                           uint32_t num_rows, uint32_t tile_lw, const scene_geom &g, bool sky_only = false);
 
+// ---- the ground class ---------------------------------------------------
+// A pass's ground blocks are the tiled blocks of its order's middle class: classify_tile gives a
+// tile class 1 only when its beam misses every cluster's padded box, the untiled blocks (class 1
+// without a proof) are numbered after every tile, and the order is stable, so they are the
+// positions [n_lead, n_lead + ground_blocks) of the order. A render takes them out of the main
+// launch when the scene and the pass allow it:
+//   the scene: a box over all clusters and 1 to 8 always-tested spheres, every one lambert;
+//   the pass: max_depth >= 2, the culled LDS kernels, the root gate on, and a sky kernel
+//   (dealt by tile classes, single samples, some sky tile; the caller checks that part).
+bool ground_scene_ok(const rt_sphere *s, const rt_material *m, const blob_t &b, const scene_geom &g);
+bool ground_pass_ok(const rt_options &o, const rt_params &p);
+uint32_t ground_blocks(uint32_t n_blocks, uint32_t n_lead, uint32_t n_sky, uint32_t W, uint32_t num_rows, uint32_t tile_lw);
+
 rt::UDiv make_udiv(uint32_t d);
 bool exact_by_reciprocal(float b);
 

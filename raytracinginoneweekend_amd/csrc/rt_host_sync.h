@@ -23,8 +23,11 @@ hipError_t launch_render(int variant, int cull, const KParams &p, uint32_t grid,
 hipError_t deep_occupancy(int variant, int wpb, size_t lds, int *blocks_per_cu, size_t *static_lds);
 hipError_t occupancy_render(int variant, int cull, int *blocks_per_cu, size_t lds, bool pairs = false);
 hipError_t static_lds_render(int variant, int cull, size_t *bytes, bool pairs = false);
+hipError_t launch_render_list(int variant, const KList &k, uint32_t grid, hipStream_t stream);
 // rt_sky.hip
 hipError_t launch_sky(const KSky &k, hipStream_t stream);
+// rt_ground.hip
+hipError_t launch_ground(int variant, const KGround &k, hipStream_t stream);
 // rt_accum.hip
 hipError_t launch_accumulate(const KAccum &k, hipStream_t stream);
 hipError_t launch_epilogue(const float *in, uint8_t *out, uint64_t n, hipStream_t stream);

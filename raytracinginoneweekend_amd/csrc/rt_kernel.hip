@@ -62,8 +62,11 @@ constexpr int kMinWaves = (CULL == 7 && !STATS) ? RT_CULL7_WAVES : RT_MIN_WAVES_
 // between twice the waves)
 // PAIRS: the main launch of a pass that stores sample pairs (KParams::n_pair_items != 0,
 // DESIGN.md §4.2), its own instantiation: the pair bookkeeping costs the loop ~3% of its issue
-template <int V, int CULL, bool STATS, bool COUNT, bool DEEP, int WPB, bool PAIRS>
-__device__ __forceinline__ void render_body(const KParams &p)
+// LIST: the redo launch of a pass with a ground kernel, its own instantiation:
+// the items are the words of the redo list `lx`, dealt in chunks of 64 by one atomic; each is
+// rendered from scratch like any item of the main launch
+template <int V, int CULL, bool STATS, bool COUNT, bool DEEP, int WPB, bool PAIRS, bool LIST = false>
+__device__ __forceinline__ void render_body(const KParams &p, const RedoList &lx = RedoList{})
 {
     constexpr bool FAST = (V == V_FAST_LDS);
     // Scene blob -> LDS (or read in place from global for the scalar-cache A/B variant):
@@ -217,7 +220,18 @@ __device__ __forceinline__ void render_body(const KParams &p)
             if (DEEP ? cnext >= cend : cnext >= run_end) {
             if (cnext >= cend) {
                 uint32_t c = 0;
-                if constexpr (DEEP) {
+                if constexpr (LIST) {
+                    // the list's count is final (the ground kernel has ended): 64 items per ticket
+                    if (lane == 0) c = atomicAdd(lx.ctr + kRedoDeal, 1u);
+                    c = __builtin_amdgcn_readfirstlane(c);
+                    const uint32_t n = __builtin_amdgcn_readfirstlane(min(lx.ctr[kRedoCount], lx.cap));
+                    if (c >= (n + 63u) / 64u) {
+                        exhausted = true;
+                        continue;
+                    }
+                    cnext = 64u * c;
+                    cend = min(64u * c + 64u, n);
+                } else if constexpr (DEEP) {
                     if (WPB == 8 && P.deep_static) {  // (the lone deep launch's instantiation only)
                         // the regions' path counts are final (the main launch has ended): lanes
                         // 0-7 read them in one round trip; chunk j of the concatenated regions
@@ -297,7 +311,10 @@ __device__ __forceinline__ void render_body(const KParams &p)
                 cend = __builtin_amdgcn_readfirstlane(min(64u * (qb0 + S(c + 1u)), GI));
                 }
             }
-            if constexpr (!DEEP) {
+            if constexpr (LIST) {
+                run_end = cend;
+                run_base = cnext;
+            } else if constexpr (!DEEP) {
                 // the chunk's run within one sample: group grp's item J is sample J / ng at
                 // position p0 + J % ng, slot [sample][position] (sample-major over the pass's
                 // permuted enumeration); one group (natural order): slot J
@@ -356,7 +373,9 @@ __device__ __forceinline__ void render_body(const KParams &p)
                     }
                     HID(sl) = hid;
                 } else {
-                    it = I;  // a pair item (the pass's full blocks) or a single tail sample; its slot
+                    // a pair item (the pass's full blocks) or a single tail sample; its slot
+                    if constexpr (LIST) it = lx.items[checked<STATS>(I, lx.cap, BC_REDO_ITEM, p.dbg)];
+                    else it = I;
                     alive = fresh = true;
                 }
             }
@@ -890,6 +909,15 @@ __global__ __launch_bounds__(64 * WPB, (WPB == 8 && !STATS ? RT_DEEP_WIDE_WAVES 
     render_body<V, 7, STATS, COUNT, true, WPB, false>(p);
 }
 
+// the redo launch of a pass with a ground kernel (culled scenes, single samples): the items of the
+// pass's redo list through the unchanged loop
+template <int V, bool STATS, bool COUNT>
+__global__ __launch_bounds__(256, (kMinWaves<V, 7, STATS>)) void render_list_kernel(const KList k)
+{
+    if (k.redo.stat && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(k.redo.stat, min(k.redo.ctr[kRedoCount], k.redo.cap));
+    render_body<V, 7, STATS, COUNT, false, 4, false, true>(k.p, k.redo);
+}
+
 // ---- launchers (called from rt_host.cpp) ---------------------------------------------
 // cull: 0 = brute force (every sphere, index order), 7 = two-level cluster walk with
 // transposed member tests (the default)
@@ -944,6 +972,23 @@ hipError_t launch_render(int variant, int cull, const KParams &p, uint32_t grid,
     const size_t lds = (size_t)p.lds_units * 16u;
     void *args[] = {const_cast<KParams *>(&p)};
     return hipLaunchKernel(fn, dim3(grid), dim3(64u * (uint32_t)wpb), args, lds, stream);
+}
+
+template <bool COUNT> static const void *render_list_ptr(int variant)
+{
+    switch (variant) {
+    case V_EXACT_LDS: return reinterpret_cast<const void *>(&render_list_kernel<V_EXACT_LDS, false, COUNT>);
+    case V_FAST_LDS: return reinterpret_cast<const void *>(&render_list_kernel<V_FAST_LDS, false, COUNT>);
+    case V_STATS_LDS: return reinterpret_cast<const void *>(&render_list_kernel<V_EXACT_LDS, true, true>);
+    default: return nullptr;
+    }
+}
+hipError_t launch_render_list(int variant, const KList &k, uint32_t grid, hipStream_t stream)
+{
+    const void *fn = k.p.segments ? render_list_ptr<true>(variant) : render_list_ptr<false>(variant);
+    if (!fn) return hipErrorInvalidValue;
+    void *args[] = {const_cast<KList *>(&k)};
+    return hipLaunchKernel(fn, dim3(grid), dim3(256), args, (size_t)k.p.lds_units * 16u, stream);
 }
 
 // workgroups per CU and static LDS of the deep kernel with wpb waves per workgroup

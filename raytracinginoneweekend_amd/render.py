@@ -656,6 +656,16 @@ def tile_order(scene, params, camera=None):
     return perm, nl.value, ns.value
 
 
+def tile_ground(scene, params, camera=None):
+    """rt_tile_ground: the pass's ground blocks, positions [n_lead, n_lead + n) of
+    tile_order()'s perm; 0 when the scene or the pass keeps them in the main launch."""
+    s, m = _scene_arrays(scene)
+    n = C.c_uint32(0)
+    check(lib().rt_tile_ground(abi.ptr(s, C.POINTER(abi.RtSphere)), len(s), abi.ptr(m, C.POINTER(abi.RtMaterial)), len(m),
+                               C.byref(_cam(camera, params)), C.byref(params), C.byref(n)))
+    return n.value
+
+
 def trap_windows(scene):
     """rt_trap_windows: per sphere (cos_lo, cos_hi), the trap window of an isolated glass ball
     (DESIGN.md §4.1a); (1, 0) for a sphere without one."""
@@ -834,6 +844,14 @@ class DeviceScene:
         h, d, n = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         check(lib().rt_scene_order_counts(self.handle, C.byref(h), C.byref(d), C.byref(n)))
         return {"host_orders": h.value, "device_orders": d.value, "hits": n.value}
+
+    def ground_counts(self):
+        """rt_scene_ground_counts: the ground kernel's samples in the last frame that used it and
+        how many of them went to the redo launch, as (ground, redone). Waits for
+        the device."""
+        g, r = C.c_uint64(0), C.c_uint64(0)
+        check(lib().rt_scene_ground_counts(self.handle, C.byref(g), C.byref(r)))
+        return g.value, r.value
 
     def usage(self):
         """rt_scene_usage_get: device bytes held and the last render's cut, as a dict."""

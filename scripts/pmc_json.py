@@ -25,12 +25,16 @@ ap.add_argument("root")
 ap.add_argument("out")
 ap.add_argument("--kernel", default="render_kernel<0, 7, false, false, false> + render_deep_kernel<0, false, false, 4|8> + sky_kernel",
                 help="kernel names joined by ' + '; the first one's dispatches count the frames")
+ap.add_argument("--also", default="ground_kernel<false, false, false> + render_list_kernel<0, false, false>",
+                help="kernels of the frame that bench.py's stamp does not name (DESIGN.md §6): summed into the frame's "
+                     "totals like the others, listed under 'also'")
 ap.add_argument("--config", default="c3")
 ap.add_argument("--camera", default="reference")
 ap.add_argument("--traversal", default="cull")
 ap.add_argument("--simds", type=int, default=1024)  # 256 CUs x 4 SIMDs
 a = ap.parse_args()
 names = [k.strip() for k in a.kernel.split(" + ") if k.strip()]
+also = [k.strip() for k in a.also.split(" + ") if k.strip()]
 
 
 def matches(k, kernel_name):
@@ -42,7 +46,7 @@ def matches(k, kernel_name):
 
 
 def which(kernel_name):
-    return next((i for i, k in enumerate(names) if matches(k, kernel_name)), None)
+    return next((i for i, k in enumerate(names + also) if matches(k, kernel_name)), None)
 
 
 # Per frame: every dispatch of the kernels in a pass summed and divided by the frames the pass's
@@ -92,6 +96,7 @@ t = sum(dur) / len(dur)
 cycles = m["GRBM_GUI_ACTIVE"] / 8.0
 rec = {
     "kernel": " + ".join(names),
+    "also": also,
     # the build these counters describe: bench.py uses them only for the same library
     "kernel_sha256": kernel_sha256(),
     "lib_sha256": lib_sha256(),
