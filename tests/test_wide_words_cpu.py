@@ -5,7 +5,8 @@ classification). tests/test_wide_words_gpu.py compares the kernels with these re
 that stopped reaching its words or its code path fails here, not silently there. No GPU.
 
 Measured, 16 threads on 8 cores: the restatement renders split/reference in 0.9 - 1.4 s,
-split/corrected in 2.3 - 3.9 s, deep/reference in 0.2 s and deep/corrected in 2.1 - 5.0 s (the
+split/corrected in 2.3 - 3.9 s, deep/reference in 0.2 s, deep/corrected in 2.1 - 5.0 s and
+ground/reference (a sky tile row and a row of far ground: 1.2 segments per sample) in 0.2 s (the
 spread is the machine's other load).
 """
 import os
@@ -52,8 +53,7 @@ def test_frame_and_bands_reach_the_wide_words():
     assert first < 2 ** 32 <= last
 
 
-@pytest.mark.parametrize("mode", sorted(WC.MODES))
-@pytest.mark.parametrize("band", sorted(WC.BANDS))
+@pytest.mark.parametrize("band,mode", WC.BAND_MODES)
 def test_band_renders_in_a_few_seconds(band, mode):
     img, seg, seconds = WC.band_ref(band, mode)
     n = img.shape[0] * WC.W * WC.SPP
@@ -73,6 +73,47 @@ def test_split_band_census():
     assert sky > 0 and surface > 0
     assert kinds == WC.ALL_KINDS
     assert len(perm) == 16 * WC.W // 64 and n_lead > 0 and n_sky > 0
+
+
+def test_ground_band_census():
+    """Under the reference camera the ground band's first tile row is sky and its second is the far
+    ground: 817 ground tiles, proven as tests/test_ground_cpu.py proves them (no ray of theirs meets
+    a clustered sphere), beside 207 tiles that meet the field. Every pixel index is >= 2^31 and
+    every key > 2^33; the only first hit inside ground tiles is the ground (a list of one), and
+    part of their samples reach the sky (those are never redone)."""
+    import ground_checks as GC
+    b = WC.BANDS["ground"]
+    assert b["num_rows"] == 16 and 1000 <= b["row_stride"] <= WC.BANDS["split"]["row_stride"]
+    assert WC.band_tiles("ground", "reference") == (2048, 207, 817, 1024)
+    lo, hi = WC.key_range("ground")
+    assert 2 ** 33 < lo < hi < 2 ** 34 and WC.index_range("ground")[0] >= 2 ** 31
+    s, m = WC.scene()
+    assert GC.check(s, m, WC.camera("reference"), WC.W, WC.H, **b) == (817, 817)
+    hits, sky = GC.first_hits_in_ground_tiles(WC.scene(), WC.params("ground"), WC.camera("reference"))
+    print("first hits in ground tiles", hits, "sky samples", sky)
+    assert list(hits) == np.flatnonzero(GC.clustered(s)[1]).tolist() and len(hits) == 1
+    assert hits[next(iter(hits))] > 64 * WC.SPP * 64 and sky > 0
+
+
+def test_small_frame_has_ground_tiles():
+    """64 x 36: four tile rows, 4 ground tiles (tests/test_ground_cpu.py), whatever the seed."""
+    assert WC.small_ground_tiles() == 4
+    for seed in WC.SEEDS.values():
+        assert rt.tile_ground(WC.scene(), WC.small_params(seed), WC.small_camera()) == 4
+
+
+@pytest.mark.parametrize("name", WC.WIDE_SEEDS)
+def test_redo_frame_redoes_samples_under_the_wide_seeds(name):
+    """The redo frame has 85 ground tiles whatever the seed, and under each wide seed ground samples
+    of three segments and more (they go to the redo launch) beside ground samples that reach the sky
+    (they never do)."""
+    import ground_checks as GC
+    p, cam = WC.redo_params(WC.SEEDS[name]), WC.redo_camera()
+    assert rt.tile_ground(WC.scene(), p, cam) == 85
+    long_paths = GC.long_paths_in_ground_rows(WC.scene(), p, cam)
+    hits, sky = GC.first_hits_in_ground_tiles(WC.scene(), p, cam)
+    print(f"seed {name}: {long_paths} segments past the second, first hits {hits}, {sky} sky samples")
+    assert long_paths > 0 and sky > 0 and len(hits) == 1
 
 
 def test_deep_band_census():

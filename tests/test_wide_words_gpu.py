@@ -3,7 +3,9 @@
 Each sample's two PCG32 streams are seeded from key = (y W + x) spp + s with increments made of the
 64-bit seed; the kernels restate that arithmetic in several places (render_kernel's fresh samples
 and rejection loop, sky_kernel's stepped products, the wavefront generator, aov_kernel, the moments
-accumulation) and carry a path's 64-bit state through the deep queue and the wavefront ray queues.
+accumulation, ground_kernel's sums cd1, cd2, cd3 and steps M, M^2, M^3 from its own key0, and
+render_list_kernel's key rebuilt from a slot word of the redo list) and carry a path's 64-bit state
+through the deep queue and the wavefront ray queues.
 The other GPU suites keep the key, both increments' high words and the pixel index's top bit at
 zero. Here bands of a 8192 x 524280 frame (keys 2^33.4 .. 2^34.0, every pixel index >= 2^31) with
 seed 1234 + 2^32, and the small frame with seeds up to 2^64 - 1, are rendered through every path and
@@ -12,6 +14,12 @@ on such words; tests/test_wide_words_cpu.py fixes that the cases reach what they
 
 Every comparison is on uint32 views with zero mismatches allowed, and the segment count equals the
 restatement's wherever the render reports one. A render is at most 16 x 8192 x 5 samples.
+
+The ground kernel and the redo launch run in split passes with ground tiles only,
+which none of the cases above has: section 8 renders the `ground` band (817 ground tiles beside lead
+and sky tiles), the small frame (4 ground tiles) and the redo frame (85 ground tiles, a tenth of
+their samples redone, under the wide seeds) in flight and as a lone split pass, and asserts
+the scene's ground counts, so that a frame that fell back to the main launch fails.
 """
 import ctypes as C
 import os
@@ -36,8 +44,8 @@ SENTINEL = 0x5a5a5a5a
 # The deep band's passes are far smaller than rt_options.deep_min_items, below which a pass issued
 # alone is not split: 0 there, so that its long paths go through the deep queue and the deep launch.
 CASES = {}
-for _band in sorted(WC.BANDS):
-    for _mode in sorted(WC.MODES):
+for _band, _mode in WC.BAND_MODES:
+    if _band != "ground":  # (section 8's)
         CASES[f"{_band}-{_mode}"] = dict(band=_band, mode=_mode, base=dict(deep_min_items=0) if _band == "deep" else {})
 for _name in WC.SEEDS:
     CASES[f"small-{_name}"] = dict(seed=WC.SEEDS[_name], base={})
@@ -315,3 +323,91 @@ def test_tile_order_of_the_split_band(tile_classes):
     print("blocks", len(want), "lead", wl, "sky", ws, "| device lead", gl, "sky", gs)
     assert wl > 0 and ws > 0 and (gl, gs) == (wl, ws)
     assert got.dtype == np.uint32 and got.shape == want.shape and np.array_equal(got, want)
+
+
+# ---- 8. the ground kernel and the redo launch ------------------------------------------------------------
+IN_FLIGHT = dict(render_streams=3, in_flight=1)  # every launch of a pass on the pass's stream
+LONE_SPLIT = dict(deep_min_items=1)              # a pass issued alone is split: the ground kernel on a stream of its own
+# _count, _passes as in VARIANTS; _seed: another seed than the band's
+GROUND_VARIANTS = {
+    "in_flight": dict(IN_FLIGHT),
+    "lone_split": dict(LONE_SPLIT),
+    "counting": dict(IN_FLIGHT, _count=True),
+    "instrumented": dict(LONE_SPLIT, stats=True, _count=True),
+    "two_passes": dict(IN_FLIGHT, _passes=True, _count=True),
+    "tile_classes": dict(IN_FLIGHT, tile_classes=1),
+    "seed_alias": dict(IN_FLIGHT, _seed=WC.SEED + 2 ** 62),
+}
+
+
+def render_ground(scene, cam, p, options, count=False):
+    """One rt_render_device call on a fresh scene with `options`: (frame as uint32, segments or None,
+    rt_scene_usage, the instrumented kernels' first bounds violation, (ground samples, redone))."""
+    import torch
+    out = torch.full((abi.rows_of(p), p.width, 3), SENTINEL, dtype=torch.int32, device="cuda:0")
+    cnt = torch.zeros(3, dtype=torch.int64, device="cuda:0") if count else None
+    ds = rt.DeviceScene(scene, device=0, options=rt.options(rt.default_options(), **options))
+    try:
+        ds.render(cam, p, out.data_ptr(), torch.cuda.current_stream().cuda_stream, cnt.data_ptr() if count else None)
+        torch.cuda.synchronize()
+        usage, counts = ds.usage(), ds.ground_counts()
+        dbg = (C.c_uint64 * 16)()
+        R.check(rt.lib().rt_scene_debug_counters(ds.handle, dbg, 1))
+    finally:
+        ds.close()
+    return out.cpu().numpy().view(np.uint32), int(cnt[0]) if count else None, usage, int(dbg[15]), counts
+
+
+@pytest.mark.parametrize("variant", list(GROUND_VARIANTS))
+def test_ground_band_matches_restatement(variant):
+    """The ground band under the reference camera: 817 tiles x 64 pixels x 5 samples through
+    ground_kernel at keys past 2^33 and pixel indices past 2^31, part of them redone by
+    render_list_kernel (scattered rays that pass the box over the field), part not (the ground
+    tiles' sky samples never are: tests/test_wide_words_cpu.py::test_ground_band_census)."""
+    v = dict(GROUND_VARIANTS[variant])
+    count, passes, seed = v.pop("_count", False), v.pop("_passes", False), v.pop("_seed", WC.SEED)
+    p, cam = WC.params("ground", seed=seed), WC.camera("reference")
+    if passes:  # a pass of 4 samples, then one of the fifth: sample_begin = 4 there
+        v["max_pass_bytes"] = abi.rows_of(p) * p.width * 12 * 4
+    ref, ref_seg, _ = WC.band_ref("ground", "reference")
+    n_ground = WC.band_tiles("ground", "reference")[2]
+    got, seg, usage, violation, (ground, redone) = render_ground(WC.scene(), cam, p, v, count)
+    print(f"ground band, {variant}: {ground} ground samples, {redone} redone, usage {usage}")
+    assert_bits(got, ref, f"ground band, {variant}")
+    if count:
+        assert seg == ref_seg
+    assert violation == 0
+    if passes:
+        assert 0 < usage["pass_samples"] < p.spp, usage
+    assert usage["lead_tiles"] > 0 and usage["sky_tiles"] > 0 and usage["split_passes"] >= 1, usage
+    assert n_ground >= 64 and ground == n_ground * 64 * WC.SPP
+    assert 0 < redone < ground
+
+
+@pytest.mark.parametrize("name", ["hi32", "max", "bit63", "alias62"])
+def test_small_frame_ground_tiles_with_wide_seeds(name):
+    """The small frame's 4 ground tiles in flight: the increments' high words (hi32), every bit set
+    (max), bit 63 of an increment (bit63), and a seed past 2^62 that names seed 1234's streams."""
+    seed = WC.SEEDS[name]
+    ref, ref_seg = WC.small_ref(seed)
+    got, seg, _, _, (ground, redone) = render_ground(WC.scene(), WC.small_camera(), WC.small_params(seed), IN_FLIGHT, True)
+    print(f"small frame, seed {name}: {ground} ground samples, {redone} redone")
+    assert_bits(got, ref, f"small frame, seed {name}, in flight")
+    assert seg == ref_seg
+    assert WC.small_ground_tiles() == 4 and ground == 4 * 64 * WC.SMALL[2]
+    assert redone <= ground
+
+
+@pytest.mark.parametrize("name", WC.WIDE_SEEDS)
+def test_redo_frame_with_wide_seeds(name):
+    """The redo frame in flight: 85 ground tiles, part of whose samples render_list_kernel redoes
+    under each wide seed (tests/test_wide_words_cpu.py shows ground samples of three segments and
+    more for each), its key rebuilt from the slot word with that seed's increments."""
+    seed = WC.SEEDS[name]
+    ref, ref_seg = WC.redo_ref(seed)
+    got, seg, _, _, (ground, redone) = render_ground(WC.scene(), WC.redo_camera(), WC.redo_params(seed), IN_FLIGHT, True)
+    print(f"redo frame, seed {name}: {ground} ground samples, {redone} redone")
+    assert_bits(got, ref, f"redo frame, seed {name}, in flight")
+    assert seg == ref_seg
+    assert ground == 85 * 64 * WC.REDO[2]
+    assert 0 < redone < ground

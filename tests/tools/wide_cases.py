@@ -13,9 +13,14 @@ Every sample owns two PCG32 streams: key = (y W + x) spp + s, increments ((2 see
                y W + x >= 2^31, keys 2^33.4 .. 2^34.0
                `deep`: the 8 rows from 366992; under the corrected camera its paths are trapped in
                glass (16.7 segments per sample), under the reference camera it is sky
+               `ground`: 16 rows 348000, 350000, ... (stride 2000) just under that horizon: the first
+               tile row is sky; of the second, the far ground, 817 tiles are ground tiles (their
+               beams meet no cluster: ground_kernel and the redo launch render them when the pass
+               is split) and 207 meet the field; keys 2^33.7 .. 2^33.8
   the seeds    SEED = 1234 + 2^32 on the bands; on the small frame (the huge scene at 64 x 36, 4 spp)
                every seed of SEEDS, among them the aliases: the increments drop the seed's top two
                bits, so s and s + 2^62 name the same streams
+               and on the redo frame (128 x 72, 5 spp, the redo camera: 85 ground tiles) the wide ones
   cuda-compat  the engine state x + y W + seed is 32 bits wide: the last 8 rows of the frame with
                seed 100000 wrap 2^32 inside the band
 
@@ -41,7 +46,11 @@ THREADS = 16
 W, H, SPP, DEPTH = 8192, 524280, 5, 64
 SEED = 1234 + 2 ** 32
 BANDS = {"split": dict(row_offset=270000, row_stride=9800, num_rows=16),
-         "deep": dict(row_offset=366992, row_stride=1, num_rows=8)}
+         "deep": dict(row_offset=366992, row_stride=1, num_rows=8),
+         "ground": dict(row_offset=348000, row_stride=2000, num_rows=16)}
+# the (band, camera) pairs the suites render; the ground band is for the reference camera only
+BAND_MODES = [("deep", "corrected"), ("deep", "reference"), ("split", "corrected"), ("split", "reference"),
+              ("ground", "reference")]
 MODES = {"reference": rt.REFERENCE, "corrected": rt.CORRECTED}
 
 SMALL = (64, 36, 4)  # W, H, spp of the small frame (the golden render huge_64x36_s4's)
@@ -86,6 +95,20 @@ def index_range(band):
 
 def camera(mode):
     return rt.Camera.default(W, H, MODES[mode])
+
+
+@functools.lru_cache(maxsize=None)
+def band_tiles(band, mode):
+    """(blocks, lead tiles, ground tiles, sky tiles) of the band's pass, from the host's
+    classification (rt.tile_order, rt.tile_ground)."""
+    perm, n_lead, n_sky = rt.tile_order(scene(), params(band), camera(mode))
+    return len(perm), n_lead, rt.tile_ground(scene(), params(band), camera(mode)), n_sky
+
+
+@functools.lru_cache(maxsize=None)
+def small_ground_tiles():
+    """The small frame's ground tiles (the class does not depend on the seed)."""
+    return rt.tile_ground(scene(), small_params(BASE_SEED), small_camera())
 
 
 def params(band, seed=SEED, rows=None, **kw):
@@ -133,6 +156,28 @@ def small_params(seed, **kw):
 def small_ref(seed):
     """(image (36, 64, 3), segments) of the small frame with `seed`."""
     img, seg = O.render_f32(*scene(), small_camera().c, small_params(seed), threads=THREADS)
+    return _frozen(img)[0], seg
+
+
+# the redo frame: the huge scene at 128 x 72, 5 spp, under tests/tools/ground_checks.py's redo camera
+# (85 ground tiles, about a tenth of whose samples go to the redo launch): render_list_kernel under
+# the wide seeds, which the small frame's 4 ground tiles barely reach
+REDO = (128, 72, 5)
+
+
+def redo_camera():
+    import ground_checks as GC
+    return GC.redo_camera(REDO[0] / REDO[1])
+
+
+def redo_params(seed, **kw):
+    return rt.make_params(REDO[0], REDO[1], REDO[2], DEPTH, seed, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def redo_ref(seed):
+    """(image (72, 128, 3), segments) of the redo frame with `seed`."""
+    img, seg = O.render_f32(*scene(), redo_camera().c, redo_params(seed), threads=THREADS)
     return _frozen(img)[0], seg
 
 
