@@ -997,6 +997,119 @@ typedef struct rt_preview_output_t {
 } rt_preview_output_t;
 int rt_preview_output(rt_preview *pv, rt_preview_output_t *out);
 
+/* ---- the progressive session: a frame in sample windows --------------------------
+ * A session fixes a scene, a camera and an rt_params record P. P.spp = N >= 2 is the WHOLE frame's
+ * sample count; the row fields and RT_FLAG_FULL_FRAME are honoured; flags are accepted or refused
+ * exactly as rt_render_var_device does. The session owns two device planes of n_pixels x 3 floats
+ * (n_pixels = P.width x the rows P renders), the running sums `acc` and the luminance moments
+ * {L_0, m1, m2} of rt_render_var_device's accumulation, and a count `done`: 0 after creation, and always
+ * a multiple of 4 or equal to N.
+ *   Step(n)  m = min(n, N - done). n % 4 != 0 with n < N - done is RT_ERR_INVALID (passes start on
+ *            multiples of 4). n = 0 or done = N renders nothing. Otherwise samples [done, done + m) of
+ *            the N-sample frame are rendered (the keys (pixel) * N + s, the streams and the sample
+ *            numbers are the frame's) and folded into the planes by the accumulation of
+ *            rt_render_var_device, in that frame's own addition order: per block of 4 samples
+ *            acc = acc + ((c0 + c1) + (c2 + c3)), then the N % 4 tail one by one, which arrives with
+ *            the last window; the moments sample by sample. Then done += m.
+ *   Resolve  (out given; done >= 2) for every rendered pixel, d = done, every operation binary32 and
+ *            rounded on its own: nf = (float)d; rgb[c] = acc[c] / nf; mean = m1 / nf; ex2 = m2 / nf;
+ *            var = fmaxf(0.0f, ex2 - mean * mean) / (float)(d - 1); rgb8[c] = the texel of rgb[c]
+ *            (pow(c, 1 / 2.2f) in double, narrowed, then (uint8)(255 c)). Laid out as P says; only
+ *            the planes given are written. With d = N these are rt_render_var_device's bits for the
+ *            same arguments, hence rt_render_device's.
+ *   Noise    (out->noisy given) t2 = noise_tau * noise_tau formed once on the host in binary32;
+ *            L = (0.2126f * rgb.r + 0.7152f * rgb.g) + 0.0722f * rgb.b; a pixel is noisy iff
+ *            var > t2 * (L * L). The step zeroes the word on the stream and the resolve adds the
+ *            number of noisy rendered pixels; the caller reads it when it likes, the library never
+ *            waits for it.
+ * The estimate after d < N samples is NOT a d-sample frame (the keys differ): it is the prefix of the
+ * N-sample frame's own sample set. A step is planned like the variance render, as under RT_DIAG_NO_PAIRS
+ * | RT_DIAG_NO_SKY: single-sample slots, proven-sky tiles traced by the main launch; the cut into
+ * passes is made for the window's samples and never changes the bits.
+ * Several sessions on one scene are independent, and plain or multi-pass renders on that scene between
+ * two steps do not disturb them (the sums belong to the session, not to the scene). A step does no host
+ * synchronisation and no allocation after creation beyond what rt_render_var_device itself does; steps
+ * of one session are ordered through its planes in the scene's stream order. After rt_scene_update
+ * moved either epoch of the scene a step is RT_ERR_INVALID with nothing enqueued, until
+ * rt_progressive_reset. rt_scene_usage does not count a session: rt_progressive_info reports its own
+ * 24 B per pixel.                                                                                     */
+typedef struct rt_progressive rt_progressive;
+typedef struct rt_progressive_outputs {
+    uint32_t size;       /* sizeof(rt_progressive_outputs)                                           */
+    float noise_tau;     /* finite, >= 0; read only when noisy is given                              */
+    float *rgb;          /* optional: linear f32, as rt_render_device lays it out                    */
+    float *variance;     /* optional: one float per pixel, as rt_render_var_device lays it out       */
+    uint8_t *rgb8;       /* optional: gamma 1/2.2 texels, 3 bytes per pixel, laid out as rgb         */
+    uint32_t *noisy;     /* optional: one device word, zeroed by the step, the count added           */
+} rt_progressive_outputs;
+typedef struct rt_progressive_info_t {
+    uint32_t size;         /* filled by the call                                                     */
+    uint32_t done, spp;    /* samples folded so far, and N                                           */
+    uint32_t reserved;
+    uint64_t n_pixels;     /* pixels the session renders                                             */
+    uint64_t state_bytes;  /* what rt_progressive_save writes                                        */
+    uint64_t device_bytes; /* the session's device allocation: 24 B per pixel                        */
+} rt_progressive_info_t;
+/* Supported API, like rt_progressive_blob_check below: a caller sizes its windows, or inspects a
+ * checkpoint before it creates a session, with the library's own rule.
+ * The Step rule alone (host arithmetic, no session): *m = min(n_samples, spp - done), or
+ * RT_ERR_INVALID (n_samples is not a multiple of 4 and stops before the frame's end; done is not a
+ * multiple of 4 or spp; done > spp; spp < 2; m null).                                                */
+int rt_progressive_window(uint32_t spp, uint32_t done, uint32_t n_samples, uint32_t *m);
+/* Checks params (as rt_render_var_device: RT_ERR_INVALID / RT_ERR_UNSUPPORTED, before the scene is
+ * looked at), camera, scene and out, then allocates both planes on the scene's device.               */
+int rt_progressive_create(rt_scene *scene, const rt_camera *camera, const rt_params *params, rt_progressive **out);
+/* Step(n_samples), then Resolve (and Noise) when `out` is not NULL, on `stream`. Every argument is
+ * checked before any HIP call and RT_ERR_INVALID names the field: out's record first (a wrong size, no
+ * plane and no count given, two of its pointers equal, a noise_tau that is negative or not finite with
+ * noisy given), then a null session, the Step rule, `out` given while done + m < 2, the scene's
+ * epochs (a resolve-only step, n_samples = 0 with `out`, is refused after a scene update too, although
+ * the planes still hold the old scene's estimate). d_segments: optional device uint64[3], as
+ * rt_render_device: the step adds its render's counts and never zeroes them; a step that renders nothing
+ * leaves them alone.                                                                                  */
+int rt_progressive_step_device(rt_progressive *pg, uint32_t n_samples, const rt_progressive_outputs *out, void *stream,
+                               uint64_t *d_segments);
+int rt_progressive_info(const rt_progressive *pg, rt_progressive_info_t *info);
+/* done = 0 with a new camera and / or seed (NULL: kept); the scene's epochs are taken anew. Nothing is
+ * enqueued, nothing allocated.                                                                        */
+int rt_progressive_reset(rt_progressive *pg, const rt_camera *camera, const uint64_t *seed);
+/* Checkpoints. save waits for the session's enqueued work and writes state_bytes bytes: a header
+ * {magic, RT_API_VERSION, layout tag, rt_params, rt_camera, n_pixels, done}, then both planes
+ * (RT_ERR_CAPACITY: cap is smaller). load waits likewise, refuses a header that does not match the
+ * session (RT_ERR_INVALID, the field named) and a buffer shorter than the header or than state_bytes
+ * (RT_ERR_CAPACITY), then uploads the planes and takes `done`; the epochs are taken anew as by reset. The
+ * blob is opaque and valid for the same library build; the scene's identity is the caller's business.
+ * rt_progressive_blob_check is load's check alone, against a params / camera pair, without a session
+ * (info optional: done, spp, n_pixels, state_bytes of the blob).                                      */
+int rt_progressive_save(rt_progressive *pg, void *host, uint64_t cap);
+int rt_progressive_load(rt_progressive *pg, const void *host, uint64_t bytes);
+int rt_progressive_blob_check(const void *host, uint64_t bytes, const rt_params *params, const rt_camera *camera,
+                              rt_progressive_info_t *info);
+int rt_progressive_destroy(rt_progressive *pg);
+/* The preview session at rest: once the camera stops, a preview session refines
+ * towards the frame the library exists to produce instead of blending new noisy frames. The session
+ * owns a progressive session (allocated on the first call, counted by rt_preview_usage) for the frame
+ * rt_params {width, height, total_spp, max_depth, seed, every row, flags 0}. A call starts a new
+ * refinement when camera, seed or total_spp differ from the one in progress, when either epoch of the
+ * scene moved, or when rt_preview_frame_device was called in between. On a start the guides (albedo,
+ * normal, depth, alpha, sphere_id) are rendered once by rt_render_aov_device with those params and
+ * samples = min(total_spp, p->spp). Every call, on `stream`, no host synchronisation:
+ *   1 step     rt_progressive_step_device(n_samples) resolved into the session's beauty and variance
+ *              planes (the Step rule holds; the first call of a refinement renders at least 2 samples)
+ *   2 split    under RT_PREVIEW_DEMODULATE, as a frame's step 2
+ *   3 filter   as a frame's step 4 on that colour and variance: no temporal stage; the carried variance
+ *              shrinks as samples arrive, so the filter narrows by itself
+ *   4 merge    as a frame's step 5 into d_rgb and / or d_rgb8 ([height][width][3])
+ * The call that completes the frame (done = total_spp), and any call after it, stores the frame itself,
+ * unfiltered: the resolve's f32 bits (rt_render_device's for those params) and their texels. After a
+ * refinement the next rt_preview_frame_device has no history, as after rt_preview_reset.
+ * RT_ERR_UNSUPPORTED on an upscaled session; RT_ERR_INVALID names a null argument, total_spp < 2 or
+ * n_samples. rt_preview_refine_info: samples done and the total of the refinement in progress (0, 0:
+ * none).                                                                                              */
+int rt_preview_refine_device(rt_preview *pv, const rt_camera *camera, uint64_t seed, uint32_t total_spp, uint32_t n_samples,
+                             float *d_rgb, uint8_t *d_rgb8, void *stream);
+int rt_preview_refine_info(const rt_preview *pv, uint32_t *done, uint32_t *total);
+
 /* Device memory a scene holds and how its renders are cut (after the last render call).  */
 typedef struct rt_scene_usage {
     uint64_t device_bytes;     /* every device allocation of the scene                       */

@@ -93,6 +93,21 @@ RT_DIAG = {
 }
 
 
+class RtProgressiveOutputs(C.Structure):
+    """rt_progressive_outputs (include/rt_api.h): what a step's resolve writes, NULL = not wanted."""
+    _fields_ = [
+        ("size", C.c_uint32), ("noise_tau", C.c_float),
+        ("rgb", C.c_void_p), ("variance", C.c_void_p), ("rgb8", C.c_void_p), ("noisy", C.c_void_p),
+    ]
+
+
+class RtProgressiveInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint32), ("done", C.c_uint32), ("spp", C.c_uint32), ("reserved", C.c_uint32),
+        ("n_pixels", C.c_uint64), ("state_bytes", C.c_uint64), ("device_bytes", C.c_uint64),
+    ]
+
+
 class RtStats(C.Structure):
     _fields_ = [
         ("primaries", C.c_uint64), ("segments", C.c_uint64), ("sphere_tests", C.c_uint64),

@@ -134,6 +134,20 @@ def _declare(L):
                                               C.c_void_p, C.c_void_p]),
         "rt_preview_merge_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]),
+        "rt_progressive_window": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32)]),
+        "rt_progressive_create": (C.c_int, [C.c_void_p, P(abi.RtCamera), P(abi.RtParams), P(C.c_void_p)]),
+        "rt_progressive_step_device": (C.c_int, [C.c_void_p, C.c_uint32, P(abi.RtProgressiveOutputs), C.c_void_p,
+                                                 C.c_void_p]),
+        "rt_progressive_info": (C.c_int, [C.c_void_p, P(abi.RtProgressiveInfo)]),
+        "rt_progressive_reset": (C.c_int, [C.c_void_p, P(abi.RtCamera), P(C.c_uint64)]),
+        "rt_progressive_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+        "rt_progressive_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+        "rt_progressive_blob_check": (C.c_int, [C.c_void_p, C.c_uint64, P(abi.RtParams), P(abi.RtCamera),
+                                                P(abi.RtProgressiveInfo)]),
+        "rt_progressive_destroy": (C.c_int, [C.c_void_p]),
+        "rt_preview_refine_device": (C.c_int, [C.c_void_p, P(abi.RtCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+        "rt_preview_refine_info": (C.c_int, [C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
         "rt_scene_kernel_times": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float), P(C.c_uint32)]),
         "rt_scene_debug_counters": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_int]),
         "rt_scene_debug_timeline": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_uint32, P(C.c_uint32)]),

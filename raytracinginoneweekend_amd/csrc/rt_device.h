@@ -357,6 +357,20 @@ struct KPreviewMerge {
     uint32_t W, H;
 };
 
+// progressive_resolve (rt_progressive.hip; rt_progressive_step_device): a session's
+// carried planes, indexed like KAccum::acc / KAccum::mom, after `done` >= 2 samples, into the outputs
+// that are given, placed as accumulate_pixels places a frame's. noisy (optional): the kernel adds the
+// number of pixels with var > t2 (L L).
+struct KResolve {
+    const float *acc, *mom;
+    float *out, *var;
+    uint8_t *out_u8;
+    uint32_t *noisy;
+    float t2;
+    uint32_t done, n_pixels;
+    uint32_t W, tiles_x, tiled_rows, row_offset, row_stride, full_frame, tile_lw;
+};
+
 // The guided upsample (rt_upsample.hip; rt_upsample_device): the low-resolution
 // image (lw x lh; l_variance and o_variance both null: no variance) and its guides, the guides of
 // the output size (W x H), the outputs.

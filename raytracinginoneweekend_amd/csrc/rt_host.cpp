@@ -957,8 +957,16 @@ int stream_leave(rt_scene *sc, hipStream_t st)
     sc->tail_valid = true;
     return RT_OK;
 }
+// A sample window of a frame (a progressive session's step): samples [a, b) of
+// the P.spp-sample frame, a a multiple of 4 and b a multiple of 4 or P.spp, folded into the caller's
+// own planes (indexed like KAccum::acc / KAccum::mom) and never divided: no pass of a window is
+// the frame's last.
+struct Window {
+    uint32_t a, b;
+    float *acc, *mom;
+};
 int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
-                       uint64_t *d_segments, float *d_var = nullptr);
+                       uint64_t *d_segments, float *d_var = nullptr, const Window *win = nullptr);
 } // namespace
 
 extern "C" int rt_render_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, float *d_rgb, void *stream,
@@ -975,9 +983,8 @@ extern "C" int rt_render_device(rt_scene *sc, const rt_camera *camera, const rt_
     return stream_leave(sc, st);
 }
 
-namespace {
-// The params of a variance render (rt_render_var*), decided before any HIP call.
-int check_var_params(const rt_params *p, const char *who)
+// The params of a variance render (rt_render_var*, rt_progressive_create), decided before any HIP call.
+int rthost::check_var_params(const rt_params *p, const char *who)
 {
     if (int rc = check_params(p); rc != RT_OK) return rc;
     const std::string w(who);
@@ -989,7 +996,6 @@ int check_var_params(const rt_params *p, const char *who)
         if (p->flags & u.bit) return fail(RT_ERR_UNSUPPORTED, w + ": " + u.name + " is not supported (the exact kernel only)");
     return RT_OK;
 }
-} // namespace
 
 extern "C" int rt_render_var_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, float *d_rgb, float *d_var,
                          void *stream, uint64_t *d_segments)
@@ -1005,6 +1011,43 @@ extern "C" int rt_render_var_device(rt_scene *sc, const rt_camera *camera, const
     if (int rc = stream_enter(sc, st); rc != RT_OK) return rc;
     if (int rc = render_device_impl(sc, camera, *params, d_rgb, st, d_segments, d_var); rc != RT_OK) return rc;
     return stream_leave(sc, st);
+}
+
+// A progressive session's step (rt_host_post.cpp): samples [a, b) of the frame into the session's
+// planes as one call on the scene (a == b: no render), then `after` (the resolve, which reads
+// those planes) on the caller's stream, inside the call's stream order.
+int rthost::render_window(rt_scene *sc, const rt_camera *camera, const rt_params &P, uint32_t a, uint32_t b, float *acc,
+                          float *mom, hipStream_t st, uint64_t *d_segments, const std::function<int()> &after)
+{
+    RT_HIP(hipSetDevice(sc->device));
+    if (int rc = stream_enter(sc, st); rc != RT_OK) return rc;
+    const Window win{a, b, acc, mom};
+    if (a < b)
+        if (int rc = render_device_impl(sc, camera, P, nullptr, st, d_segments, nullptr, &win); rc != RT_OK) return rc;
+    if (after)
+        if (int rc = after(); rc != RT_OK) return rc;
+    return stream_leave(sc, st);
+}
+
+// The rows and the pixel decomposition of the pass that P describes (rt_host_sync.h).
+rthost::PixelLayout rthost::pixel_layout(const rt_params &P)
+{
+    PixelLayout l{};
+    l.W = P.width;
+    l.row_offset = P.row_offset;
+    l.row_stride = P.row_stride ? P.row_stride : 1;
+    l.num_rows = rows_of(P);
+    l.full_frame = (P.flags & RT_FLAG_FULL_FRAME) ? 1u : 0u;
+    l.n_pixels = static_cast<uint64_t>(P.width) * l.num_rows;
+    // 64-pixel tiles (one wave's lanes for one sample), 8 x 8 (the kernel's decomposition takes
+    // 2^lw x 64/2^lw; 16x4, 32x2 and 64x1 measured alike or slower for strided row shares:
+    // 8-way share 0.61-0.62 ms at 8x8, 0.62 at 32x2, 0.66 at 64x1)
+    l.tile_lw = 3u;
+    const uint32_t tw = 1u << l.tile_lw, th = 64u >> l.tile_lw;
+    const bool tiled = (P.width % tw) == 0u;
+    l.tiles_x = tiled ? P.width / tw : 1u;
+    l.tiled_rows = tiled ? (l.num_rows / th) * th : 0u;
+    return l;
 }
 
 namespace {
@@ -1024,23 +1067,18 @@ int frame_params(const rt_scene *sc, const rt_camera *camera, const rt_params &P
     k.H = P.height;
     k.spp = P.spp;
     k.max_depth = P.max_depth;
-    k.row_offset = P.row_offset;
-    k.row_stride = P.row_stride ? P.row_stride : 1;
-    k.num_rows = rows_of(P);
-    k.full_frame = (P.flags & RT_FLAG_FULL_FRAME) ? 1u : 0u;
+    const PixelLayout l = pixel_layout(P);
+    k.row_offset = l.row_offset;
+    k.row_stride = l.row_stride;
+    k.num_rows = l.num_rows;
+    k.full_frame = l.full_frame;
     k.inc_data = ((2ull * P.seed) << 1u) | 1ull;
     k.inc_cam = ((2ull * P.seed + 1ull) << 1u) | 1ull;
-    const uint64_t n_pixels = static_cast<uint64_t>(P.width) * k.num_rows;
-    if (n_pixels >= (1ull << 31)) return fail(RT_ERR_INVALID, std::string(who) + ": more than 2^31 pixels in one call");
-    k.n_pixels = static_cast<uint32_t>(n_pixels);
-    // 64-pixel tiles (one wave's lanes for one sample), 8 x 8 (the kernel's decomposition takes
-    // 2^lw x 64/2^lw; 16x4, 32x2 and 64x1 measured alike or slower for strided row shares:
-    // 8-way share 0.61-0.62 ms at 8x8, 0.62 at 32x2, 0.66 at 64x1)
-    k.tile_lw = 3u;
-    const uint32_t tw = 1u << k.tile_lw, th = 64u >> k.tile_lw;
-    const bool tiled = (P.width % tw) == 0u;
-    k.tiles_x = tiled ? P.width / tw : 1u;
-    k.tiled_rows = tiled ? (k.num_rows / th) * th : 0u;
+    if (l.n_pixels >= (1ull << 31)) return fail(RT_ERR_INVALID, std::string(who) + ": more than 2^31 pixels in one call");
+    k.n_pixels = static_cast<uint32_t>(l.n_pixels);
+    k.tile_lw = l.tile_lw;
+    k.tiles_x = l.tiles_x;
+    k.tiled_rows = l.tiled_rows;
     k.n_spheres = sc->n_spheres;
     k.n_materials = sc->n_materials;
     return RT_OK;
@@ -1208,11 +1246,12 @@ struct WaveQueues {
 // The plan's memory: under a cap, workspaces left larger (or more numerous) by earlier frames are
 // re-cut once; then the multi-pass sums, the ring's slots, the lone passes' and the ray queues.
 // (The deep queues are bound pass by pass, bind_deep_queue.) Records the cut for rt_scene_usage_get.
-int reserve(rt_scene *sc, const Plan &pl, const KernelChoice &c, WaveQueues &wq)
+int reserve(rt_scene *sc, const Plan &pl, const KernelChoice &c, WaveQueues &wq, bool carried = false)
 {
     const PlanInput &in = pl.in;
     const uint64_t per_sample = in.n_pixels * 12ull;
-    const bool multi_pass = pl.ring_samples < in.spp;
+    // (carried: a window's sums live in its session's planes, whatever the number of its passes)
+    const bool multi_pass = pl.ring_samples < in.spp && !carried;
     if (in.max_workspace_bytes) {
         uint64_t after = 0;
         for (uint32_t w = 0; w < kMaxWs; ++w) {
@@ -1284,6 +1323,10 @@ struct Frame {
     bool ground;
     uint32_t ground_pos0, ground_pos1;
     uint32_t ring;               // the call's slot in the timing events' ring
+    // the call's samples [s_begin, s_end) of the frame's P.spp (a whole frame: all of them), and
+    // the window's own planes (null: the scene's multi-pass sums)
+    uint32_t s_begin, s_end;
+    float *win_acc, *win_mom;
     // more than one render stream: passes rotate over sc->xs and the ring's workspaces
     bool pipe() const { return pl.streams > 1; }
 };
@@ -1336,7 +1379,7 @@ int begin_pass(const Frame &f, Pass &p, rt::KParams &k)
         RT_HIP(hipMemsetAsync(seg_b, 0, 3 * sizeof(unsigned long long), p.xst));
     }
     sc->ctr_dirty[wb] = true;
-    if (p.s0 == 0) RT_HIP(hipEventRecord(sc->ev_begin[f.ring], p.xst));
+    if (p.s0 == f.s_begin) RT_HIP(hipEventRecord(sc->ev_begin[f.ring], p.xst));
     k.sample_begin = p.s0;
     k.sample_end = p.s1;
     k.n_pair_items = static_cast<uint32_t>(((p.s1 - p.s0) - pl.slot_rows(p.s0, p.s1, p.pass_pairs)) * pl.in.n_pixels);
@@ -1736,17 +1779,17 @@ int accumulate(const Frame &f, const Pass &p, const rt::KParams &k)
     const uint32_t full_blocks_end = P.spp & ~3u;  // samples [0, full_blocks_end) form blocks of 4
     rt::KAccum a{};
     a.slots = sc->slots[wb];
-    a.acc = sc->acc;
+    a.acc = f.win_acc ? f.win_acc : sc->acc;
     a.out = f.d_rgb;
     a.out_u8 = nullptr;
-    a.mom = sc->mom;
+    a.mom = f.win_mom ? f.win_mom : sc->mom;
     a.var = f.d_var;
     a.n_pixels = k.n_pixels;
     a.n_samples = s1 - s0;
     a.n_blocks = (std::min(s1, full_blocks_end) - std::min(s0, full_blocks_end)) / 4u;
     a.paired = k.n_pair_items ? 1u : 0u;
     a.first = s0 == 0;
-    a.last = s1 == P.spp;
+    a.last = s1 == P.spp && !f.win_acc;
     a.spp = P.spp;
     a.W = P.width;
     a.tiles_x = k.tiles_x;
@@ -1799,8 +1842,11 @@ int accumulate(const Frame &f, const Pass &p, const rt::KParams &k)
 // mean luminance. Its samples' colours must reach the accumulation one by one, so it is planned as
 // under RT_DIAG_NO_PAIRS | RT_DIAG_NO_SKY whatever the scene's options say.
 int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
-                       uint64_t *d_segments, float *d_var)
+                       uint64_t *d_segments, float *d_var, const Window *win)
 {
+    // (a window: launch_accumulate takes the moments kernel where KAccum::var is set, and no pass of
+    // a window writes through it or through d_rgb)
+    if (win) d_var = win->mom;
     const bool moments = d_var != nullptr;
     rt::KParams k{};
     if (int rc = frame_params(sc, camera, P, k, "rt_render_device"); rc) return rc;
@@ -1819,13 +1865,15 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     const bool may_split = f.deep_split && !c.wave && c.cull_mode == 7 && f.deep_split < P.max_depth;
     if (int rc = pair_occupancy(sc, k, f.c); rc) return rc;
 
-    // the cut of the frame (rt_plan.cpp), then its memory
-    const PlanInput in{k.n_pixels, P.spp, c.wave ? 1u : render_streams_of(O),  // the wavefront variant: caller stream only
+    // the cut of the call's samples (rt_plan.cpp; a window's: passes of a multiple of 4 from its
+    // first sample, itself one), then its memory
+    const uint32_t s_begin = win ? win->a : 0u, s_end = win ? win->b : P.spp;
+    const PlanInput in{k.n_pixels, s_end - s_begin, c.wave ? 1u : render_streams_of(O),  // the wavefront variant: caller stream only
                        O.workspaces_per_stream, O.max_pass_bytes, O.max_workspace_bytes, O.ring_pass_bytes, O.wave_queue_rays,
                        c.wave, moments, c.pairs_ok, (O.diag & RT_DIAG_PAIRS) != 0u, may_split};
     if (int rc = plan_frame(in, f.pl); rc) return rc;
     WaveQueues wq;
-    if (int rc = reserve(sc, pl, c, wq); rc) return rc;
+    if (int rc = reserve(sc, pl, c, wq, win != nullptr); rc) return rc;
 
     // the frame's dealing order (not with sample pairs) and the sky kernel: the
     // tiles proven to send every primary ray to the sky are rendered by sky_kernel at the frame's
@@ -1850,13 +1898,15 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
 #endif
     f.ring = static_cast<uint32_t>(sc->calls % rt_scene::kRing);
     ++sc->calls;
+    f.s_begin = s_begin, f.s_end = s_end;
+    f.win_acc = win ? win->acc : nullptr, f.win_mom = win ? win->mom : nullptr;
 
     auto others_running = [&] { return f.pipe() && sc->last_ws >= 0 && hipEventQuery(sc->ev_done[sc->last_ws]) == hipErrorNotReady; };
     // a frame issued alone that fits one pass takes it whole (Plan::whole); otherwise ring passes
     const uint64_t first_pass =
         pl.whole && !others_running() && !(O.diag & RT_DIAG_IN_FLIGHT) ? pl.lone_samples : pl.ring_samples;
-    for (uint32_t s0 = 0, s1 = 0; s0 < P.spp; s0 = s1) {
-        s1 = static_cast<uint32_t>(std::min<uint64_t>(P.spp, s0 + (s0 == 0 ? first_pass : pl.ring_samples)));
+    for (uint32_t s0 = s_begin, s1 = s_begin; s0 < s_end; s0 = s1) {
+        s1 = static_cast<uint32_t>(std::min<uint64_t>(s_end, s0 + (s0 == s_begin ? first_pass : pl.ring_samples)));
         Pass p{s0, s1};
         p.in_flight = others_running() || (f.pipe() && (O.diag & RT_DIAG_IN_FLIGHT));
         p.pass_pairs = pl.ring_pairs && p.in_flight;
@@ -1883,7 +1933,7 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
         if (f.sky_kernel && s1 == P.spp)
             if (int rc = launch_sky_tiles(f, p, k); rc) return rc;
         if (c.variant == rt::V_STATS_LDS) sc->dbg_waves = p.stats_waves;
-        if (s1 == P.spp) RT_HIP(hipEventRecord(sc->ev_end[f.ring], p.xst));
+        if (s1 == s_end) RT_HIP(hipEventRecord(sc->ev_end[f.ring], p.xst));
         if (f.pipe()) {
             RT_HIP(hipEventRecord(sc->ev_done[p.wb], p.xst));
             sc->last_ws = static_cast<int>(p.wb);

@@ -3,11 +3,13 @@
 // guided upsample, each with its argument checks, defaults, level driver, stream-ordered *_device
 // entry point and the synchronous host-plane call through the cached context (rt_host_sync.h
 // SyncCall); and the preview session, which runs those stages after a scene's render calls, one
-// frame per call. The kernels are rt_denoise.hip, rt_temporal.hip, rt_upsample.hip and rt_preview.hip.
+// frame per call, and the progressive session, which runs a frame's render in sample windows. The
+// kernels are rt_denoise.hip, rt_temporal.hip, rt_upsample.hip, rt_preview.hip and rt_progressive.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <type_traits>
 
@@ -510,6 +512,13 @@ struct rt_preview {
     // the scene's epochs at the session's last frame (rt_scene_motion)
     uint64_t geometry_epoch = 0, appearance_epoch = 0;
     rt_preview_planes_t last{};    // last.frames: frames since creation or the last reset
+    // rt_preview_refine_device: the progressive session of the view at rest,
+    // allocated on first use, and the refinement in progress (refining: no frame call since its start)
+    rt_progressive *refine = nullptr;
+    bool refining = false;
+    rt_camera refine_camera{};
+    uint64_t refine_seed = 0;
+    uint64_t refine_geometry = 0, refine_appearance = 0;
 };
 
 namespace {
@@ -807,6 +816,7 @@ int rt_preview_frame_device(rt_preview *pv, const rt_camera *camera, uint64_t se
     if (!pv) return fail(RT_ERR_INVALID, "rt_preview_frame_device: null session");
     if (!camera) return fail(RT_ERR_INVALID, "rt_preview_frame_device: camera is null");
     if (!d_rgb && !d_rgb8) return fail(RT_ERR_INVALID, "rt_preview_frame_device: d_rgb and d_rgb8 are both null");
+    pv->refining = false;  // (a refinement restarts after a frame call)
     return preview_frame(*pv, camera, seed, d_rgb, d_rgb8, static_cast<hipStream_t>(stream));
 }
 
@@ -842,6 +852,11 @@ int rt_preview_usage(const rt_preview *pv, uint64_t *bytes)
 {
     if (!pv || !bytes) return fail(RT_ERR_INVALID, "rt_preview_usage: null argument");
     *bytes = pv->bytes;
+    if (pv->refine) {
+        rt_progressive_info_t info{};
+        if (int rc = rt_progressive_info(pv->refine, &info); rc != RT_OK) return rc;
+        *bytes += info.device_bytes;
+    }
     return RT_OK;
 }
 
@@ -849,6 +864,7 @@ void rt_preview_destroy(rt_preview *pv)
 {
     if (!pv) return;
     // (the frames enqueued may still run: hipFree waits for the device)
+    if (pv->refine) (void)rt_progressive_destroy(pv->refine);
     if (pv->arena && hipSetDevice(pv->device) == hipSuccess) (void)hipFree(pv->arena);
     delete pv;
 }
@@ -875,6 +891,358 @@ int rt_preview_merge_device(uint32_t width, uint32_t height, const float *filter
     if (!filtered) return fail(RT_ERR_INVALID, w + "filtered is null");
     if (!d_rgb && !d_rgb8) return fail(RT_ERR_INVALID, w + "d_rgb and d_rgb8 are both null");
     RT_HIP(rt::launch_preview_merge({filtered, albedo, d_rgb, d_rgb8, width, height}, static_cast<hipStream_t>(stream)));
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ---- the progressive session (include/rt_api.h; kernel in rt_progressive.hip) -----
+// The carried planes are one device allocation made by rt_progressive_create: acc, then mom, each
+// n_pixels x 3 floats. ev_tail follows the last step's work (save and load wait for it).
+struct rt_progressive {
+    rt_scene *scene = nullptr;
+    int device = 0;
+    rt_params p{};
+    rt_camera camera{};
+    PixelLayout layout{};
+    uint32_t done = 0;
+    float *acc = nullptr, *mom = nullptr;
+    hipEvent_t ev_tail = nullptr;
+    bool tail_valid = false;
+    uint64_t geometry_epoch = 0, appearance_epoch = 0;
+};
+
+namespace {
+
+// The head of a checkpoint (rt_progressive_save); the planes follow it.
+struct ProgressiveHeader {
+    uint64_t magic;
+    uint32_t version, layout;
+    rt_params params;
+    rt_camera camera;
+    uint64_t n_pixels;
+    uint32_t done, reserved;
+};
+constexpr uint64_t kProgressiveMagic = 0x31474f5250545152ull;  // "RQTPROG1"
+// acc[n_pixels][3] then mom[n_pixels][3] = {L_0, m1, m2}, floats, in the natural enumeration of 8 x 8 tiles
+constexpr uint32_t kProgressiveLayout = 0x33383301u;
+
+uint64_t progressive_plane_bytes(uint64_t n_pixels) { return n_pixels * 3u * sizeof(float); }
+uint64_t progressive_state_bytes(uint64_t n_pixels) { return sizeof(ProgressiveHeader) + 2u * progressive_plane_bytes(n_pixels); }
+
+// The Step rule: m = min(n, spp - done); a window that stops before the frame's end holds whole blocks of 4.
+int progressive_window(const std::string &w, uint32_t spp, uint32_t done, uint32_t n, uint32_t *m)
+{
+    if (spp < 2u) return fail(RT_ERR_INVALID, w + "spp must be at least 2");
+    if (done > spp || (done != spp && (done & 3u))) return fail(RT_ERR_INVALID, w + "done must be a multiple of 4 or spp");
+    const uint32_t left = spp - done;
+    if ((n & 3u) && n < left)
+        return fail(RT_ERR_INVALID, w + "n_samples must be a multiple of 4 before the frame's end (passes start on multiples of 4)");
+    *m = n < left ? n : left;
+    return RT_OK;
+}
+
+// load's check: the blob against the params and camera of a session.
+int progressive_blob_check(const std::string &w, const void *host, uint64_t bytes, const rt_params &P, const rt_camera &cam,
+                           rt_progressive_info_t *info)
+{
+    if (!host) return fail(RT_ERR_INVALID, w + "host is null");
+    if (bytes < sizeof(ProgressiveHeader)) return fail(RT_ERR_CAPACITY, w + "bytes is smaller than a checkpoint's header");
+    ProgressiveHeader h;
+    std::memcpy(&h, host, sizeof h);
+    if (h.magic != kProgressiveMagic) return fail(RT_ERR_INVALID, w + "magic: not a checkpoint of rt_progressive_save");
+    if (h.version != RT_API_VERSION) return fail(RT_ERR_INVALID, w + "version: the checkpoint is of another RT_API_VERSION");
+    if (h.layout != kProgressiveLayout) return fail(RT_ERR_INVALID, w + "layout: the checkpoint's planes are laid out otherwise");
+    const struct { const char *name; uint64_t blob, own; } fields[] = {
+        {"width", h.params.width, P.width}, {"height", h.params.height, P.height}, {"spp", h.params.spp, P.spp},
+        {"max_depth", h.params.max_depth, P.max_depth}, {"seed", h.params.seed, P.seed},
+        {"row_offset", h.params.row_offset, P.row_offset}, {"row_stride", h.params.row_stride, P.row_stride},
+        {"num_rows", h.params.num_rows, P.num_rows}, {"flags", h.params.flags, P.flags}};
+    for (const auto &f : fields)
+        if (f.blob != f.own)
+            return fail(RT_ERR_INVALID, w + "params." + f.name + " of the checkpoint (" + std::to_string(f.blob) +
+                                            ") is not the session's (" + std::to_string(f.own) + ")");
+    if (std::memcmp(&h.camera, &cam, sizeof(rt_camera)) != 0) return fail(RT_ERR_INVALID, w + "camera of the checkpoint is not the session's");
+    const uint64_t n_pixels = pixel_layout(P).n_pixels;
+    if (h.n_pixels != n_pixels) return fail(RT_ERR_INVALID, w + "n_pixels of the checkpoint is not the session's");
+    if (h.done > P.spp || (h.done != P.spp && (h.done & 3u)))
+        return fail(RT_ERR_INVALID, w + "done of the checkpoint is not a multiple of 4 or spp");
+    if (bytes < progressive_state_bytes(n_pixels)) return fail(RT_ERR_CAPACITY, w + "bytes is smaller than the checkpoint (truncated)");
+    if (info)
+        *info = rt_progressive_info_t{static_cast<uint32_t>(sizeof(rt_progressive_info_t)), h.done, P.spp, 0u, n_pixels,
+                                      progressive_state_bytes(n_pixels), 2u * progressive_plane_bytes(n_pixels)};
+    return RT_OK;
+}
+
+// The outputs record of a step, before the session is looked at.
+int check_progressive_outputs(const rt_progressive_outputs *o, const std::string &w)
+{
+    if (!o) return RT_OK;
+    if (o->size != sizeof(rt_progressive_outputs)) return fail(RT_ERR_INVALID, w + "out.size is not sizeof(rt_progressive_outputs)");
+    const struct { const char *name; const void *ptr; } planes[4] = {
+        {"rgb", o->rgb}, {"variance", o->variance}, {"rgb8", o->rgb8}, {"noisy", o->noisy}};
+    bool any = false;
+    for (int i = 0; i < 4; ++i) {
+        any = any || planes[i].ptr;
+        for (int j = 0; j < i; ++j)
+            if (planes[i].ptr && planes[i].ptr == planes[j].ptr)
+                return fail(RT_ERR_INVALID, w + "out." + planes[i].name + " is also out." + planes[j].name);
+    }
+    if (!any) return fail(RT_ERR_INVALID, w + "out: rgb, variance, rgb8 and noisy are all null");
+    if (o->noisy && (!std::isfinite(o->noise_tau) || o->noise_tau < 0.f))
+        return fail(RT_ERR_INVALID, w + "out.noise_tau must be finite and not negative");
+    return RT_OK;
+}
+
+int progressive_epochs(rt_progressive &pg)
+{
+    rt_scene_motion_t sm{};
+    if (int rc = rt_scene_motion(pg.scene, &sm); rc != RT_OK) return rc;
+    pg.geometry_epoch = sm.geometry_epoch, pg.appearance_epoch = sm.appearance_epoch;
+    return RT_OK;
+}
+
+// save and load: the session's enqueued work has finished
+int progressive_wait(rt_progressive &pg)
+{
+    RT_HIP(hipSetDevice(pg.device));
+    if (pg.tail_valid) RT_HIP(hipEventSynchronize(pg.ev_tail));
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_progressive_window(uint32_t spp, uint32_t done, uint32_t n_samples, uint32_t *m)
+{
+    if (!m) return fail(RT_ERR_INVALID, "rt_progressive_window: m is null");
+    return progressive_window("rt_progressive_window: ", spp, done, n_samples, m);
+}
+
+int rt_progressive_create(rt_scene *scene, const rt_camera *camera, const rt_params *params, rt_progressive **out)
+{
+    const std::string w = "rt_progressive_create: ";
+    if (int rc = check_var_params(params, "rt_progressive_create"); rc != RT_OK) return rc;
+    const PixelLayout l = pixel_layout(*params);
+    if (l.n_pixels >= (1ull << 31)) return fail(RT_ERR_INVALID, w + "params: more than 2^31 pixels in one call");
+    if (!l.n_pixels) return fail(RT_ERR_INVALID, w + "params: no rows to render");
+    if (!camera) return fail(RT_ERR_INVALID, w + "camera is null");
+    if (!scene) return fail(RT_ERR_INVALID, w + "scene is null");
+    if (!out) return fail(RT_ERR_INVALID, w + "out is null");
+    rt_progressive *pg = new rt_progressive;
+    pg->scene = scene;
+    pg->device = scene_device(scene);
+    pg->p = *params;
+    pg->camera = *camera;
+    pg->layout = l;
+    void *arena = nullptr;
+    hipError_t e = hipSetDevice(pg->device);
+    if (e == hipSuccess) e = hipMalloc(&arena, 2u * progressive_plane_bytes(l.n_pixels));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&pg->ev_tail, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        if (arena) (void)hipFree(arena);
+        delete pg;
+        return fail(RT_ERR_DEVICE, w + "the session's planes: " + hipGetErrorString(e));
+    }
+    pg->acc = static_cast<float *>(arena);
+    pg->mom = pg->acc + 3u * l.n_pixels;
+    if (int rc = progressive_epochs(*pg); rc != RT_OK) {
+        (void)rt_progressive_destroy(pg);
+        return rc;
+    }
+    *out = pg;
+    return RT_OK;
+}
+
+int rt_progressive_step_device(rt_progressive *pg, uint32_t n_samples, const rt_progressive_outputs *out, void *stream,
+                               uint64_t *d_segments)
+{
+    const std::string w = "rt_progressive_step_device: ";
+    if (int rc = check_progressive_outputs(out, w); rc != RT_OK) return rc;
+    if (!pg) return fail(RT_ERR_INVALID, w + "null session");
+    uint32_t m = 0;
+    if (int rc = progressive_window(w, pg->p.spp, pg->done, n_samples, &m); rc != RT_OK) return rc;
+    if (out && pg->done + m < 2u) return fail(RT_ERR_INVALID, w + "out is given but no sample is done (a resolve needs done >= 2)");
+    rt_scene_motion_t sm{};
+    if (int rc = rt_scene_motion(pg->scene, &sm); rc != RT_OK) return rc;
+    if (sm.geometry_epoch != pg->geometry_epoch || sm.appearance_epoch != pg->appearance_epoch)
+        return fail(RT_ERR_INVALID, w + "the scene was updated since the session's first step (rt_progressive_reset starts the frame again)");
+    if (!m && !out) return RT_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t a = pg->done, b = pg->done + m;
+    const PixelLayout &l = pg->layout;
+    auto resolve = [&]() -> int {
+        if (!out) return RT_OK;
+        if (out->noisy) RT_HIP(hipMemsetAsync(out->noisy, 0, sizeof(uint32_t), st));
+        rt::KResolve k{};
+        k.acc = pg->acc, k.mom = pg->mom;
+        k.out = out->rgb, k.var = out->variance, k.out_u8 = out->rgb8, k.noisy = out->noisy;
+        k.t2 = out->noisy ? out->noise_tau * out->noise_tau : 0.f;
+        k.done = b;
+        k.n_pixels = static_cast<uint32_t>(l.n_pixels);
+        k.W = l.W, k.tiles_x = l.tiles_x, k.tiled_rows = l.tiled_rows, k.tile_lw = l.tile_lw;
+        k.row_offset = l.row_offset, k.row_stride = l.row_stride, k.full_frame = l.full_frame;
+        RT_HIP(rt::launch_progressive_resolve(k, st));
+        return RT_OK;
+    };
+    if (int rc = render_window(pg->scene, &pg->camera, pg->p, a, b, pg->acc, pg->mom, st, d_segments, resolve); rc != RT_OK) {
+        // (a failure part of the way leaves the planes undefined: the frame starts again)
+        if (m) pg->done = 0;
+        return rc;
+    }
+    pg->done = b;
+    RT_HIP(hipEventRecord(pg->ev_tail, st));
+    pg->tail_valid = true;
+    return RT_OK;
+}
+
+int rt_progressive_info(const rt_progressive *pg, rt_progressive_info_t *info)
+{
+    if (!pg) return fail(RT_ERR_INVALID, "rt_progressive_info: null session");
+    if (!info) return fail(RT_ERR_INVALID, "rt_progressive_info: info is null");
+    const uint64_t n = pg->layout.n_pixels;
+    *info = rt_progressive_info_t{static_cast<uint32_t>(sizeof(rt_progressive_info_t)), pg->done, pg->p.spp, 0u, n,
+                                  progressive_state_bytes(n), 2u * progressive_plane_bytes(n)};
+    return RT_OK;
+}
+
+int rt_progressive_reset(rt_progressive *pg, const rt_camera *camera, const uint64_t *seed)
+{
+    if (!pg) return fail(RT_ERR_INVALID, "rt_progressive_reset: null session");
+    if (int rc = progressive_epochs(*pg); rc != RT_OK) return rc;
+    if (camera) pg->camera = *camera;
+    if (seed) pg->p.seed = *seed;
+    pg->done = 0;
+    return RT_OK;
+}
+
+int rt_progressive_save(rt_progressive *pg, void *host, uint64_t cap)
+{
+    const std::string w = "rt_progressive_save: ";
+    if (!pg) return fail(RT_ERR_INVALID, w + "null session");
+    if (!host) return fail(RT_ERR_INVALID, w + "host is null");
+    const uint64_t n = pg->layout.n_pixels, plane = progressive_plane_bytes(n);
+    if (cap < progressive_state_bytes(n)) return fail(RT_ERR_CAPACITY, w + "cap is smaller than state_bytes (rt_progressive_info)");
+    if (int rc = progressive_wait(*pg); rc != RT_OK) return rc;
+    const ProgressiveHeader h{kProgressiveMagic, RT_API_VERSION, kProgressiveLayout, pg->p, pg->camera, n, pg->done, 0u};
+    std::memcpy(host, &h, sizeof h);
+    // (acc and mom are adjacent: one copy)
+    RT_HIP(hipMemcpy(static_cast<char *>(host) + sizeof h, pg->acc, 2u * plane, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_progressive_load(rt_progressive *pg, const void *host, uint64_t bytes)
+{
+    const std::string w = "rt_progressive_load: ";
+    if (!pg) return fail(RT_ERR_INVALID, w + "null session");
+    rt_progressive_info_t info{};
+    if (int rc = progressive_blob_check(w, host, bytes, pg->p, pg->camera, &info); rc != RT_OK) return rc;
+    if (int rc = progressive_wait(*pg); rc != RT_OK) return rc;
+    RT_HIP(hipMemcpy(pg->acc, static_cast<const char *>(host) + sizeof(ProgressiveHeader), info.device_bytes, hipMemcpyHostToDevice));
+    RT_HIP(hipDeviceSynchronize());  // (the planes are in place before a step on any stream)
+    if (int rc = progressive_epochs(*pg); rc != RT_OK) return rc;
+    pg->done = info.done;
+    return RT_OK;
+}
+
+int rt_progressive_blob_check(const void *host, uint64_t bytes, const rt_params *params, const rt_camera *camera,
+                              rt_progressive_info_t *info)
+{
+    const std::string w = "rt_progressive_blob_check: ";
+    if (int rc = check_var_params(params, "rt_progressive_blob_check"); rc != RT_OK) return rc;
+    if (!camera) return fail(RT_ERR_INVALID, w + "camera is null");
+    return progressive_blob_check(w, host, bytes, *params, *camera, info);
+}
+
+int rt_progressive_destroy(rt_progressive *pg)
+{
+    if (!pg) return fail(RT_ERR_INVALID, "rt_progressive_destroy: null session");
+    // (the steps enqueued may still run: hipFree waits for the device)
+    if (hipSetDevice(pg->device) == hipSuccess) {
+        if (pg->acc) (void)hipFree(pg->acc);
+        if (pg->ev_tail) (void)hipEventDestroy(pg->ev_tail);
+    }
+    delete pg;
+    return RT_OK;
+}
+
+// The preview session at rest (include/rt_api.h): the session's own progressive session steps the
+// frame of total_spp samples into beauty / variance; until the frame is complete every call filters
+// the estimate with its carried variance (no temporal stage), then it stores the frame itself.
+int rt_preview_refine_device(rt_preview *pv, const rt_camera *camera, uint64_t seed, uint32_t total_spp, uint32_t n_samples,
+                             float *d_rgb, uint8_t *d_rgb8, void *stream)
+{
+    const std::string w = "rt_preview_refine_device: ";
+    if (!pv) return fail(RT_ERR_INVALID, w + "null session");
+    if (!camera) return fail(RT_ERR_INVALID, w + "camera is null");
+    if (!d_rgb && !d_rgb8) return fail(RT_ERR_INVALID, w + "d_rgb and d_rgb8 are both null");
+    if (total_spp < 2u) return fail(RT_ERR_INVALID, w + "total_spp must be at least 2 (a variance needs two samples)");
+    if (pv->up.size) return fail(RT_ERR_UNSUPPORTED, w + "an upscaled session does not refine (rt_preview_create_upscaled made it)");
+    const rt_preview_params &P = pv->p;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const rt_params rp{P.width, P.height, total_spp, P.max_depth, seed, 0u, 1u, 0u, 0u};
+    rt_scene_motion_t sm{};
+    if (int rc = rt_scene_motion(pv->scene, &sm); rc != RT_OK) return rc;
+    const bool restart = !pv->refining || !pv->refine || pv->refine->p.spp != total_spp || pv->refine_seed != seed ||
+                         std::memcmp(&pv->refine_camera, camera, sizeof(rt_camera)) != 0 ||
+                         sm.geometry_epoch != pv->refine_geometry || sm.appearance_epoch != pv->refine_appearance;
+    // the Step rule before anything is enqueued or started
+    uint32_t m = 0;
+    if (int rc = progressive_window(w, total_spp, restart ? 0u : pv->refine->done, n_samples, &m); rc != RT_OK) return rc;
+    if ((restart ? 0u : pv->refine->done) + m < 2u)
+        return fail(RT_ERR_INVALID, w + "n_samples: the first call of a refinement must render at least 2 samples");
+    const rt_preview::Guides &g = pv->g[pv->cur];
+    if (restart) {
+        if (!pv->refine) {
+            if (int rc = rt_progressive_create(pv->scene, camera, &rp, &pv->refine); rc != RT_OK) return rc;
+        } else {
+            if (int rc = rt_progressive_reset(pv->refine, camera, &seed); rc != RT_OK) return rc;
+            pv->refine->p.spp = total_spp;  // (the planes do not depend on the sample count)
+        }
+        pv->refining = false;
+        pv->last.frames = 0u;  // the next frame call has no history, as after rt_preview_reset
+        // the guides, once per refinement
+        const rt_aov_buffers aov{static_cast<uint32_t>(sizeof(rt_aov_buffers)), total_spp < P.spp ? total_spp : P.spp,
+                                 pv->albedo, g.normal, g.depth, pv->alpha, g.id};
+        if (int rc = rt_render_aov_device(pv->scene, camera, &rp, &aov, st); rc != RT_OK) return rc;
+        pv->refine_camera = *camera, pv->refine_seed = seed;
+        pv->refine_geometry = sm.geometry_epoch, pv->refine_appearance = sm.appearance_epoch;
+    }
+    const rt_progressive_outputs po{static_cast<uint32_t>(sizeof(rt_progressive_outputs)), 0.f, pv->beauty, pv->variance, nullptr,
+                                    nullptr};
+    if (int rc = rt_progressive_step_device(pv->refine, n_samples, &po, st, nullptr); rc != RT_OK) return rc;
+    pv->refining = true;
+    if (pv->refine->done == total_spp) {
+        // the frame itself, unfiltered: the resolve's bits and their texels
+        RT_HIP(rt::launch_preview_merge({pv->beauty, nullptr, d_rgb, d_rgb8, P.width, P.height}, st));
+        return RT_OK;
+    }
+    const bool demod = (P.flags & RT_PREVIEW_DEMODULATE) != 0u;
+    const float *color = pv->beauty, *variance = pv->variance;
+    if (demod) {
+        RT_HIP(rt::launch_preview_split({pv->beauty, pv->variance, pv->albedo, pv->illum, pv->illum_var, P.width, P.height}, st));
+        color = pv->illum, variance = pv->illum_var;
+    }
+    const rt_denoise_buffers db{static_cast<uint32_t>(sizeof(rt_denoise_buffers)), color, pv->albedo, g.normal, g.depth,
+                                pv->filtered, pv->scratch};
+    const rt_denoise_var_buffers vb{static_cast<uint32_t>(sizeof(rt_denoise_var_buffers)), P.var_floor, variance, nullptr,
+                                    pv->var_scratch};
+    // (a FEEDBACK session's levels use the planes a frame's do: the first level's output goes to the
+    // history planes, which the next frame call does not read: it has no history)
+    const bool feedback = (P.flags & RT_PREVIEW_FEEDBACK) != 0u;
+    float *const c1 = feedback ? pv->h[pv->cur].color : nullptr, *const v1 = feedback ? pv->h[pv->cur].variance : nullptr;
+    if (int rc = denoise_var_levels(P.denoise, db, vb, pv->terms, st, c1, v1); rc != RT_OK) return rc;
+    const float *const filtered = feedback && P.denoise.levels == 1u ? c1 : pv->filtered;
+    RT_HIP(rt::launch_preview_merge({filtered, demod ? pv->albedo : nullptr, d_rgb, d_rgb8, P.width, P.height}, st));
+    return RT_OK;
+}
+
+int rt_preview_refine_info(const rt_preview *pv, uint32_t *done, uint32_t *total)
+{
+    if (!pv || !done || !total) return fail(RT_ERR_INVALID, "rt_preview_refine_info: null argument");
+    *done = pv->refining ? pv->refine->done : 0u;
+    *total = pv->refining ? pv->refine->p.spp : 0u;
     return RT_OK;
 }
 

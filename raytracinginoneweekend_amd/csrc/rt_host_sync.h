@@ -53,6 +53,8 @@ hipError_t launch_upsample(const KUpsample &k, hipStream_t stream);
 // rt_preview.hip
 hipError_t launch_preview_split(const KPreviewSplit &k, hipStream_t stream);
 hipError_t launch_preview_merge(const KPreviewMerge &k, hipStream_t stream);
+// rt_progressive.hip
+hipError_t launch_progressive_resolve(const KResolve &k, hipStream_t stream);
 // rt_tiles.hip
 hipError_t launch_classify_tiles(const rttile::KTiles &k, hipStream_t stream);
 hipError_t launch_order_blocks(const uint8_t *cls, uint32_t n_blocks, uint32_t *perm, uint32_t *counts, hipStream_t stream);
@@ -78,6 +80,23 @@ int scene_device(const rt_scene *sc);
 
 // The params of a render call, decided before any HIP call (rt_host.cpp).
 int check_params(const rt_params *p);
+// ... and of a variance render or a progressive session: spp >= 2, the exact kernel only.
+int check_var_params(const rt_params *p, const char *who);
+
+// The rows a call renders and how its pixels are enumerated (the natural enumeration: 64-pixel
+// tiles of 2^tile_lw x 64/2^tile_lw over the tiled rows, then the other rows pixel by pixel), which
+// indexes the running sums and places the outputs (accumulate_pixels, progressive_resolve).
+struct PixelLayout {
+    uint32_t W, num_rows, row_offset, row_stride, full_frame, tile_lw, tiles_x, tiled_rows;
+    uint64_t n_pixels;
+};
+PixelLayout pixel_layout(const rt_params &P);
+
+// Samples [a, b) of the P.spp-sample frame (a a multiple of 4, b one or P.spp; a == b: nothing)
+// folded into acc / mom, [n_pixels][3] floats each, by the passes of a variance render that never
+// reaches its last pass; then `after` on `st`; one call on the scene's stream order (rt_host.cpp).
+int render_window(rt_scene *sc, const rt_camera *camera, const rt_params &P, uint32_t a, uint32_t b, float *acc, float *mom,
+                  hipStream_t st, uint64_t *d_segments, const std::function<int()> &after);
 
 // The scene of a synchronous render: the context keeps its device scene between calls.
 struct SyncScene {

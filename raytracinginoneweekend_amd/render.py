@@ -585,6 +585,20 @@ class Preview:
                                             seed, C.c_void_p(rgb_ptr or 0), C.c_void_p(rgb8_ptr or 0),
                                             C.c_void_p(stream or 0)))
 
+    def refine(self, camera, seed, total_spp, n_samples, rgb_ptr=None, rgb8_ptr=None, stream=None):
+        """rt_preview_refine_device: the view at rest. Enqueue the next n_samples samples of the
+        total_spp-sample frame of (camera, seed) and store the estimate, filtered with its own
+        variance until the frame is complete and exact from then on."""
+        check(lib().rt_preview_refine_device(self.handle, C.byref(_cam_record(camera)) if camera is not None else None,
+                                             seed, total_spp, n_samples, C.c_void_p(rgb_ptr or 0), C.c_void_p(rgb8_ptr or 0),
+                                             C.c_void_p(stream or 0)))
+
+    def refine_info(self):
+        """rt_preview_refine_info: (samples done, total) of the refinement in progress, (0, 0): none."""
+        done, total = C.c_uint32(0), C.c_uint32(0)
+        check(lib().rt_preview_refine_info(self.handle, C.byref(done), C.byref(total)))
+        return done.value, total.value
+
     def reset(self):
         """The next frame has no history."""
         check(lib().rt_preview_reset(self.handle))
@@ -618,6 +632,89 @@ class Preview:
     def close(self):
         if self.handle:
             lib().rt_preview_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def progressive_outputs(rgb_ptr=None, variance_ptr=None, rgb8_ptr=None, noisy_ptr=None, noise_tau=0.0):
+    """An rt_progressive_outputs record from device addresses (None: that plane is not wanted)."""
+    return abi.RtProgressiveOutputs(C.sizeof(abi.RtProgressiveOutputs), noise_tau, rgb_ptr or None, variance_ptr or None,
+                                    rgb8_ptr or None, noisy_ptr or None)
+
+
+def progressive_window(spp, done, n_samples):
+    """rt_progressive_window: the samples a step of n_samples takes after `done` of an spp-sample
+    frame (the Step rule of include/rt_api.h); raises RtError where the step would be refused."""
+    m = C.c_uint32(0)
+    check(lib().rt_progressive_window(spp, done, n_samples, C.byref(m)))
+    return m.value
+
+
+def progressive_blob_check(blob, params, camera):
+    """rt_progressive_blob_check: rt_progressive_load's check of a checkpoint against a params /
+    camera pair, without a session; the blob's info as a dict."""
+    info = abi.RtProgressiveInfo()
+    buf = (C.c_char * len(blob)).from_buffer_copy(blob) if len(blob) else None
+    check(lib().rt_progressive_blob_check(buf, len(blob), C.byref(params) if params is not None else None,
+                                          C.byref(_cam_record(camera)) if camera is not None else None, C.byref(info)))
+    return {n: getattr(info, n) for n in ("done", "spp", "n_pixels", "state_bytes", "device_bytes")}
+
+
+class Progressive:
+    """A progressive session on a DeviceScene (rt_progressive_create): the frame
+    that `params` describes (params.spp is the whole frame's sample count), rendered in sample
+    windows whose sums stay on the device; after the last window the outputs hold the bits of
+    render_var / render for the same arguments. Close it before its scene."""
+
+    def __init__(self, device_scene, camera, params):
+        h = C.c_void_p()
+        sc = device_scene.handle if device_scene is not None else None
+        cam = C.byref(_cam_record(camera)) if camera is not None else None
+        check(lib().rt_progressive_create(sc, cam, C.byref(params) if params is not None else None, C.byref(h)))
+        self.handle = h
+        self.scene = device_scene  # (kept alive as long as the session)
+
+    def step(self, n_samples, rgb_ptr=None, variance_ptr=None, rgb8_ptr=None, noisy_ptr=None, noise_tau=0.0, stream=None,
+             segments=None, outputs=None):
+        """Enqueue the frame's next n_samples samples on `stream`, then (when an output is given)
+        the estimate after them: linear float32 into rgb_ptr, the variance of the mean luminance
+        into variance_ptr, texels into rgb8_ptr, the number of pixels noisier than noise_tau into
+        the device word noisy_ptr (device addresses; `outputs`: a ready record instead)."""
+        if outputs is None and (rgb_ptr or variance_ptr or rgb8_ptr or noisy_ptr):
+            outputs = progressive_outputs(rgb_ptr, variance_ptr, rgb8_ptr, noisy_ptr, noise_tau)
+        check(lib().rt_progressive_step_device(self.handle, n_samples, C.byref(outputs) if outputs is not None else None,
+                                               C.c_void_p(stream or 0), C.c_void_p(segments) if segments else None))
+
+    def info(self):
+        """rt_progressive_info as a dict: done, spp, n_pixels, state_bytes, device_bytes."""
+        r = abi.RtProgressiveInfo()
+        check(lib().rt_progressive_info(self.handle, C.byref(r)))
+        return {n: getattr(r, n) for n in ("done", "spp", "n_pixels", "state_bytes", "device_bytes")}
+
+    def reset(self, camera=None, seed=None):
+        """The frame starts again (done = 0), with another camera and / or seed when given."""
+        check(lib().rt_progressive_reset(self.handle, C.byref(_cam_record(camera)) if camera is not None else None,
+                                         C.byref(C.c_uint64(seed)) if seed is not None else None))
+
+    def save(self):
+        """rt_progressive_save: the session's state as bytes (waits for its enqueued work)."""
+        buf = C.create_string_buffer(self.info()["state_bytes"])
+        check(lib().rt_progressive_save(self.handle, buf, len(buf)))
+        return buf.raw
+
+    def load(self, blob):
+        """rt_progressive_load: continue from a checkpoint of a session with the same arguments."""
+        buf = (C.c_char * len(blob)).from_buffer_copy(blob) if len(blob) else None
+        check(lib().rt_progressive_load(self.handle, buf, len(blob)))
+
+    def close(self):
+        if self.handle:
+            lib().rt_progressive_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -819,6 +916,10 @@ class DeviceScene:
         """A preview session on this scene (Preview; preview_params makes the record, preview_upscale
         the record of an upscaled one)."""
         return Preview(self, params, upscale)
+
+    def progressive(self, camera, params):
+        """A progressive session on this scene (Progressive): the frame of `params` in sample windows."""
+        return Progressive(self, _cam(camera, params), params)
 
     def tile_order(self, camera, params, stream=None):
         """rt_tile_order_device: the pass's dealing order computed by the device's classification
