@@ -1,6 +1,7 @@
 // rt_host_build.cpp — host-only half of the C-ABI (include/rt_api.h): the reference's camera
 // and scene constructors bit for bit, options, the scene blob (always-tested list + clusters)
-// and the walk-shortcut proofs, exact-division checks, the PPM writer. No HIP here, so that the
+// and the walk-shortcut proofs, everything a device scene is derived from (derive_scene),
+// exact-division checks, the PPM writer. No HIP here, so that the
 // CPU sanitizer builds (tests/sanitize/Makefile) compile this file as it ships.
 //
 // Compiled with -ffp-contract=off: the camera basis and the huge-scene generator must round
@@ -881,6 +882,109 @@ size_t plane_layout(Plane *planes, size_t n_planes, size_t n_px)
     return total;
 }
 
+// The rows a call renders: num_rows, or (0) every row_stride-th row from row_offset to the frame's end.
+uint32_t rows_of(const rt_params &p)
+{
+    if (p.num_rows) return p.num_rows;
+    const uint32_t st = p.row_stride ? p.row_stride : 1;
+    return p.row_offset >= p.height ? 0 : (p.height - p.row_offset + st - 1) / st;
+}
+
+// ---- what a scene derives from its records (rt_scene_create_ex and rt_scene_update) -----------
+// The checks of the records, before any HIP call (who: the entry point's name).
+int check_records(const char *who, const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
+                  uint32_t n_materials)
+{
+    const std::string w(who);
+    for (uint32_t i = 0; i < n_spheres; ++i)
+        if (spheres[i].material >= n_materials)
+            return fail(RT_ERR_INVALID, w + ": sphere " + std::to_string(i) + " has material index " +
+                                            std::to_string(spheres[i].material) + " >= " + std::to_string(n_materials));
+    for (uint32_t i = 0; i < n_materials; ++i)
+        if (materials[i].kind > RT_DIELECTRIC)
+            return fail(RT_ERR_INVALID, w + ": material " + std::to_string(i) + " has unknown kind");
+    return RT_OK;
+}
+
+void derive_scene(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, const rt_options &opt,
+                  SceneDerived &d)
+{
+    std::vector<float> hit(static_cast<size_t>(std::max(n_spheres, 1u)) * 12, 0.f);
+    d.table.resize(4 * static_cast<size_t>(n_spheres));
+    d.flat.resize(5 * static_cast<size_t>(n_spheres));
+    for (uint32_t i = 0; i < n_spheres; ++i) {
+        const rt_sphere &sp = spheres[i];
+        const rt_material &mt = materials[sp.material];
+        float *h = hit.data() + 12 * static_cast<size_t>(i);
+        h[0] = sp.center[0]; h[1] = sp.center[1]; h[2] = sp.center[2]; h[3] = sp.radius;
+        h[4] = mt.albedo[0]; h[5] = mt.albedo[1]; h[6] = mt.albedo[2]; h[7] = mt.param;
+        std::memcpy(h + 8, &mt.kind, 4);
+        std::memcpy(d.table.data() + 4 * static_cast<size_t>(i), h, 16);
+        float *f = d.flat.data() + 5 * static_cast<size_t>(i);
+        std::memcpy(f, &mt.kind, 4);
+        std::memcpy(f + 1, h + 4, 16);
+    }
+    d.blobs[0] = build_blob(spheres, n_spheres, false, opt.cluster_size);
+    d.blobs[1] = build_blob(spheres, n_spheres, true, opt.cluster_size);
+    const std::vector<uint32_t> shortcut =
+        shortcut_words(spheres, n_spheres, materials, d.blobs[1], (opt.diag & RT_DIAG_NO_NEIGHBOURS) != 0);
+    // shading records join each blob (so they sit in LDS next to the geometry): per original
+    // sphere index {c, r}, {albedo, param}, then the material kinds as bytes, 16-B padded
+    for (blob_t &b : d.blobs) {
+        b.shade_offset = static_cast<uint32_t>(b.data.size() / 4);
+        for (uint32_t i = 0; i < n_spheres; ++i) b.data.insert(b.data.end(), hit.data() + 12 * static_cast<size_t>(i), hit.data() + 12 * static_cast<size_t>(i) + 8);
+        std::vector<uint8_t> kinds((n_spheres + 15u) / 16u * 16u, 0);
+        for (uint32_t i = 0; i < n_spheres; ++i) kinds[i] = static_cast<uint8_t>(materials[spheres[i].material].kind);
+        const size_t at = b.data.size();
+        b.data.resize(at + kinds.size() / 4);
+        if (!kinds.empty()) std::memcpy(b.data.data() + at, kinds.data(), kinds.size());  // (no sphere: no bytes, null pointers)
+        // dielectric constants per sphere index (raytracer.hxx:166-174 and the Schlick ratio
+        // :47): {1 / ior, (1 - ior) / (1 + ior), (1 - 1/ior) / (1 + 1/ior), shortcut}, the same
+        // binary32 operations the kernel would run (this file is built with -ffp-contract=off);
+        // and the sphere's walk-shortcut word (shortcut_words; as raw bits)
+        for (uint32_t i = 0; i < n_spheres; ++i) {
+            const rt_material &mt = materials[spheres[i].material];
+            float dc[4] = {0.f, 0.f, 0.f, 0.f};
+            if (mt.kind == RT_DIELECTRIC) {
+                const float ior = mt.param, inv = 1.f / ior;
+                dc[0] = inv;
+                dc[1] = (1.f - ior) / (1.f + ior);
+                dc[2] = (1.f - inv) / (1.f + inv);
+                std::memcpy(&dc[3], &shortcut[i], 4);
+            }
+            b.data.insert(b.data.end(), dc, dc + 4);
+        }
+        b.units = static_cast<uint32_t>(b.data.size() / 4);
+    }
+    d.geom = scene_geometry(spheres, d.blobs[1]);
+    d.has_geom = d.blobs[1].n_clusters != 0u;
+    d.ground_ok = d.has_geom && ground_scene_ok(spheres, materials, d.blobs[1], d.geom);
+    d.in_fast_range = true;
+    for (uint32_t i = 0; i < n_spheres; ++i) {
+        for (float v : {spheres[i].center[0], spheres[i].center[1], spheres[i].center[2], spheres[i].radius})
+            if (!(std::fabs(v) <= 0x1p19f)) d.in_fast_range = false;
+        // the hit normal's short division by r (rt_trace.h div3_short) needs |r| >= 2^-40
+        if (!(std::fabs(spheres[i].radius) >= 0x1p-40f)) d.in_fast_range = false;
+    }
+    // the windows, then the empty set; a scene without spheres keeps one empty window
+    d.trap = trap_windows(spheres, n_spheres, materials);
+    const size_t nw = std::max<size_t>(n_spheres, 1u);
+    d.trap.resize(4 * nw);
+    for (size_t i = (opt.diag & RT_DIAG_NO_TRAP_END) ? 0 : nw; i < 2 * nw; ++i) {
+        d.trap[2 * i] = 1.f;
+        d.trap[2 * i + 1] = 0.f;
+    }
+    if (n_spheres == 0) { d.trap[0] = 1.f; d.trap[1] = 0.f; }
+    // the culled scene's geometry as classify_tiles_kernel reads it (rt_tiles.h KTiles::geom)
+    const scene_geom &g = d.geom;
+    d.geom_words.assign(g.root, g.root + 6);
+    d.geom_words.insert(d.geom_words.end(), g.boxes.begin(), g.boxes.end());
+    static_assert(sizeof(rt_sphere) == 5 * sizeof(float), "rt_sphere records follow the boxes as words");
+    const size_t at = d.geom_words.size();
+    d.geom_words.resize(at + 5u * g.always.size());
+    if (!g.always.empty()) std::memcpy(d.geom_words.data() + at, g.always.data(), g.always.size() * sizeof(rt_sphere));
+}
+
 } // namespace rthost
 
 extern "C" {
@@ -923,10 +1027,7 @@ int rt_tile_order(const rt_sphere *spheres, uint32_t n_spheres, const rt_materia
     if (int rc = default_options(opt); rc) return rc;
     const blob_t b = build_blob(spheres, n_spheres, true, opt.cluster_size);
     const scene_geom g = scene_geometry(spheres, b);
-    const uint32_t st = params->row_stride ? params->row_stride : 1u;
-    const uint32_t rows = params->num_rows ? params->num_rows
-                          : params->row_offset >= params->height ? 0u
-                                                                 : (params->height - params->row_offset + st - 1u) / st;
+    const uint32_t st = params->row_stride ? params->row_stride : 1u, rows = rows_of(*params);
     const tile_order t = classify_tiles(*camera, params->width, params->height, params->row_offset, st, rows, 3u, g);
     *n_blocks = static_cast<uint32_t>(t.perm.size());
     *n_lead = t.n_lead;
@@ -951,10 +1052,7 @@ int rt_tile_ground(const rt_sphere *spheres, uint32_t n_spheres, const rt_materi
     const blob_t b = build_blob(spheres, n_spheres, true, opt.cluster_size);
     const scene_geom g = scene_geometry(spheres, b);
     if (!b.n_clusters || !ground_scene_ok(spheres, materials, b, g) || !ground_pass_ok(opt, *params)) return RT_OK;
-    const uint32_t st = params->row_stride ? params->row_stride : 1u;
-    const uint32_t rows = params->num_rows ? params->num_rows
-                          : params->row_offset >= params->height ? 0u
-                                                                 : (params->height - params->row_offset + st - 1u) / st;
+    const uint32_t st = params->row_stride ? params->row_stride : 1u, rows = rows_of(*params);
     const tile_order t = classify_tiles(*camera, params->width, params->height, params->row_offset, st, rows, 3u, g);
     if (t.n_sky) *n_ground = ground_blocks(static_cast<uint32_t>(t.perm.size()), t.n_lead, t.n_sky, params->width, rows, 3u);
     return RT_OK;

@@ -1,6 +1,7 @@
 // rt_host_build.h — the host-only half of the library (rt_host_build.cpp): error reporting,
 // options, the reference's camera and scene constructors, the scene blob and cluster builder,
-// the walk-shortcut proofs, exact-division checks and the PPM writer. No HIP: this half is also
+// the walk-shortcut proofs, what a scene derives from its records (derive_scene), exact-division
+// checks and the PPM writer. No HIP: this half is also
 // built with -fsanitize=address,undefined / thread for the CPU sanitizer runs (tests/sanitize).
 #pragma once
 #include <cstdint>
@@ -29,11 +30,15 @@ int check_options(const rt_options &o);
 int default_options(rt_options &out);
 
 // ---- scene blob: always-tested list + spatial clusters -------------------
-struct blob_t {
-    std::vector<float> data;  // 16-byte units
+// what a blob's readers need beside its data (a device scene keeps this record per blob, rt_scene.h)
+struct blob_meta {
     uint32_t n_geo = 0, n_always = 0, n_clusters = 0, clus_offset = 0, n_clusters_real = 0;
     uint32_t n_supers = 0, supers_offset = 0, shade_offset = 0;
     float clus_pad = 0.f;
+    uint32_t units = 0;  // the data's 16-byte units, shading records included (derive_scene sets it)
+};
+struct blob_t : blob_meta {
+    std::vector<float> data;  // 16-byte units
     std::vector<uint32_t> always;  // sphere indices tested on every segment (not clustered)
 };
 blob_t build_blob(const rt_sphere *s, uint32_t n, bool clustered, uint32_t cluster_max);
@@ -80,6 +85,26 @@ bool ground_scene_ok(const rt_sphere *s, const rt_material *m, const blob_t &b, 
 bool ground_pass_ok(const rt_options &o, const rt_params &p);
 uint32_t ground_blocks(uint32_t n_blocks, uint32_t n_lead, uint32_t n_sky, uint32_t W, uint32_t num_rows, uint32_t tile_lw);
 
+// ---- what a scene derives from its records (rt_scene_create_ex and rt_scene_update) --------
+// The checks of the records, before any HIP call (who: the entry point's name).
+int check_records(const char *who, const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials,
+                  uint32_t n_materials);
+// Everything derived from the records, on the host: the one derivation both entry points install.
+struct SceneDerived {
+    blob_t blobs[2];             // with the shading records, kinds, dielectric constants, shortcut words
+    std::vector<float> trap;     // the windows, then the empty set
+    scene_geom geom;             // the tile classes' geometry, and as classify_tiles_kernel reads it
+    bool has_geom = false;
+    bool ground_ok = false;      // a root box and 1 to 8 always-tested spheres, all lambert
+    std::vector<float> geom_words;
+    bool in_fast_range = true;
+    std::vector<float> table;    // [n][4] {cx, cy, cz, r}
+    std::vector<float> flat;     // [n][5] {kind bits, albedo, param}
+};
+void derive_scene(const rt_sphere *spheres, uint32_t n_spheres, const rt_material *materials, const rt_options &opt,
+                  SceneDerived &d);
+
+uint32_t rows_of(const rt_params &p);  // the rows a call renders (num_rows = 0: to the frame's end)
 rt::UDiv make_udiv(uint32_t d);
 bool exact_by_reciprocal(float b);
 

@@ -1,6 +1,6 @@
 // rt_host_multi.cpp — the multi-GPU context of the C-ABI (rt_multi_*, rt_render_multi_*): per-rank
 // scenes, interleaved row tiles, the gather over RCCL (or its stand-in) and the de-interleave.
-// It reaches scenes through the public scene API only (rt_scene stays rt_host.cpp's own record).
+// It reaches scenes through the public scene API only (rt_scene stays rt_scene.h's record, private to the files around it).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/rt_api.h"
+#include "rt_hip_own.h"
 #include "rt_host_build.h"
 #include "rt_host_sync.h"
 
@@ -170,41 +171,25 @@ struct rt_multi {
     bool rccl = false;  // every rank on its own device: gather over RCCL
     const rccl_api *api = nullptr;  // RCCL, or the stand-in (RT_DIAG_STANDIN_TRANSPORT)
     std::vector<rt_scene *> sc;
-    std::vector<hipStream_t> st;        // rank r > 0: its stream (rank 0 runs on the caller's stream)
     std::vector<ncclComm_t> comm;
-    std::vector<void *> tile;           // f32 tile per rank, on its device
-    std::vector<size_t> tile_bytes;
-    std::vector<void *> tile8;          // u8 tile per rank (RT_OUTPUT_RGB8)
-    std::vector<size_t> tile8_bytes;
-    std::vector<uint64_t *> seg;        // per rank: {segments, sphere tests, box tests}
-    void *gather = nullptr;             // on rank 0's device: N slots of the largest tile
-    size_t gather_bytes = 0;
-    std::vector<hipEvent_t> ev_ready;   // virtual rank r: its tile is complete
-    hipEvent_t ev_copied = nullptr;     // caller stream: virtual ranks' tiles copied out
+    // what a rank owns on its device (rt_multi_destroy lets it go with that device current)
+    struct Rank {
+        Stream st;              // rank r > 0: its stream (rank 0 runs on the caller's stream)
+        DevBuf<float> tile;     // f32 tile
+        DevBuf<uint8_t> tile8;  // u8 tile (RT_OUTPUT_RGB8)
+        DevBuf<uint64_t> seg;   // {segments, sphere tests, box tests}
+        Event ev_ready;         // a virtual rank: its tile is complete
+    };
+    std::vector<Rank> rk;
+    DevBuf<char> gather;  // on rank 0's device: N slots of the largest tile
+    Event ev_copied;      // caller stream: virtual ranks' tiles copied out
     bool copied_valid = false;
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+    Event ev_t0, ev_t1;
 };
 
 namespace {
 
 int multi_fail_destroy(rt_multi *m, int rc);
-
-// ensure() on a given device. Growing reallocates and so synchronises that device; the
-// buffers of a context grow only when a frame is larger than any before it (rt_api.h)
-int grow(int device, void **ptr, size_t *have, size_t want)
-{
-    if (*have >= want && *ptr) return RT_OK;
-    RT_HIP(hipSetDevice(device));
-    if (*ptr) {
-        RT_HIP(hipDeviceSynchronize());
-        RT_HIP(hipFree(*ptr));
-        *ptr = nullptr;
-        *have = 0;
-    }
-    RT_HIP(hipMalloc(ptr, std::max<size_t>(want, 256)));
-    *have = want;
-    return RT_OK;
-}
 
 uint32_t multi_rows(uint32_t H, int n, int r)
 {
@@ -264,13 +249,7 @@ int rt_multi_create_ex(const rt_sphere *spheres, uint32_t n_spheres, const rt_ma
     m->rccl = N > 1 && (distinct || standin);
     m->api = standin ? &standin_api() : &rccl();
     m->sc.assign(N, nullptr);
-    m->st.assign(N, nullptr);
-    m->tile.assign(N, nullptr);
-    m->tile_bytes.assign(N, 0);
-    m->tile8.assign(N, nullptr);
-    m->tile8_bytes.assign(N, 0);
-    m->seg.assign(N, nullptr);
-    m->ev_ready.assign(N, nullptr);
+    m->rk.resize(N);
     int rc = RT_OK;
     auto chk = [&](hipError_t e, const char *what) {
         if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
@@ -280,16 +259,16 @@ int rt_multi_create_ex(const rt_sphere *spheres, uint32_t n_spheres, const rt_ma
         rc = rt_scene_create_ex(spheres, n_spheres, materials, n_materials, m->dev[r], &opt, &m->sc[r]);
         if (rc != RT_OK) break;
         chk(hipSetDevice(m->dev[r]), "hipSetDevice");
-        if (r > 0) chk(hipStreamCreateWithFlags(&m->st[r], hipStreamNonBlocking), "hipStreamCreate");
-        chk(hipMalloc((void **)&m->seg[r], 3 * sizeof(uint64_t)), "hipMalloc");
-        chk(hipMemset(m->seg[r], 0, 3 * sizeof(uint64_t)), "hipMemset");
-        chk(hipEventCreateWithFlags(&m->ev_ready[r], hipEventDisableTiming), "hipEventCreate");
+        if (r > 0) chk(m->rk[r].st.make(hipStreamNonBlocking), "hipStreamCreate");
+        chk(m->rk[r].seg.alloc(3 * sizeof(uint64_t)), "hipMalloc");
+        chk(hipMemset(m->rk[r].seg.get(), 0, 3 * sizeof(uint64_t)), "hipMemset");
+        chk(m->rk[r].ev_ready.make(hipEventDisableTiming), "hipEventCreate");
     }
     if (rc == RT_OK) {
         chk(hipSetDevice(m->dev[0]), "hipSetDevice");
-        chk(hipEventCreateWithFlags(&m->ev_copied, hipEventDisableTiming), "hipEventCreate");
-        chk(hipEventCreate(&m->ev_t0), "hipEventCreate");
-        chk(hipEventCreate(&m->ev_t1), "hipEventCreate");
+        chk(m->ev_copied.make(hipEventDisableTiming), "hipEventCreate");
+        chk(m->ev_t0.make(hipEventDefault), "hipEventCreate");
+        chk(m->ev_t1.make(hipEventDefault), "hipEventCreate");
     }
     if (rc == RT_OK && m->rccl) {
         const rccl_api &api = *m->api;
@@ -315,7 +294,7 @@ int rt_multi_destroy(rt_multi *m)
     if (!m) return RT_OK;
     for (int r = 0; r < m->n; ++r) {
         (void)hipSetDevice(m->dev[r]);
-        if (m->st[r]) (void)hipStreamSynchronize(m->st[r]);
+        if (m->rk[r].st) (void)hipStreamSynchronize(m->rk[r].st.get());
     }
     (void)hipSetDevice(m->dev[0]);
     (void)hipDeviceSynchronize();
@@ -323,18 +302,11 @@ int rt_multi_destroy(rt_multi *m)
         if (c) m->api->comm_destroy(c);
     for (int r = 0; r < m->n; ++r) {
         (void)hipSetDevice(m->dev[r]);
-        if (m->tile[r]) (void)hipFree(m->tile[r]);
-        if (m->tile8[r]) (void)hipFree(m->tile8[r]);
-        if (m->seg[r]) (void)hipFree(m->seg[r]);
-        if (m->ev_ready[r]) (void)hipEventDestroy(m->ev_ready[r]);
-        if (m->st[r]) (void)hipStreamDestroy(m->st[r]);
+        m->rk[r] = rt_multi::Rank{};
         if (m->sc[r]) rt_scene_destroy(m->sc[r]);
     }
     (void)hipSetDevice(m->dev[0]);
-    if (m->gather) (void)hipFree(m->gather);
-    for (hipEvent_t e : {m->ev_copied, m->ev_t0, m->ev_t1})
-        if (e) (void)hipEventDestroy(e);
-    delete m;
+    delete m;  // (the gather buffer and the three events: rank 0's device)
     return RT_OK;
 }
 
@@ -362,14 +334,15 @@ int rt_multi_render_device(rt_multi *m, const rt_camera *camera, const rt_params
     // buffers (grow only: a new, larger frame size costs one synchronisation)
     for (int r = 0; r < N; ++r) {
         const size_t rows = multi_rows(H, N, r);
-        if (int rc = grow(m->dev[r], &m->tile[r], &m->tile_bytes[r], std::max<size_t>(rows, 1) * row_vals * 4u); rc) return rc;
+        RT_HIP(hipSetDevice(m->dev[r]));
+        if (int rc = m->rk[r].tile.ensure(std::max<size_t>(rows, 1) * row_vals * 4u); rc) return rc;
         if (format == RT_OUTPUT_RGB8)
-            if (int rc = grow(m->dev[r], &m->tile8[r], &m->tile8_bytes[r], std::max<size_t>(rows, 1) * row_vals); rc) return rc;
+            if (int rc = m->rk[r].tile8.ensure(std::max<size_t>(rows, 1) * row_vals); rc) return rc;
     }
+    RT_HIP(hipSetDevice(m->dev[0]));
     if (N > 1)
-        if (int rc = grow(m->dev[0], &m->gather, &m->gather_bytes, static_cast<size_t>(N) * rows_max * row_vals * es); rc)
-            return rc;
-    auto tile_of = [&](int r) -> void * { return format == RT_OUTPUT_F32 ? m->tile[r] : m->tile8[r]; };
+        if (int rc = m->gather.ensure(static_cast<size_t>(N) * rows_max * row_vals * es); rc) return rc;
+    auto tile_of = [&](int r) -> void * { return format == RT_OUTPUT_F32 ? static_cast<void *>(m->rk[r].tile.get()) : m->rk[r].tile8.get(); };
     // 1. every rank renders its rows (rank 0 on the caller's stream); virtual ranks wait until
     //    the caller stream has copied their previous tile out
     for (int r = 0; r < N; ++r) {
@@ -380,14 +353,14 @@ int rt_multi_render_device(rt_multi *m, const rt_camera *camera, const rt_params
         p.row_stride = static_cast<uint32_t>(N);
         p.num_rows = rows;
         p.flags &= ~static_cast<uint32_t>(RT_FLAG_FULL_FRAME);
-        hipStream_t rs = r == 0 ? cs : m->st[r];
+        hipStream_t rs = r == 0 ? cs : m->rk[r].st.get();
         RT_HIP(hipSetDevice(m->dev[r]));
-        if (r > 0 && !m->rccl && m->copied_valid) RT_HIP(hipStreamWaitEvent(rs, m->ev_copied, 0));
-        if (int rc = rt_render_device(m->sc[r], camera, &p, static_cast<float *>(m->tile[r]), rs, m->seg[r]); rc) return rc;
+        if (r > 0 && !m->rccl && m->copied_valid) RT_HIP(hipStreamWaitEvent(rs, m->ev_copied.get(), 0));
+        if (int rc = rt_render_device(m->sc[r], camera, &p, m->rk[r].tile.get(), rs, m->rk[r].seg.get()); rc) return rc;
         if (format == RT_OUTPUT_RGB8)
-            RT_HIP(rt::launch_epilogue(static_cast<const float *>(m->tile[r]), static_cast<uint8_t *>(m->tile8[r]),
+            RT_HIP(rt::launch_epilogue(m->rk[r].tile.get(), m->rk[r].tile8.get(),
                                        static_cast<uint64_t>(rows) * row_vals, rs));
-        if (r > 0 && !m->rccl) RT_HIP(hipEventRecord(m->ev_ready[r], rs));
+        if (r > 0 && !m->rccl) RT_HIP(hipEventRecord(m->rk[r].ev_ready.get(), rs));
     }
     // 2. the gather: tile r -> slot r of the gather buffer on rank 0's device
     const size_t slot_bytes = static_cast<size_t>(rows_max) * row_vals * es;
@@ -398,9 +371,9 @@ int rt_multi_render_device(rt_multi *m, const rt_camera *camera, const rt_params
             const size_t cnt = static_cast<size_t>(multi_rows(H, N, r)) * row_vals;
             if (!cnt) continue;
             const ncclDataType_t ty = format == RT_OUTPUT_F32 ? ncclFloat : ncclUint8;
-            nr = api.send(tile_of(r), cnt, ty, 0, m->comm[r], m->st[r]);
+            nr = api.send(tile_of(r), cnt, ty, 0, m->comm[r], m->rk[r].st.get());
             if (nr == ncclSuccess)
-                nr = api.recv(static_cast<char *>(m->gather) + r * slot_bytes, cnt, ty, r, m->comm[0], cs);
+                nr = api.recv(m->gather.get() + r * slot_bytes, cnt, ty, r, m->comm[0], cs);
         }
         const ncclResult_t ne = api.group_end();
         if (nr == ncclSuccess) nr = ne;
@@ -410,11 +383,11 @@ int rt_multi_render_device(rt_multi *m, const rt_camera *camera, const rt_params
         for (int r = 1; r < N; ++r) {
             const size_t bytes = static_cast<size_t>(multi_rows(H, N, r)) * row_vals * es;
             if (!bytes) continue;
-            RT_HIP(hipStreamWaitEvent(cs, m->ev_ready[r], 0));
-            RT_HIP(hipMemcpyAsync(static_cast<char *>(m->gather) + r * slot_bytes, tile_of(r), bytes,
+            RT_HIP(hipStreamWaitEvent(cs, m->rk[r].ev_ready.get(), 0));
+            RT_HIP(hipMemcpyAsync(m->gather.get() + r * slot_bytes, tile_of(r), bytes,
                                   hipMemcpyDeviceToDevice, cs));
         }
-        RT_HIP(hipEventRecord(m->ev_copied, cs));
+        RT_HIP(hipEventRecord(m->ev_copied.get(), cs));
         m->copied_valid = true;
     }
     // 3. de-interleave on rank 0's device: frame row r + i N <- tile r row i
@@ -423,7 +396,7 @@ int rt_multi_render_device(rt_multi *m, const rt_camera *camera, const rt_params
     for (int r = 0; r < N; ++r) {
         const uint32_t rows = multi_rows(H, N, r);
         if (!rows) continue;
-        const void *src = r == 0 ? tile_of(0) : static_cast<const void *>(static_cast<char *>(m->gather) + r * slot_bytes);
+        const void *src = r == 0 ? tile_of(0) : static_cast<const void *>(m->gather.get() + r * slot_bytes);
         RT_HIP(hipMemcpy2DAsync(static_cast<char *>(d_out) + r * row_bytes, row_bytes * N, src, row_bytes, row_bytes,
                                 rows, hipMemcpyDeviceToDevice, cs));
     }
@@ -454,26 +427,27 @@ int multi_render_host(rt_multi *m, const rt_camera *camera, const rt_params *par
     const size_t bytes = static_cast<size_t>(params->width) * params->height * 3u * es;
     for (int r = 0; r < m->n; ++r) {
         RT_HIP(hipSetDevice(m->dev[r]));
-        RT_HIP(hipMemset(m->seg[r], 0, 3 * sizeof(uint64_t)));
+        RT_HIP(hipMemset(m->rk[r].seg.get(), 0, 3 * sizeof(uint64_t)));
     }
     RT_HIP(hipSetDevice(m->dev[0]));
-    void *d_out = nullptr;
-    hipStream_t cs = nullptr;
-    RT_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    DevBuf<char> d_out;
+    Stream own_cs;
+    RT_HIP(own_cs.make(hipStreamNonBlocking));
+    const hipStream_t cs = own_cs.get();
     int rc = RT_OK;
     auto chk = [&](hipError_t e, const char *what) {
         if (e != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
         return rc == RT_OK;
     };
-    chk(hipMalloc(&d_out, bytes), "hipMalloc");
-    if (rc == RT_OK) chk(hipEventRecord(m->ev_t0, cs), "hipEventRecord");
-    if (rc == RT_OK) rc = rt_multi_render_device(m, camera, params, format, d_out, cs);
+    chk(d_out.alloc(bytes), "hipMalloc");
+    if (rc == RT_OK) chk(hipEventRecord(m->ev_t0.get(), cs), "hipEventRecord");
+    if (rc == RT_OK) rc = rt_multi_render_device(m, camera, params, format, d_out.get(), cs);
     (void)hipSetDevice(m->dev[0]);
-    if (rc == RT_OK) chk(hipEventRecord(m->ev_t1, cs), "hipEventRecord");
-    if (rc == RT_OK) chk(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
+    if (rc == RT_OK) chk(hipEventRecord(m->ev_t1.get(), cs), "hipEventRecord");
+    if (rc == RT_OK) chk(hipMemcpyAsync(out, d_out.get(), bytes, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
     for (int r = 0; r < m->n; ++r) {
         (void)hipSetDevice(m->dev[r]);
-        if (m->st[r]) chk(hipStreamSynchronize(m->st[r]), "hipStreamSynchronize");
+        if (m->rk[r].st) chk(hipStreamSynchronize(m->rk[r].st.get()), "hipStreamSynchronize");
     }
     (void)hipSetDevice(m->dev[0]);
     chk(hipStreamSynchronize(cs), "hipStreamSynchronize");
@@ -481,14 +455,12 @@ int multi_render_host(rt_multi *m, const rt_camera *camera, const rt_params *par
     for (int r = 0; r < m->n && rc == RT_OK; ++r) {
         uint64_t v[3];
         (void)hipSetDevice(m->dev[r]);
-        chk(hipMemcpy(v, m->seg[r], sizeof v, hipMemcpyDeviceToHost), "hipMemcpy");
+        chk(hipMemcpy(v, m->rk[r].seg.get(), sizeof v, hipMemcpyDeviceToHost), "hipMemcpy");
         for (int i = 0; i < 3; ++i) segs[i] += v[i];
     }
     (void)hipSetDevice(m->dev[0]);
     float ms = 0.f;
-    if (rc == RT_OK) chk(hipEventElapsedTime(&ms, m->ev_t0, m->ev_t1), "hipEventElapsedTime");
-    if (d_out) (void)hipFree(d_out);
-    (void)hipStreamDestroy(cs);
+    if (rc == RT_OK) chk(hipEventElapsedTime(&ms, m->ev_t0.get(), m->ev_t1.get()), "hipEventElapsedTime");
     if (rc == RT_OK && stats) {
         stats->primaries = static_cast<uint64_t>(params->width) * params->height * params->spp;
         stats->segments = segs[0];

@@ -15,6 +15,7 @@
 
 #include "../../include/rt_api.h"
 #include "rt_device.h"
+#include "rt_hip_own.h"
 #include "rt_host_build.h"
 #include "rt_host_sync.h"
 
@@ -486,7 +487,7 @@ struct rt_preview {
     int device = 0;
     rt_preview_params p{};
     uint32_t terms = 0;            // the filter's edge terms (check_denoise)
-    void *arena = nullptr;
+    DevBuf<char> arena;
     uint64_t bytes = 0;
     // the frame's render, its guides that no later frame reads, and what DEMODULATE makes of it
     float *beauty = nullptr, *variance = nullptr, *albedo = nullptr, *alpha = nullptr;
@@ -739,12 +740,12 @@ int preview_create(rt_scene *scene, const rt_preview_params *p, const rt_preview
     pv->last.size = static_cast<uint32_t>(sizeof(rt_preview_planes_t));
     pv->bytes = preview_carve(*pv, nullptr);
     hipError_t e = hipSetDevice(pv->device);
-    if (e == hipSuccess) e = hipMalloc(&pv->arena, pv->bytes);
+    if (e == hipSuccess) e = pv->arena.alloc(pv->bytes);
     if (e != hipSuccess) {
         delete pv;
         return fail(RT_ERR_DEVICE, std::string(who) + ": the session's planes: " + hipGetErrorString(e));
     }
-    preview_carve(*pv, static_cast<char *>(pv->arena));
+    preview_carve(*pv, pv->arena.get());
     *out = pv;
     return RT_OK;
 }
@@ -865,7 +866,7 @@ void rt_preview_destroy(rt_preview *pv)
     if (!pv) return;
     // (the frames enqueued may still run: hipFree waits for the device)
     if (pv->refine) (void)rt_progressive_destroy(pv->refine);
-    if (pv->arena && hipSetDevice(pv->device) == hipSuccess) (void)hipFree(pv->arena);
+    (void)hipSetDevice(pv->device);
     delete pv;
 }
 
@@ -906,8 +907,9 @@ struct rt_progressive {
     rt_camera camera{};
     PixelLayout layout{};
     uint32_t done = 0;
+    DevBuf<float> planes;
     float *acc = nullptr, *mom = nullptr;
-    hipEvent_t ev_tail = nullptr;
+    Event ev_tail;
     bool tail_valid = false;
     uint64_t geometry_epoch = 0, appearance_epoch = 0;
 };
@@ -1006,7 +1008,7 @@ int progressive_epochs(rt_progressive &pg)
 int progressive_wait(rt_progressive &pg)
 {
     RT_HIP(hipSetDevice(pg.device));
-    if (pg.tail_valid) RT_HIP(hipEventSynchronize(pg.ev_tail));
+    if (pg.tail_valid) RT_HIP(hipEventSynchronize(pg.ev_tail.get()));
     return RT_OK;
 }
 
@@ -1036,16 +1038,14 @@ int rt_progressive_create(rt_scene *scene, const rt_camera *camera, const rt_par
     pg->p = *params;
     pg->camera = *camera;
     pg->layout = l;
-    void *arena = nullptr;
     hipError_t e = hipSetDevice(pg->device);
-    if (e == hipSuccess) e = hipMalloc(&arena, 2u * progressive_plane_bytes(l.n_pixels));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&pg->ev_tail, hipEventDisableTiming);
+    if (e == hipSuccess) e = pg->planes.alloc(2u * progressive_plane_bytes(l.n_pixels));
+    if (e == hipSuccess) e = pg->ev_tail.make(hipEventDisableTiming);
     if (e != hipSuccess) {
-        if (arena) (void)hipFree(arena);
         delete pg;
         return fail(RT_ERR_DEVICE, w + "the session's planes: " + hipGetErrorString(e));
     }
-    pg->acc = static_cast<float *>(arena);
+    pg->acc = pg->planes.get();
     pg->mom = pg->acc + 3u * l.n_pixels;
     if (int rc = progressive_epochs(*pg); rc != RT_OK) {
         (void)rt_progressive_destroy(pg);
@@ -1092,7 +1092,7 @@ int rt_progressive_step_device(rt_progressive *pg, uint32_t n_samples, const rt_
         return rc;
     }
     pg->done = b;
-    RT_HIP(hipEventRecord(pg->ev_tail, st));
+    RT_HIP(hipEventRecord(pg->ev_tail.get(), st));
     pg->tail_valid = true;
     return RT_OK;
 }
@@ -1159,10 +1159,7 @@ int rt_progressive_destroy(rt_progressive *pg)
 {
     if (!pg) return fail(RT_ERR_INVALID, "rt_progressive_destroy: null session");
     // (the steps enqueued may still run: hipFree waits for the device)
-    if (hipSetDevice(pg->device) == hipSuccess) {
-        if (pg->acc) (void)hipFree(pg->acc);
-        if (pg->ev_tail) (void)hipEventDestroy(pg->ev_tail);
-    }
+    (void)hipSetDevice(pg->device);
     delete pg;
     return RT_OK;
 }

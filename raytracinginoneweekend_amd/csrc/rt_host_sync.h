@@ -1,8 +1,9 @@
-// rt_host_sync.h — what the device half's three files share (rt_host.cpp: scenes, renders, the
-// cached context; rt_host_post.cpp: the filters and temporal accumulation; rt_host_multi.cpp: the
-// multi-GPU context): the kernels' launchers, the HIP error forms, the params check, and the one
-// path every synchronous host-buffer entry point takes through the cached per-device context
-// (SyncCall, implemented in rt_host.cpp).
+// rt_host_sync.h — what the device half's files share (the four around the scene record, rt_scene.h:
+// rt_host_scene.cpp, rt_host_order.cpp, rt_host.cpp, rt_host_synccall.cpp; rt_host_post.cpp: the
+// filters, temporal accumulation and sessions; rt_host_multi.cpp: the multi-GPU context): the
+// kernels' launchers, the HIP error forms, the params checks, a scene's device and sample windows
+// for those that do not see the record, and the one path every synchronous host-buffer entry point
+// takes through the cached per-device context (SyncCall, implemented in rt_host_synccall.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,7 +76,8 @@ inline int hip_rc(hipError_t e, const char *what)
     return e == hipSuccess ? RT_OK : fail(RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-// The device a scene was created on (rt_scene is rt_host.cpp's own record).
+// The device a scene was created on (rt_scene is rt_scene.h's record, which rt_host_post.cpp and
+// rt_host_multi.cpp do not include; rt_host_scene.cpp).
 int scene_device(const rt_scene *sc);
 
 // The params of a render call, decided before any HIP call (rt_host.cpp).

@@ -136,7 +136,7 @@ __device__ __forceinline__ float canonical_pm1(uint64_t &st, uint64_t inc)
 }
 // RN(a / b) for a per-render divisor b (the image width or height): one reciprocal rb = RN(1/b)
 // and one FMA correction (Markstein) when the host has checked, for this b, that the sequence
-// reproduces the IEEE quotient for every float mantissa (rt_host.cpp exact_by_reciprocal: the
+// reproduces the IEEE quotient for every float mantissa (rt_host_build.cpp exact_by_reciprocal: the
 // result then holds for every normal a >= 0, the scaling by powers of two being exact);
 // otherwise the IEEE division.
 __device__ __forceinline__ float div_const(float a, float b, float rb, bool fast)
@@ -732,7 +732,7 @@ __device__ __forceinline__ uint64_t sphere_key(bool want, float4 s, uint32_t id,
 // last hit was a dielectric sphere, whose geo entry, original index (hid; kShortcut: the sphere
 // has a shortcut word) and shortcut word (nbw) wait in the lane's LDS slots.
 //
-// The shortcut (rt_host.cpp shortcut_words; KParams::iso): when the segment (0, 1.002 t] up to
+// The shortcut (rt_host_build.cpp shortcut_words; KParams::iso): when the segment (0, 1.002 t] up to
 // the sphere's own candidate t lies in the ball |p - C|^2 <= fl(r r) kIsoR2Grow (both ends
 // checked; the ball is convex), the host has shown that it misses the padded box of every
 // clustered sphere but the sphere's at most two neighbours (none: "isolated"), whose slots nbw

@@ -6,7 +6,8 @@
 //
 //   host_check host <golden dir>        scene generators vs the reference's scene dumps, camera
 //                                       vs the restatement, cluster/neighbour-list builder on the
-//                                       huge scene and adversarial scenes, exact-division checks,
+//                                       huge scene and adversarial scenes, the scene derivation bit
+//                                       for bit (derive_scene), exact-division checks,
 //                                       the synchronous calls' plane layout, the pass planner's cuts,
 //                                       options parser (fixed and random strings), PPM writer
 //   host_check render <scene.bin> <golden.f32> W H spp depth seed row0 stride rows mode threads
@@ -176,6 +177,92 @@ void check_builders(const std::string &golden)
         check_blob(t, mm, true, 4);
         check_blob(t, mm, false, 16);
     }
+}
+
+// 64-bit FNV-1a over the bytes of an array
+template <class T> uint64_t fnv1a(const std::vector<T> &v)
+{
+    uint64_t h = 14695981039346656037ull;
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(v.data());
+    for (size_t i = 0; i < v.size() * sizeof(T); ++i) h = (h ^ p[i]) * 1099511628211ull;
+    return h;
+}
+
+struct DeriveCase {
+    std::vector<rt_sphere> s;
+    std::vector<rt_material> m;
+};
+
+// the huge scene, the simple scene, an adversarial scene (a negative radius, a centre beyond 2^19,
+// a radius below 2^-40, glass of several indices of refraction, touching and nested balls) and
+// the scene without spheres
+std::vector<DeriveCase> derive_cases(const std::string &golden)
+{
+    std::vector<DeriveCase> c(4);
+    CHECK(load_scene(golden + "/scene_huge_1234.bin", c[0].s, c[0].m));
+    c[1].s.resize(1024);
+    c[1].m.resize(1024);
+    uint32_t ns = 0, nm = 0;
+    CHECK(rt_scene_simple(c[1].s.data(), 1024, &ns, c[1].m.data(), 1024, &nm) == RT_OK);
+    c[1].s.resize(ns);
+    c[1].m.resize(nm);
+    c[2].m = {{RT_LAMBERT, {.5f, .5f, .5f}, 0.f},   {RT_DIELECTRIC, {1, 1, 1}, 1.5f}, {RT_METAL, {.7f, .6f, .5f}, .2f},
+              {RT_DIELECTRIC, {1, 1, 1}, 1.33f},    {RT_DIELECTRIC, {1, 1, 1}, 2.4f}, {RT_DIELECTRIC, {1, 1, 1}, 1.f},
+              {RT_DIELECTRIC, {1, 1, 1}, 0.75f}};
+    c[2].s = {{{0.f, -1000.f, 0.f}, 1000.f, 0u}, {{0.f, 1.f, 0.f}, 1.f, 1u},      {{0.f, 1.f, 0.f}, -.9f, 1u},
+              {{4.f, 1.f, 0.f}, 1.f, 2u},        {{-4.f, 1.f, 0.f}, 1.f, 3u},     {{600000.f, 1.f, 2.f}, .5f, 4u},
+              {{2.f, .2f, 2.f}, 0x1p-41f, 5u},   {{-2.f, .2f, 2.f}, .2f, 6u},     {{-2.f, .2f, 2.4f}, .2f, 4u},
+              {{1.f, .2f, -3.f}, .2f, 0u},       {{1.5f, .2f, -3.f}, .2f, 3u},    {{7.f, .3f, 7.f}, .3f, 1u}};
+    std::mt19937 rng(11);
+    std::uniform_real_distribution<float> U(-11.f, 11.f);
+    for (uint32_t i = 0; i < 60; ++i) c[2].s.push_back({{U(rng), .2f, U(rng)}, .2f, i % 7u});
+    c[3].m = {{RT_LAMBERT, {.5f, .5f, .5f}, 0.f}};
+    return c;
+}
+
+// What a scene derives from its records (rthost::derive_scene), bit for bit: every derived array's
+// hash and the three flags, per scene under the default options and under RT_DIAG_NO_TRAP_END |
+// RT_DIAG_NO_NEIGHBOURS. The constants are those of derive_scene as it stood in rt_host.cpp at
+// 152caca, before it moved to rt_host_build.cpp (profiles/hostsplit/derive_words.txt says how they
+// were obtained): the device scenes, and so the golden frames, depend on these bits.
+void check_derive(const std::string &golden)
+{
+    static const struct {
+        uint64_t blob0, blob1, trap, geom_words, table, flat;
+        bool in_fast_range, has_geom, ground_ok;
+    } want[8] = {
+        {0x4f54fa9e42869b78ull, 0xf6dbc24cb6371f5dull, 0x5a2f61fcb595ff19ull, 0x529f39df29530df0ull, 0x93a14d825fcc0e29ull, 0x1c6ef68951427301ull, 1, 1, 1},
+        {0xef307f7c23635578ull, 0x2d4351f3ed79d18dull, 0x0d04cfbaaec761e5ull, 0x529f39df29530df0ull, 0x93a14d825fcc0e29ull, 0x1c6ef68951427301ull, 1, 1, 1},
+        {0xcc4faec9cd58d405ull, 0xcc4faec9cd58d405ull, 0x97cf91e389d7ac45ull, 0xc51bf4eb83b97b3bull, 0x182bf30f88f5454cull, 0xba20e3a2ac7d5aafull, 1, 0, 0},
+        {0xcc4faec9cd58d405ull, 0xcc4faec9cd58d405ull, 0x97cf91e389d7ac45ull, 0xc51bf4eb83b97b3bull, 0x182bf30f88f5454cull, 0xba20e3a2ac7d5aafull, 1, 0, 0},
+        {0xbedbbcca4f38924cull, 0xabce91f71a5ceb15ull, 0x7b0bc7bfbb4e4ed6ull, 0x59c8f52c39ff7f86ull, 0x53b1d16a6260063aull, 0x4d8d746c3a842f12ull, 0, 1, 1},
+        {0xbedbbcca4f38924cull, 0xabce91f71a5ceb15ull, 0x5a640bd8e7221825ull, 0x59c8f52c39ff7f86ull, 0x53b1d16a6260063aull, 0x4d8d746c3a842f12ull, 0, 1, 1},
+        {0x24a95cb574ab082bull, 0x24a95cb574ab082bull, 0x6af9b6af0b2793c5ull, 0x09f6eaf179126bd8ull, 0xcbf29ce484222325ull, 0xcbf29ce484222325ull, 1, 0, 0},
+        {0x24a95cb574ab082bull, 0x24a95cb574ab082bull, 0x6af9b6af0b2793c5ull, 0x09f6eaf179126bd8ull, 0xcbf29ce484222325ull, 0xcbf29ce484222325ull, 1, 0, 0},
+    };
+    const std::vector<DeriveCase> cases = derive_cases(golden);
+    for (size_t i = 0; i < cases.size(); ++i)
+        for (uint32_t v = 0; v < 2u; ++v) {
+            rt_options o = rthost::library_defaults();
+            o.diag = v ? uint32_t(RT_DIAG_NO_TRAP_END | RT_DIAG_NO_NEIGHBOURS) : 0u;
+            const DeriveCase &c = cases[i];
+            const uint32_t n = static_cast<uint32_t>(c.s.size());
+            CHECK(rthost::check_records("host_check", c.s.data(), n, c.m.data(), static_cast<uint32_t>(c.m.size())) == RT_OK);
+            rthost::SceneDerived d;
+            rthost::derive_scene(c.s.data(), n, c.m.data(), o, d);
+            const auto &w = want[2 * i + v];
+            CHECK(fnv1a(d.blobs[0].data) == w.blob0 && fnv1a(d.blobs[1].data) == w.blob1);
+            CHECK(fnv1a(d.trap) == w.trap && fnv1a(d.geom_words) == w.geom_words);
+            CHECK(fnv1a(d.table) == w.table && fnv1a(d.flat) == w.flat);
+            CHECK(d.in_fast_range == w.in_fast_range && d.has_geom == w.has_geom && d.ground_ok == w.ground_ok);
+            for (const rthost::blob_t &b : d.blobs) CHECK(b.units == b.data.size() / 4u && b.shade_offset <= b.units);
+            CHECK(d.table.size() == 4u * n && d.flat.size() == 5u * n && d.trap.size() == 4u * std::max(n, 1u));
+        }
+    // the records' checks refuse a material index past the table and an unknown kind
+    const rt_sphere s1 = {{0.f, 0.f, 0.f}, 1.f, 1u};
+    const rt_material m1 = {RT_LAMBERT, {.5f, .5f, .5f}, 0.f}, m2 = {RT_DIELECTRIC + 1u, {1, 1, 1}, 1.f};
+    CHECK(rthost::check_records("host_check", &s1, 1, &m1, 1) == RT_ERR_INVALID);
+    CHECK(rthost::check_records("host_check", nullptr, 0, &m2, 1) == RT_ERR_INVALID);
 }
 
 // tile classes: the frame-sized classification runs on several threads (each
@@ -564,6 +651,7 @@ int main(int argc, char **argv)
         check_scene_generators(golden);
         check_cameras();
         check_builders(golden);
+        check_derive(golden);
         check_tiles(golden);
         check_divisions();
         check_plane_layout();

@@ -211,8 +211,9 @@ def test_constants_the_edge_cases_straddle():
     129, 256, 257 the half and the whole of rt_scene::kRing."""
     src = os.path.join(os.path.dirname(os.path.abspath(rt.__file__)), "csrc")
     host = open(os.path.join(src, "rt_host.cpp")).read()
+    scene = open(os.path.join(src, "rt_scene.h")).read()
     ground = open(os.path.join(src, "rt_ground.hip")).read()
     assert re.search(r"#\s*define\s+RT_GROUND_SPT\s+32u?\b", host)
-    assert re.search(r"\bkRing\s*=\s*256u?\b", host)
+    assert re.search(r"\bkRing\s*=\s*256u?\b", scene)
     assert re.search(r"\bkGroundAlways\s*=\s*8u?\b", ground)
     assert re.search(r"#\s*define\s+RT_GROUND_RING\s+8u?\b", ground)
