@@ -1110,6 +1110,116 @@ int rt_preview_refine_device(rt_preview *pv, const rt_camera *camera, uint64_t s
                              float *d_rgb, uint8_t *d_rgb8, void *stream);
 int rt_preview_refine_info(const rt_preview *pv, uint32_t *done, uint32_t *total);
 
+/* ---- the adaptive session: a progressive session that retires converged tiles -----
+ * A session of its own type beside rt_progressive_* (whose contract above is unchanged). It fixes a
+ * scene, a camera, an rt_params record P and an rt_adaptive_params record. P.spp = N >= 2 is the cap of
+ * every pixel's sample count; P's row fields, RT_FLAG_FULL_FRAME and flags are taken or refused exactly
+ * as rt_progressive_create does. noise_tau is finite and >= 0, max_noisy is in 0..63, min_samples is a
+ * multiple of 4 and >= 4.
+ *   Blocks   the 64-pixel blocks of P's natural enumeration: the 8 x 8 tiles over the tiled rows in
+ *            row-major tile order, then row-major runs of 64 pixels over the leftover rows. B of them;
+ *            n_pixels % 64 != 0 is RT_ERR_UNSUPPORTED at creation.
+ *   State    the two planes of a progressive session, acc and mom (24 B per pixel); per block one
+ *            uint32 d_b, the samples folded into it (0 at start), and one flag word; the frontier
+ *            `done`; the active set A (every block at start); two permutation buffers of B words; four
+ *            count words on the device and in pinned host memory.
+ *   Step(n)  1 Render. A empty or done == N: nothing is rendered. Otherwise m is the progressive Step
+ *              rule's (rt_progressive_window(N, done, n)), and samples [done, done + m) of the N-sample
+ *              frame are rendered FOR THE PIXELS OF THE BLOCKS IN A ONLY (the keys (pixel) * N + s, the
+ *              streams and the sample numbers are the frame's) and folded into the planes by the
+ *              accumulation of rt_render_var_device in the frame's own addition order, as a progressive
+ *              step does. Then done += m and d_b = done for every b in A: every active block has the
+ *              same d_b, which is what makes one window serve them all.
+ *            2 Resolve (whenever done >= 2, also without `out`). For every pixel the progressive
+ *              session's Resolve with d = d_b of its block. The outputs that are given are written for
+ *              the whole frame: rgb, variance, rgb8 and `samples`, a uint32 plane laid out like variance
+ *              that holds d_b. A retired block's pixels are written again, with the same bits, at
+ *              every step.
+ *            3 Retire. t2 = noise_tau * noise_tau formed once on the host in binary32; a pixel is noisy
+ *              iff var > t2 * (L * L), the progressive session's expression; c_b = the noisy pixels of
+ *              block b. A block b of A leaves A when d_b >= min_samples and c_b <= max_noisy. A never
+ *              grows. out->noisy (optional; the step zeroes the word first) receives the sum of c_b over
+ *              ALL blocks, each at its own d_b.
+ *            4 Compact. The next step's dealing order is the frame's dealing order restricted to A,
+ *              relative order kept: the frame's order is the one its progressive window would take for
+ *              this camera and rows (lead tiles, others, proven-sky tiles), and the identity with every
+ *              block in the middle class where the scene or the flags have no tile classes
+ *              (RT_FLAG_BRUTE_FORCE, a scene without clusters). The three class counts are counted
+ *              again; {|A|, lead, others, sky} go to the pinned words and an event is recorded.
+ * The host wait: the host sizes a step's launches from these counts, so before a step plans its passes
+ * it waits for the previous step's event, and for nothing else: one short event wait per step (like a
+ * first render under rt_options.tile_classes = 1). rt_adaptive_info makes the same wait.
+ * The session is finished when done == N or A is empty; further steps render nothing and resolve
+ * again. With min_samples >= N nothing retires before the end: every step's outputs are then the
+ * progressive session's bits, and after the last window rt_render_var_device's, hence rt_render_device's
+ * (this follows from the rules; it is not a mode). A pixel that stopped after d samples holds the
+ * d-sample prefix of the N-sample frame's own sample set.
+ * A step is planned like a progressive step over 64 |A| pixel positions (single-sample slots, no sky
+ * and no ground kernel); the cut into passes never changes the bits. Several adaptive and progressive
+ * sessions on one scene, and plain renders between their steps, do not disturb each other. After
+ * rt_scene_update moved either epoch a step is RT_ERR_INVALID with nothing enqueued, until
+ * rt_adaptive_reset. rt_scene_usage does not count a session: rt_adaptive_info reports its bytes.
+ * Not provided: checkpoints of an adaptive session, re-activating a retired block, masks inside a block. */
+typedef struct rt_adaptive rt_adaptive;
+typedef struct rt_adaptive_params {
+    uint32_t size;        /* sizeof(rt_adaptive_params)                                               */
+    float noise_tau;      /* finite, >= 0: a pixel is noisy iff var > tau^2 L^2                       */
+    uint32_t max_noisy;   /* 0..63: a block retires with at most this many noisy pixels               */
+    uint32_t min_samples; /* a multiple of 4, >= 4: no block retires with fewer samples               */
+} rt_adaptive_params;
+typedef struct rt_adaptive_outputs {
+    uint32_t size;       /* sizeof(rt_adaptive_outputs)                                               */
+    uint32_t reserved;   /* 0                                                                         */
+    float *rgb;          /* optional: linear f32, as rt_render_device lays it out                     */
+    float *variance;     /* optional: one float per pixel, as rt_render_var_device lays it out        */
+    uint8_t *rgb8;       /* optional: gamma 1/2.2 texels, 3 bytes per pixel, laid out as rgb          */
+    uint32_t *samples;   /* optional: d_b of the pixel's block, one word per pixel, laid out as variance */
+    uint32_t *noisy;     /* optional: one device word, zeroed by the step, the sum of c_b added       */
+} rt_adaptive_outputs;
+typedef struct rt_adaptive_info_t {
+    uint32_t size;             /* filled by the call                                                  */
+    uint32_t done, spp;        /* the frontier, and N                                                 */
+    uint32_t n_blocks;         /* B                                                                   */
+    uint32_t active_blocks;    /* |A| after the last step                                             */
+    uint32_t finished;         /* 1: done == N or A is empty                                          */
+    uint64_t n_pixels;         /* pixels of the frame the session covers: 64 B                        */
+    uint64_t samples_rendered; /* 64 x the sum of d_b                                                 */
+    uint64_t device_bytes;     /* the session's device allocation: 24 B per pixel, 16 B per block, the counts */
+} rt_adaptive_info_t;
+/* Every argument is checked before any HIP call and RT_ERR_INVALID names the field: the adaptive
+ * record first (null, size, noise_tau, max_noisy, min_samples), then params as rt_progressive_create
+ * (RT_ERR_INVALID / RT_ERR_UNSUPPORTED), n_pixels % 64 (RT_ERR_UNSUPPORTED), camera, scene and out;
+ * then the planes, the block words and both permutation buffers are allocated on the scene's device. */
+int rt_adaptive_create(rt_scene *scene, const rt_camera *camera, const rt_params *params, const rt_adaptive_params *adaptive,
+                       rt_adaptive **out);
+/* Step(n_samples) on `stream`. Checked before any HIP call, RT_ERR_INVALID naming the field: out's
+ * record first (a wrong size, two of its pointers equal; `out` may be NULL and may hold no plane: the
+ * step then retires and compacts only), then a null session, the Step rule, `out` given while
+ * done + m < 2, the scene's epochs. Then the host wait above. d_segments: optional device uint64[3] as
+ * rt_progressive_step_device: the step adds its render's counts; a step that renders nothing leaves
+ * them alone.                                                                                         */
+int rt_adaptive_step_device(rt_adaptive *ad, uint32_t n_samples, const rt_adaptive_outputs *out, void *stream,
+                            uint64_t *d_segments);
+/* Waits for the last step's counts (the host wait above), then reports.                               */
+int rt_adaptive_info(rt_adaptive *ad, rt_adaptive_info_t *info);
+/* d_b of every block, in natural block order, into host[0 .. B): synchronous (it waits for the
+ * session's enqueued work); for tools and tests. RT_ERR_CAPACITY: cap < B.                            */
+int rt_adaptive_blocks(rt_adaptive *ad, uint32_t *host, uint32_t cap);
+/* A = every block, d_b = 0, done = 0, with a new camera and / or seed (NULL: kept); the scene's epochs
+ * are taken anew. Nothing is enqueued, nothing allocated.                                             */
+int rt_adaptive_reset(rt_adaptive *ad, const rt_camera *camera, const uint64_t *seed);
+int rt_adaptive_destroy(rt_adaptive *ad);
+/* The compaction stage alone, on device pointers without a session (the kernel of Step 4): d_src_perm
+ * holds n_blocks distinct block numbers below n_blocks, of which the first class_counts[0] are the lead
+ * class, the next class_counts[1] the middle class and the last class_counts[2] the sky class (host
+ * array; their sum must be n_blocks); d_active holds one word per natural block, nonzero = kept.
+ * d_out_perm[0 .. kept) receives the kept entries in d_src_perm's order (entries past `kept` are left
+ * alone), d_counts[0 .. 4) = {kept, kept lead, kept middle, kept sky}. One launch on `stream` of the
+ * current device, no host synchronisation. RT_ERR_INVALID names a null pointer, n_blocks = 0 or above
+ * 2^26, a class sum that is not n_blocks, d_out_perm == d_src_perm.                                    */
+int rt_block_compact_device(const uint32_t *d_src_perm, uint32_t n_blocks, const uint32_t class_counts[3],
+                            const uint32_t *d_active, uint32_t *d_out_perm, uint32_t *d_counts, void *stream);
+
 /* Device memory a scene holds and how its renders are cut (after the last render call).  */
 typedef struct rt_scene_usage {
     uint64_t device_bytes;     /* every device allocation of the scene                       */

@@ -13,7 +13,8 @@ from .render import (DeviceScene, MultiContext, default_options, default_options
                      temporal_params, tile_ground, tile_order, trap_windows, Preview, preview_merge_device,
                      preview_params, preview_split_device, preview_upscale, upsample, upsample_buffers,
                      upsample_device, upsample_params, sphere_table, Progressive, progressive_blob_check,
-                     progressive_outputs, progressive_window)
+                     progressive_outputs, progressive_window, Adaptive, adaptive_outputs, adaptive_params,
+                     block_compact_device)
 from .scene import (Dielectric, Lambert, Metal, RaytracerData, Sphere, cuda_scene_arrays, huge_scene,  # noqa: F401
                     huge_scene_arrays, simple_scene, simple_scene_arrays)
 

@@ -108,6 +108,29 @@ class RtProgressiveInfo(C.Structure):
     ]
 
 
+class RtAdaptiveParams(C.Structure):
+    """rt_adaptive_params (include/rt_api.h): the retire rule of an adaptive session."""
+    _fields_ = [
+        ("size", C.c_uint32), ("noise_tau", C.c_float), ("max_noisy", C.c_uint32), ("min_samples", C.c_uint32),
+    ]
+
+
+class RtAdaptiveOutputs(C.Structure):
+    """rt_adaptive_outputs (include/rt_api.h): what a step's resolve writes, NULL = not wanted."""
+    _fields_ = [
+        ("size", C.c_uint32), ("reserved", C.c_uint32),
+        ("rgb", C.c_void_p), ("variance", C.c_void_p), ("rgb8", C.c_void_p), ("samples", C.c_void_p), ("noisy", C.c_void_p),
+    ]
+
+
+class RtAdaptiveInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint32), ("done", C.c_uint32), ("spp", C.c_uint32), ("n_blocks", C.c_uint32),
+        ("active_blocks", C.c_uint32), ("finished", C.c_uint32),
+        ("n_pixels", C.c_uint64), ("samples_rendered", C.c_uint64), ("device_bytes", C.c_uint64),
+    ]
+
+
 class RtStats(C.Structure):
     _fields_ = [
         ("primaries", C.c_uint64), ("segments", C.c_uint64), ("sphere_tests", C.c_uint64),

@@ -145,6 +145,15 @@ def _declare(L):
         "rt_progressive_blob_check": (C.c_int, [C.c_void_p, C.c_uint64, P(abi.RtParams), P(abi.RtCamera),
                                                 P(abi.RtProgressiveInfo)]),
         "rt_progressive_destroy": (C.c_int, [C.c_void_p]),
+        "rt_adaptive_create": (C.c_int, [C.c_void_p, P(abi.RtCamera), P(abi.RtParams), P(abi.RtAdaptiveParams),
+                                         P(C.c_void_p)]),
+        "rt_adaptive_step_device": (C.c_int, [C.c_void_p, C.c_uint32, P(abi.RtAdaptiveOutputs), C.c_void_p, C.c_void_p]),
+        "rt_adaptive_info": (C.c_int, [C.c_void_p, P(abi.RtAdaptiveInfo)]),
+        "rt_adaptive_blocks": (C.c_int, [C.c_void_p, P(C.c_uint32), C.c_uint32]),
+        "rt_adaptive_reset": (C.c_int, [C.c_void_p, P(abi.RtCamera), P(C.c_uint64)]),
+        "rt_adaptive_destroy": (C.c_int, [C.c_void_p]),
+        "rt_block_compact_device": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
         "rt_preview_refine_device": (C.c_int, [C.c_void_p, P(abi.RtCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
         "rt_preview_refine_info": (C.c_int, [C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),

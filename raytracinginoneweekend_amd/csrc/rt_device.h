@@ -371,6 +371,36 @@ struct KResolve {
     uint32_t W, tiles_x, tiled_rows, row_offset, row_stride, full_frame, tile_lw;
 };
 
+// adaptive_resolve (rt_adaptive.hip; rt_adaptive_step_device): KResolve with a
+// sample count per natural 64-pixel block. d_b[b]: the samples folded into block b; active[b] != 0:
+// the block is still rendered, and then holds `done` samples (the kernel stores that in d_b[b]) and
+// leaves the active set (active[b] = 0) when done >= min_samples and at most max_noisy of its pixels
+// have var > t2 (L L). samples (optional): a plane laid out like var that receives d_b. noisy
+// (optional): the kernel adds every block's noisy pixels.
+struct KAdaptive {
+    const float *acc, *mom;
+    float *out, *var;
+    uint8_t *out_u8;
+    uint32_t *samples;
+    uint32_t *noisy;
+    uint32_t *d_b, *active;
+    float t2;
+    uint32_t done, n_blocks, min_samples, max_noisy;
+    uint32_t W, tiles_x, tiled_rows, row_offset, row_stride, full_frame, tile_lw;
+};
+
+// compact_blocks_kernel (rt_adaptive.hip; rt_block_compact_device): the n entries of the dealing
+// order src (null: the identity), of which the first n0 are its lead class and the next n1 its
+// middle class, restricted to the blocks whose word in active[n_nat] is set (null: all of them),
+// into out; counts = {kept, kept of each class}.
+struct KCompact {
+    const uint32_t *src;
+    const uint32_t *active;
+    uint32_t *out;
+    uint32_t *counts;
+    uint32_t n, n_nat, n0, n1;
+};
+
 // The guided upsample (rt_upsample.hip; rt_upsample_device): the low-resolution
 // image (lw x lh; l_variance and o_variance both null: no variance) and its guides, the guides of
 // the output size (W x H), the outputs.

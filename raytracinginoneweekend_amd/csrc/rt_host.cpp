@@ -196,12 +196,15 @@ int stream_leave(rt_scene *sc, hipStream_t st)
 // the P.spp-sample frame, a a multiple of 4 and b a multiple of 4 or P.spp, folded into the caller's
 // own planes (indexed like KAccum::acc / KAccum::mom) and never divided: no pass of a window is
 // the frame's last.
+// `blocks` (an adaptive session's): the window's passes are over these blocks' pixels alone.
 struct Window {
     uint32_t a, b;
     float *acc, *mom;
+    const WindowBlocks *blocks;
 };
 int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
                        uint64_t *d_segments, float *d_var = nullptr, const Window *win = nullptr);
+int window_first_order(rt_scene *sc, const rt_camera *camera, const rt_params &P, hipStream_t st, WindowBlocks &blocks);
 } // namespace
 
 extern "C" int rt_render_device(rt_scene *sc, const rt_camera *camera, const rt_params *params, float *d_rgb, void *stream,
@@ -243,16 +246,19 @@ extern "C" int rt_render_var_device(rt_scene *sc, const rt_camera *camera, const
     return stream_leave(sc, st);
 }
 
-// A progressive session's step (rt_host_post.cpp): samples [a, b) of the frame into the session's
+// A progressive session's step (rt_host_post.cpp; an adaptive session's, rt_host_adaptive.cpp, with
+// `blocks`): samples [a, b) of the frame into the session's
 // planes as one call on the scene (a == b: no render), then `after` (the resolve, which reads
 // those planes) on the caller's stream, inside the call's stream order.
 int rthost::render_window(rt_scene *sc, const rt_camera *camera, const rt_params &P, uint32_t a, uint32_t b, float *acc,
-                          float *mom, hipStream_t st, uint64_t *d_segments, const std::function<int()> &after)
+                          float *mom, hipStream_t st, uint64_t *d_segments, const std::function<int()> &after, WindowBlocks *blocks)
 {
     RT_HIP(hipSetDevice(sc->device));
     if (int rc = stream_enter(sc, st); rc != RT_OK) return rc;
-    const Window win{a, b, acc, mom};
-    if (a < b)
+    if (blocks && blocks->first)
+        if (int rc = window_first_order(sc, camera, P, st, *blocks); rc != RT_OK) return rc;
+    const Window win{a, b, acc, mom, blocks};
+    if (a < b && (!blocks || blocks->n_active))
         if (int rc = render_device_impl(sc, camera, P, nullptr, st, d_segments, nullptr, &win); rc != RT_OK) return rc;
     if (after)
         if (int rc = after(); rc != RT_OK) return rc;
@@ -538,6 +544,7 @@ struct Frame {
     uint32_t deep_split;  // the split depth for this camera (0: none)
     unsigned long long deep_key;
     const Order *ord;  // the frame's dealing order, if any
+    const WindowBlocks *blocks;  // a window over a block list: its own dealing order instead (ord stays null)
     bool sky_kernel;             // the proven-sky tiles are rendered by sky_kernel at the last pass
     uint32_t sky_pos0;           // the first pixel position of those tiles (n_pixels: none)
     // the ground tiles (the tiled blocks of the order's middle class, which come
@@ -626,9 +633,11 @@ void deal_groups(const Frame &f, Pass &p, rt::KParams &k)
 {
     rt_scene *sc = f.sc;
     const Order *ord = f.ord;
-    const uint64_t n_pixels = k.n_pixels;
+    const uint64_t n_pixels = k.n_pixels;  // (the pass's positions: under a block list fewer than the frame's pixels)
     const uint32_t s0 = p.s0, s1 = p.s1;
-    p.ordered = ord && ord->d_perm && !k.n_pair_items;
+    const WindowBlocks *bl = f.blocks;
+    const uint32_t *perm = bl ? bl->d_perm : ord ? ord->d_perm : nullptr;
+    p.ordered = perm && !k.n_pair_items;
     fill_frame_consts(k);
     // items: the pass's pair items and its single tail samples (one slot each); with the sky
     // kernel, the positions before the sky tiles'
@@ -667,10 +676,14 @@ void deal_groups(const Frame &f, Pass &p, rt::KParams &k)
     k.grp_pix[1] = k.grp_pix[2] = k.grp_pix[3] = k.n_pixels;
     k.div_grp[0] = make_udiv(k.n_pixels);
     if (p.ordered) {
-        const rthost::tile_order &t = ord->t;
+        // the order's lead and sky blocks and all of them: the frame's, or the block list's own
+        rthost::tile_order t;
+        t.n_lead = bl ? bl->cls[0] : ord->t.n_lead;
+        t.n_sky = bl ? bl->cls[2] : ord->t.n_sky;
+        const uint32_t n_ordered = bl ? bl->n_active : ord->n_blocks;
         const uint64_t S = s1 - s0;
-        const uint64_t nbl[3] = {t.n_lead, ord->n_blocks - t.n_lead - t.n_sky, f.sky_kernel ? 0u : t.n_sky};
-        k.block_perm = ord->d_perm;
+        const uint64_t nbl[3] = {t.n_lead, n_ordered - t.n_lead - t.n_sky, f.sky_kernel ? 0u : t.n_sky};
+        k.block_perm = perm;
 #ifdef RT_ORDER_NULLPERM  // A/B build switch (with RT_ORDER_IDENTITY): the identity permutation not read
         k.block_perm = nullptr;
 #endif
@@ -1079,8 +1092,22 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     rt::KParams k{};
     if (int rc = frame_params(sc, camera, P, k, "rt_render_device"); rc) return rc;
     if (k.n_pixels == 0) return RT_OK;
+    // A window over a block list: from here on k.n_pixels counts the pass's positions, 64 per listed
+    // block. Everything below that takes it (the plan, FrameConsts::n_pixels and its divisor, the
+    // slots, the deep queue's pixel flags, KAccum::n_pixels, sky_pos0) means positions of the pass;
+    // what places a pixel in the frame (W, tiles_x, tiled_rows, tile_lw, the row fields) stays the
+    // frame's, and the running sums are indexed by the natural index the permutation yields.
+    const WindowBlocks *blocks = win ? win->blocks : nullptr;
+    if (blocks) {
+        if (!blocks->d_perm || static_cast<uint64_t>(blocks->n_active) * 64u > k.n_pixels ||
+            static_cast<uint64_t>(blocks->cls[0]) + blocks->cls[1] + blocks->cls[2] != blocks->n_active)
+            return fail(RT_ERR_INVALID, "render_window: bad block list");
+        k.n_pixels = 64u * blocks->n_active;
+        if (k.n_pixels == 0) return RT_OK;
+    }
     const rt_options &O = sc->opt;
     Frame f{sc, P, st, d_rgb, d_var, d_segments};
+    f.blocks = blocks;
     const KernelChoice &c = f.c;
     const Plan &pl = f.pl;
 
@@ -1106,7 +1133,8 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     // the frame's dealing order (not with sample pairs) and the sky kernel: the
     // tiles proven to send every primary ray to the sky are rendered by sky_kernel at the frame's
     // last pass (all samples, one thread per pixel, no slots), the passes deal the others
-    if (c.order_ok && !pl.pairs)
+    // (a block list is its own order, whatever the scene and the flags: the identity's where they have none)
+    if (c.order_ok && !pl.pairs && !blocks)
         if (int rc = pass_order(sc, *camera, k, st, &f.ord); rc) return rc;
     // (max_depth 0: every sample's colour is 0, main.cxx:74, not the sky's)
     f.sky_kernel = f.ord && f.ord->d_perm && f.ord->t.n_sky && P.max_depth > 0 && !(O.diag & RT_DIAG_NO_SKY) && !moments;
@@ -1170,6 +1198,30 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     }
     // (every launch above that reads the order's permutation is ordered before st's tail)
     return order_used(sc, f.ord, st);
+}
+
+// The first window of an adaptive session: the dealing order the frame's own window would take
+// (pass_order's for this camera and rows where the kernel choice deals by tile classes, else the
+// identity), handed to the session, which enqueues its copy on `st`; the cached order is then marked
+// as read up to st's tail, so its pool slot is not recycled under that copy.
+int window_first_order(rt_scene *sc, const rt_camera *camera, const rt_params &P, hipStream_t st, WindowBlocks &blocks)
+{
+    rt::KParams k{};
+    if (int rc = frame_params(sc, camera, P, k, "render_window"); rc) return rc;
+    KernelChoice c{};
+    if (int rc = choose_kernel(sc, *camera, P, true, k, c); rc) return rc;
+    const Order *ord = nullptr;
+    if (c.order_ok)
+        if (int rc = pass_order(sc, *camera, k, st, &ord); rc) return rc;
+    const bool ordered = ord && ord->d_perm;
+    if (int rc = blocks.first(ordered ? ord->d_perm : nullptr, ordered ? ord->t.n_lead : 0u, ordered ? ord->t.n_sky : 0u); rc) return rc;
+    blocks.first = nullptr;
+    // the window's passes run on the render streams, which nothing else orders behind st's work
+    RT_HIP(sc->ev_blocks.make(hipEventDisableTiming));
+    RT_HIP(hipEventRecord(sc->ev_blocks.get(), st));
+    for (const rthost::Stream &x : sc->xs)
+        if (x) RT_HIP(hipStreamWaitEvent(x.get(), sc->ev_blocks.get(), 0));
+    return order_used(sc, ord, st);
 }
 
 int render_compat(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,

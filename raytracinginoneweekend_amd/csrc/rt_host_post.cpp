@@ -914,6 +914,19 @@ struct rt_progressive {
     uint64_t geometry_epoch = 0, appearance_epoch = 0;
 };
 
+// The Step rule: m = min(n, spp - done); a window that stops before the frame's end holds whole blocks of 4.
+// (rt_host_sync.h: the adaptive session, rt_host_adaptive.cpp, takes its windows by the same rule)
+int rthost::progressive_window(const std::string &w, uint32_t spp, uint32_t done, uint32_t n, uint32_t *m)
+{
+    if (spp < 2u) return fail(RT_ERR_INVALID, w + "spp must be at least 2");
+    if (done > spp || (done != spp && (done & 3u))) return fail(RT_ERR_INVALID, w + "done must be a multiple of 4 or spp");
+    const uint32_t left = spp - done;
+    if ((n & 3u) && n < left)
+        return fail(RT_ERR_INVALID, w + "n_samples must be a multiple of 4 before the frame's end (passes start on multiples of 4)");
+    *m = n < left ? n : left;
+    return RT_OK;
+}
+
 namespace {
 
 // The head of a checkpoint (rt_progressive_save); the planes follow it.
@@ -931,18 +944,6 @@ constexpr uint32_t kProgressiveLayout = 0x33383301u;
 
 uint64_t progressive_plane_bytes(uint64_t n_pixels) { return n_pixels * 3u * sizeof(float); }
 uint64_t progressive_state_bytes(uint64_t n_pixels) { return sizeof(ProgressiveHeader) + 2u * progressive_plane_bytes(n_pixels); }
-
-// The Step rule: m = min(n, spp - done); a window that stops before the frame's end holds whole blocks of 4.
-int progressive_window(const std::string &w, uint32_t spp, uint32_t done, uint32_t n, uint32_t *m)
-{
-    if (spp < 2u) return fail(RT_ERR_INVALID, w + "spp must be at least 2");
-    if (done > spp || (done != spp && (done & 3u))) return fail(RT_ERR_INVALID, w + "done must be a multiple of 4 or spp");
-    const uint32_t left = spp - done;
-    if ((n & 3u) && n < left)
-        return fail(RT_ERR_INVALID, w + "n_samples must be a multiple of 4 before the frame's end (passes start on multiples of 4)");
-    *m = n < left ? n : left;
-    return RT_OK;
-}
 
 // load's check: the blob against the params and camera of a session.
 int progressive_blob_check(const std::string &w, const void *host, uint64_t bytes, const rt_params &P, const rt_camera &cam,

@@ -1,6 +1,6 @@
 // rt_host_sync.h — what the device half's files share (the four around the scene record, rt_scene.h:
 // rt_host_scene.cpp, rt_host_order.cpp, rt_host.cpp, rt_host_synccall.cpp; rt_host_post.cpp: the
-// filters, temporal accumulation and sessions; rt_host_multi.cpp: the multi-GPU context): the
+// filters, temporal accumulation and sessions; rt_host_adaptive.cpp: the adaptive session; rt_host_multi.cpp: the multi-GPU context): the
 // kernels' launchers, the HIP error forms, the params checks, a scene's device and sample windows
 // for those that do not see the record, and the one path every synchronous host-buffer entry point
 // takes through the cached per-device context (SyncCall, implemented in rt_host_synccall.cpp).
@@ -56,6 +56,9 @@ hipError_t launch_preview_split(const KPreviewSplit &k, hipStream_t stream);
 hipError_t launch_preview_merge(const KPreviewMerge &k, hipStream_t stream);
 // rt_progressive.hip
 hipError_t launch_progressive_resolve(const KResolve &k, hipStream_t stream);
+// rt_adaptive.hip
+hipError_t launch_adaptive_resolve(const KAdaptive &k, hipStream_t stream);
+hipError_t launch_compact_blocks(const KCompact &k, hipStream_t stream);
 // rt_tiles.hip
 hipError_t launch_classify_tiles(const rttile::KTiles &k, hipStream_t stream);
 hipError_t launch_order_blocks(const uint8_t *cls, uint32_t n_blocks, uint32_t *perm, uint32_t *counts, hipStream_t stream);
@@ -97,8 +100,24 @@ PixelLayout pixel_layout(const rt_params &P);
 // Samples [a, b) of the P.spp-sample frame (a a multiple of 4, b one or P.spp; a == b: nothing)
 // folded into acc / mom, [n_pixels][3] floats each, by the passes of a variance render that never
 // reaches its last pass; then `after` on `st`; one call on the scene's stream order (rt_host.cpp).
+// `blocks` (an adaptive session's step): the window renders the pixels of these
+// 64-pixel blocks alone. A pass over them is a pass whose position count is 64 n_active and whose
+// block permutation is d_perm; the frame's width, tiles and rows stay the frame's.
+struct WindowBlocks {
+    const uint32_t *d_perm;  // the blocks' natural numbers in dealing order (device), n_active entries
+    uint32_t n_active;
+    uint32_t cls[3];         // its lead / other / sky blocks (their sum is n_active)
+    // The session's first window: called inside the call's stream order, before the render, with the
+    // frame's own dealing order (frame_perm null: the identity, every block in the middle class), of
+    // which it enqueues its copy on `st` and fills the fields above. Null: they are filled already.
+    std::function<int(const uint32_t *frame_perm, uint32_t n_lead, uint32_t n_sky)> first;
+};
 int render_window(rt_scene *sc, const rt_camera *camera, const rt_params &P, uint32_t a, uint32_t b, float *acc, float *mom,
-                  hipStream_t st, uint64_t *d_segments, const std::function<int()> &after);
+                  hipStream_t st, uint64_t *d_segments, const std::function<int()> &after, WindowBlocks *blocks = nullptr);
+
+// The Step rule of a progressive or adaptive session (rt_host_post.cpp): *m = min(n, spp - done);
+// a window that stops before the frame's end holds whole blocks of 4. `w` starts the message.
+int progressive_window(const std::string &w, uint32_t spp, uint32_t done, uint32_t n, uint32_t *m);
 
 // The scene of a synchronous render: the context keeps its device scene between calls.
 struct SyncScene {

@@ -226,6 +226,9 @@ struct rt_scene {
     uint32_t ground_ring = 0;
     uint64_t ground_call = 0;  // calls of the frame ground_samples and ground_ring belong to
     rthost::Event ev_gpre, ev_ground;
+    // after an adaptive session's copy of the frame's dealing order, enqueued on the caller's stream
+    // at the session's first window: the render streams, whose passes read it, wait
+    rthost::Event ev_blocks;
     // ring of (start, end) events bracketing the render kernels of each rt_render_device call
     static constexpr uint32_t kRing = 256;
     std::vector<rthost::Event> ev_begin, ev_end;

@@ -724,6 +724,85 @@ class Progressive:
             pass
 
 
+def adaptive_params(noise_tau, max_noisy=0, min_samples=4):
+    """An rt_adaptive_params record: a block retires once it holds min_samples samples and at most
+    max_noisy of its 64 pixels have var > noise_tau^2 L^2."""
+    return abi.RtAdaptiveParams(C.sizeof(abi.RtAdaptiveParams), noise_tau, max_noisy, min_samples)
+
+
+def adaptive_outputs(rgb_ptr=None, variance_ptr=None, rgb8_ptr=None, samples_ptr=None, noisy_ptr=None):
+    """An rt_adaptive_outputs record from device addresses (None: that plane is not wanted)."""
+    return abi.RtAdaptiveOutputs(C.sizeof(abi.RtAdaptiveOutputs), 0, rgb_ptr or None, variance_ptr or None, rgb8_ptr or None,
+                                 samples_ptr or None, noisy_ptr or None)
+
+
+def block_compact_device(src_perm_ptr, n_blocks, class_counts, active_ptr, out_perm_ptr, counts_ptr, stream=None):
+    """rt_block_compact_device: the adaptive session's compaction kernel alone, on device addresses:
+    the entries of the dealing order at src_perm_ptr whose block's word at active_ptr is nonzero, in
+    order, to out_perm_ptr; {kept, kept lead, kept middle, kept sky} to counts_ptr."""
+    cc = (C.c_uint32 * 3)(*class_counts) if class_counts is not None else None
+    check(lib().rt_block_compact_device(C.c_void_p(src_perm_ptr or 0), n_blocks, cc, C.c_void_p(active_ptr or 0),
+                                        C.c_void_p(out_perm_ptr or 0), C.c_void_p(counts_ptr or 0), C.c_void_p(stream or 0)))
+
+
+class Adaptive:
+    """An adaptive session on a DeviceScene (rt_adaptive_create): the frame that
+    `params` describes in sample windows, like Progressive, but a 64-pixel block whose noise estimate
+    has fallen under the rule of `adaptive` (adaptive_params) is rendered no further. params.spp is the
+    cap of every pixel's sample count. Close it before its scene."""
+
+    def __init__(self, device_scene, camera, params, adaptive):
+        h = C.c_void_p()
+        sc = device_scene.handle if device_scene is not None else None
+        cam = C.byref(_cam_record(camera)) if camera is not None else None
+        check(lib().rt_adaptive_create(sc, cam, C.byref(params) if params is not None else None,
+                                       C.byref(adaptive) if adaptive is not None else None, C.byref(h)))
+        self.handle = h
+        self.scene = device_scene  # (kept alive as long as the session)
+
+    def step(self, n_samples, rgb_ptr=None, variance_ptr=None, rgb8_ptr=None, samples_ptr=None, noisy_ptr=None, stream=None,
+             segments=None, outputs=None):
+        """Enqueue the next n_samples samples of the blocks still active on `stream`, then the
+        estimate of the whole frame (every block after its own sample count) into the planes given,
+        the retire rule and the next step's block list. Waits for the previous step's block counts."""
+        if outputs is None and (rgb_ptr or variance_ptr or rgb8_ptr or samples_ptr or noisy_ptr):
+            outputs = adaptive_outputs(rgb_ptr, variance_ptr, rgb8_ptr, samples_ptr, noisy_ptr)
+        check(lib().rt_adaptive_step_device(self.handle, n_samples, C.byref(outputs) if outputs is not None else None,
+                                            C.c_void_p(stream or 0), C.c_void_p(segments) if segments else None))
+
+    def info(self):
+        """rt_adaptive_info as a dict: done, spp, n_blocks, active_blocks, finished, n_pixels,
+        samples_rendered, device_bytes (waits for the last step's block counts)."""
+        r = abi.RtAdaptiveInfo()
+        check(lib().rt_adaptive_info(self.handle, C.byref(r)))
+        return {n: getattr(r, n) for n in ("done", "spp", "n_blocks", "active_blocks", "finished", "n_pixels",
+                                           "samples_rendered", "device_bytes")}
+
+    def blocks(self):
+        """rt_adaptive_blocks: the samples folded into every 64-pixel block, in natural block order
+        (uint32 array; synchronous)."""
+        n = self.info()["n_blocks"]
+        out = np.zeros(n, dtype=np.uint32)
+        check(lib().rt_adaptive_blocks(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return out
+
+    def reset(self, camera=None, seed=None):
+        """The frame starts again (every block active, no sample), with another camera and / or seed when given."""
+        check(lib().rt_adaptive_reset(self.handle, C.byref(_cam_record(camera)) if camera is not None else None,
+                                      C.byref(C.c_uint64(seed)) if seed is not None else None))
+
+    def close(self):
+        if self.handle:
+            lib().rt_adaptive_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def preview_split_device(width, height, beauty, variance, albedo, illumination, variance_out, stream=None):
     """Enqueue rt_preview_split_device (device addresses): illumination = beauty / albedo',
     variance_out = variance / luminance(albedo')^2."""
@@ -920,6 +999,11 @@ class DeviceScene:
     def progressive(self, camera, params):
         """A progressive session on this scene (Progressive): the frame of `params` in sample windows."""
         return Progressive(self, _cam(camera, params), params)
+
+    def adaptive(self, camera, params, adaptive):
+        """An adaptive session on this scene (Adaptive): the frame of `params` in sample windows that
+        leave out the 64-pixel blocks retired by the rule of `adaptive` (adaptive_params)."""
+        return Adaptive(self, _cam(camera, params), params, adaptive)
 
     def tile_order(self, camera, params, stream=None):
         """rt_tile_order_device: the pass's dealing order computed by the device's classification
