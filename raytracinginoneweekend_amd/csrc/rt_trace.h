@@ -381,18 +381,21 @@ __device__ __forceinline__ bool fast_div(const RayDiv &r)
 }
 // n / r for the three components of n by the short form, with r's refined reciprocal formed once.
 // The caller has checked that no operand takes the IEEE sequence's scaling or fix-up paths:
-// r in [2^-40, 2^20], every |n_i| in [2^-100, 2^21] (so no zero, whose sign the short form can
-// lose, and no quotient below 2^-126).
+// |r| in [2^-40, 2^20], of either sign (the hollow ball's radius is negative), every |n_i| in
+// [2^-100, 2^21] (so no zero, whose sign the short form can lose, and no quotient below 2^-126).
 __device__ __forceinline__ f3 div3_short(f3 n, float r)
 {
     const float y0 = __builtin_amdgcn_rcpf(r);
     const RayDiv rr{r, fmaf(fmaf(-r, y0, 1.f), y0, y0), 1u};
     return mk(div_ray(n.x, rr), div_ray(n.y, rr), div_ray(n.z, rr));
 }
-// every active lane's |n_i| >= 2^-100 (a wave-uniform answer; one min3 and one compare per lane)
+// every active lane's |n_i| >= 2^-100 (a wave-uniform answer; one min3 and one compare per lane).
+// The minimum is IEEE 754-2019's (v_minimum3_f32): a NaN component stays NaN and fails the
+// compare, where fminf would drop it and let the lane pass.
 __device__ __forceinline__ bool all_lanes_min_abs_ok(f3 n)
 {
-    return !ballot(!(fminf(fminf(fabsf(n.x), fabsf(n.y)), fabsf(n.z)) >= 0x1p-100f));
+    const float m = __builtin_elementwise_minimum(__builtin_elementwise_minimum(fabsf(n.x), fabsf(n.y)), fabsf(n.z));
+    return !ballot(!(m >= 0x1p-100f));
 }
 // the near root (-b - sqrt(disc)) / a and its sqrt, raytracer.hxx:62-63; FD: 1 the short forms
 // (the caller has branched on fast_div), 0 the IEEE forms, -1 a branch on fast_div here
