@@ -175,6 +175,13 @@ typedef struct rt_options {
                                        scene has not seen: 0 = on the host (0),
                                        1 = by kernels on a stream of the scene's own, without a
                                        device-wide synchronisation. Same order, same bits        */
+    uint32_t sky_moments;           /* frames that carry per-pixel moments (rt_render_var_device,
+                                       the progressive, adaptive and preview sessions; DESIGN.md
+                                       §4.21): 0 = their proven-sky tiles are traced by the main
+                                       launch (0), 1 = sky_moments_kernel renders them, sums and
+                                       moments, and the main launch deals the other tiles alone.
+                                       Same bits and segment count; the sphere- and box-test
+                                       counters (d_segments[1], [2]) drop by the tests it saves   */
 } rt_options;
 enum rt_diag {
     RT_DIAG_IEEE_ROOTS = 1u << 0,      /* the IEEE sqrt/division sequences for every root     */
@@ -214,7 +221,8 @@ enum rt_diag {
 int rt_options_default(rt_options *out);
 /* Applies "key=value[,key=value...]" (fields above; diag bits as ieee_roots, no_shortcut,
  * no_neighbours, no_root_box, shade_lds, shade_global, stats, stats_deep_only, verbose,
- * standin_transport = 0/1) to *inout; RT_ERR_INVALID on an unknown key or a bad value.   */
+ * standin_transport = 0/1; tile_classes and sky_moments are fields, 0/1) to *inout;
+ * RT_ERR_INVALID on an unknown key or a bad value.                                       */
 int rt_options_parse(const char *text, rt_options *inout);
 /* The options of scenes created without explicit ones (NULL: the library defaults).      */
 int rt_set_default_options(const rt_options *options);
@@ -429,7 +437,13 @@ int rt_scene_ground_counts(rt_scene *scene, uint64_t *ground_samples, uint64_t *
  * RT_FLAG_SCALAR_SCENE, RT_FLAG_WAVEFRONT and RT_FLAG_CUDA_COMPAT return RT_ERR_UNSUPPORTED. Every
  * argument is checked before any HIP call. The frame is planned with one sample per slot and its
  * proven-sky tiles traced by the main launch (as under RT_DIAG_NO_PAIRS | RT_DIAG_NO_SKY), whatever
- * the scene's options say: the per-sample colours must reach the accumulation. A frame of several
+ * the scene's other options say: the per-sample colours must reach the accumulation. With
+ * rt_options.sky_moments = 1 the proven-sky tiles go to the sky kernel's moments form instead, which
+ * folds each colour into the pixel's sum and moments itself (same bits; rt_scene_usage.sky_tiles
+ * reports them). Of d_segments' three words the first, the segments, is the same
+ * with the option on or off; the sphere-test and box-test words come out smaller with it on, because
+ * the kernel tests its samples, proven to miss, against nothing, exactly as rt_render_device's counters
+ * relate to a render under RT_DIAG_NO_SKY. A frame of several
  * passes carries {L_0, m1, m2} per pixel in a workspace accounted like the multi-pass sums
  * (rt_scene_usage, max_workspace_bytes), allocated by the first such frame. d_segments, stream
  * order and frames in flight are rt_render_device's.                                           */

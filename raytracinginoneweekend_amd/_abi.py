@@ -71,7 +71,7 @@ class RtOptions(C.Structure):
         ("deep_split", C.c_uint32), ("max_pass_bytes", C.c_uint64), ("max_workspace_bytes", C.c_uint64),
         ("deep_min_items", C.c_uint64), ("cluster_size", C.c_uint32), ("transpose_max", C.c_uint32),
         ("wave_queue_rays", C.c_uint32), ("diag", C.c_uint32), ("ring_pass_bytes", C.c_uint64),
-        ("tile_classes", C.c_uint32),
+        ("tile_classes", C.c_uint32), ("sky_moments", C.c_uint32),
     ]
 
 

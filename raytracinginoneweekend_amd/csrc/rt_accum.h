@@ -5,13 +5,24 @@
 
 namespace rt {
 
-// MOMENTS (rt_render_var_device; single-sample slots, no sky kernel): from the
-// same slot loads, in sample order, the shifted moments of the samples' luminance, carried between
-// passes in k.mom[ni] = {L_0, m1, m2}; the last pass writes the variance of the mean to k.var.
+// MOMENTS (rt_render_var_device; single-sample slots): from the same slot loads,
+// in sample order, the shifted moments of the samples' luminance, carried between passes in
+// k.mom[ni] = {L_0, m1, m2}; the last pass writes the variance of the mean to k.var. The sky
+// positions of a plan with sky_moments_kernel (rt_sky.hip) are folded there: the
+// last pass of a one-shot frame finds their sums at their sample-0 slots and {L_0, m1, m2} at their
+// sample-1 slots.
 // A template on MOMENTS: accumulate_kernel (false) and accumulate_moments_kernel (true).
-__device__ __forceinline__ float accum_luminance(const f3 &c)
+//
+// One sample's colour into the shifted moments, samples in order: its luminance L, d = L - L_0
+// (frame_first: the frame's sample 0, L_0 = L and d = 0), m1 += d, m2 += d d. The one statement of
+// this arithmetic, for accumulate_pixels<true> and sky_moments_kernel.
+__device__ __forceinline__ void fold_luminance(const f3 &c, bool frame_first, float &l0, float &m1, float &m2)
 {
-    return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+    const float l = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+    if (frame_first) l0 = l;
+    const float d = l - l0;
+    m1 = m1 + d;
+    m2 = m2 + d * d;
 }
 
 template <bool MOMENTS>
@@ -52,8 +63,13 @@ __device__ __forceinline__ void accumulate_pixels(const KAccum &k)
     f3 acc;
     float l0 = 0.f, m1 = 0.f, m2 = 0.f;  // MOMENTS: L_0 and the shifted sums
     (void)l0; (void)m1; (void)m2;
-    if (sky) acc = mk(k.slots[3 * i], k.slots[3 * i + 1], k.slots[3 * i + 2]);
-    else if (k.first) acc = mk(0.f, 0.f, 0.f);
+    if (sky) {
+        acc = mk(k.slots[3 * i], k.slots[3 * i + 1], k.slots[3 * i + 2]);
+        if (MOMENTS) {
+            const float *m = k.slots + 3u * ((size_t)k.n_pixels + i);
+            l0 = m[0], m1 = m[1], m2 = m[2];
+        }
+    } else if (k.first) acc = mk(0.f, 0.f, 0.f);
     else acc = mk(k.acc[3 * ni], k.acc[3 * ni + 1], k.acc[3 * ni + 2]);
     // main.cxx:205 = libstdc++ reduce (<numeric>:443-460): ((c0+c1)+(c2+c3)) per block of 4,
     // blocks in order, then the spp % 4 tail one by one. Passes start on a multiple of 4.
@@ -69,14 +85,7 @@ __device__ __forceinline__ void accumulate_pixels(const KAccum &k)
         for (uint32_t t = 4u * k.n_blocks; t < k.n_samples; ++t) acc = acc + ld(t - 2u * k.n_blocks);
     } else if (MOMENTS) {
         if (!k.first) l0 = k.mom[3 * ni], m1 = k.mom[3 * ni + 1], m2 = k.mom[3 * ni + 2];
-        // sample t of the pass: d = L - L_0 (the frame's sample 0: L_0 = L, d = 0), m1 += d, m2 += d d
-        auto fold = [&](const f3 &c, uint32_t t) {
-            const float l = accum_luminance(c);
-            if (k.first && t == 0u) l0 = l;
-            const float d = l - l0;
-            m1 = m1 + d;
-            m2 = m2 + d * d;
-        };
+        auto fold = [&](const f3 &c, uint32_t t) { fold_luminance(c, k.first && t == 0u, l0, m1, m2); };  // sample t of the pass
         uint32_t s = 0;
         for (; s < 4u * k.n_blocks; s += 4u) {
             const f3 c0 = ld(s), c1 = ld(s + 1u), c2 = ld(s + 2u), c3 = ld(s + 3u);

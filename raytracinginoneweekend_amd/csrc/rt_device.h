@@ -191,7 +191,8 @@ struct KAccum {
     uint32_t deep_rcap;
     const uint32_t *block_perm;  // the pass's permuted enumeration (KParams::block_perm), or null
     // positions from sky_pos0 on are the sky kernel's (n_pixels: none): skipped by every pass but
-    // the last, whose accumulation divides their sums (at their sample-0 slots) by spp
+    // the last, whose accumulation divides their sums (at their sample-0 slots) by spp; the moments
+    // instantiation also takes {L_0, m1, m2} from their sample-1 slots (sky_moments_kernel)
     uint32_t sky_pos0;
     // split passes accumulate in two parts: part 1 (after the main launch, beside the deep one)
     // the pixels none of whose samples went to the deep queue, part 2 (after the deep launch)
@@ -230,6 +231,18 @@ struct KSky {
     uint32_t pos0, n_pix;          // the sky positions [pos0, pos0 + n_pix) of the enumeration
     float *sums;
     unsigned long long *segments;  // optional: adds n_pix * spp segments (no sphere test)
+};
+// Its moments form (sky_moments_kernel): samples [s_a, s_b) of the frame's fc.spp for
+// the same positions (sky.sums unused; sky.segments gains n_pix * (s_b - s_a)). The pixel's running
+// sum and {L_0, m1, m2} are read (s_a > 0) and written at acc / mom + 3 j. natural = 1 (a session's
+// window): j is the pixel's natural index, acc and mom the session's planes (KAccum::acc / mom).
+// natural = 0 (a one-shot frame, s_a = 0 and s_b = fc.spp): j = i - pos0, acc the positions' sample-0
+// slots and mom their sample-1 slots of the last pass's workspace, which that pass's accumulation reads.
+struct KSkyMoments {
+    KSky sky;
+    uint32_t s_a, s_b;
+    uint32_t natural;
+    float *acc, *mom;
 };
 
 // The redo list of a pass: the item words (= slot indices) of the samples

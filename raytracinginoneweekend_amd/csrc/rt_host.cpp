@@ -546,6 +546,7 @@ struct Frame {
     const Order *ord;  // the frame's dealing order, if any
     const WindowBlocks *blocks;  // a window over a block list: its own dealing order instead (ord stays null)
     bool sky_kernel;             // the proven-sky tiles are rendered by sky_kernel at the last pass
+                                 // (a frame with moments: by sky_moments_kernel, at the call's last pass)
     uint32_t sky_pos0;           // the first pixel position of those tiles (n_pixels: none)
     // the ground tiles (the tiled blocks of the order's middle class, which come
     // before its untiled blocks) are rendered by ground_kernel pass by pass, the samples it punts
@@ -659,7 +660,7 @@ void deal_groups(const Frame &f, Pass &p, rt::KParams &k)
     // 2.466-2.474 ms vs 2.528-2.547 with none, 2.474-2.495 with 1; period unchanged;
     // profiles/r06/ab/sky_room.txt). RT_LONE_SKY_ROOM >= 0 (A/B build switch) fixes it.
     // (with a ground kernel, which then runs beside it too: the share of both)
-    if (!p.in_flight && f.sky_kernel && p.ordered && s1 == f.P.spp && f.pipe() && !(sc->opt.diag & RT_DIAG_SKY_SERIAL)) {
+    if (!p.in_flight && f.sky_kernel && p.ordered && s1 == f.s_end && f.pipe() && !(sc->opt.diag & RT_DIAG_SKY_SERIAL)) {
         const double sky_frac = 1.0 - static_cast<double>(f.sky_pos0 - ground_px) / static_cast<double>(n_pixels);
         const int room = RT_LONE_SKY_ROOM >= 0 ? RT_LONE_SKY_ROOM : static_cast<int>(wg_cu * sky_frac * 0.4 + 0.5);
         wg_cu = std::max(1, wg_cu - room);
@@ -977,22 +978,43 @@ int launch_deep(const Frame &f, Pass &p, const rt::KParams &k)
 // pass's accumulation. A pass issued alone runs it on another stream, after the workspace is
 // free, beside the main launch (which leaves it room) and the deep launch; beside other renders
 // it follows the pass on its stream.
+// A frame with moments (rt_options.sky_moments = 1): sky_moments_kernel at the call's
+// last pass, the call's samples. A one-shot frame's sums go to the positions' sample-0 slots as
+// above and {L_0, m1, m2} to their sample-1 slots (the workspace of a pass holds two rows at least:
+// spp >= 2). A window's kernel reads and writes the session's planes, which until now only the
+// caller's stream touched: it is ordered after everything that stream held when the call began
+// (ev_enter: the previous step's sky kernel, accumulation and resolve), and the step's own
+// accumulation and resolve follow it through ev_done or ev_sky like any pass's.
 int launch_sky_tiles(const Frame &f, Pass &p, const rt::KParams &k)
 {
     rt_scene *sc = f.sc;
     const uint32_t wb = p.wb;
-    rt::KSky ks{};
+    rt::KSkyMoments km{};
+    rt::KSky &ks = km.sky;
     ks.fc = k.fc;
     ks.block_perm = k.block_perm;
     ks.pos0 = f.sky_pos0;
     ks.n_pix = k.n_pixels - f.sky_pos0;
     ks.sums = k.slots + 3u * static_cast<size_t>(f.sky_pos0);
     ks.segments = k.segments;
-    p.sky_aside = f.pipe() && !p.in_flight && !(sc->opt.diag & RT_DIAG_SKY_SERIAL);
-    if (!p.sky_aside) {
-        RT_HIP(rt::launch_sky(ks, p.xst));
-        return RT_OK;
+    const bool moments = f.d_var != nullptr, window = f.win_acc != nullptr;
+    if (moments) {
+        km.s_a = f.s_begin;
+        km.s_b = f.s_end;
+        km.natural = window ? 1u : 0u;
+        km.acc = window ? f.win_acc : ks.sums;
+        km.mom = window ? f.win_mom : ks.sums + 3u * static_cast<size_t>(k.n_pixels);
+        ks.sums = nullptr;
+        if (!window && sc->ws.slots[wb].bytes() < 2u * 12u * static_cast<uint64_t>(k.n_pixels))
+            return fail(RT_ERR_CAPACITY, "rt_render_var_device: the last pass's workspace holds no second slot row");
     }
+    auto launch = [&](hipStream_t s) -> int {
+        if (moments && window && s != f.st) RT_HIP(hipStreamWaitEvent(s, sc->ev_enter.get(), 0));
+        RT_HIP(moments ? rt::launch_sky_moments(km, s) : rt::launch_sky(ks, s));
+        return RT_OK;
+    };
+    p.sky_aside = f.pipe() && !p.in_flight && !(sc->opt.diag & RT_DIAG_SKY_SERIAL);
+    if (!p.sky_aside) return launch(p.xst);
     // the next render stream, not a stream of its own: HIP maps streams to hardware
     // queues round-robin in creation order, and a ninth stream shared a queue with one
     // of the render streams, behind whose main launch the sky kernel then waited (one
@@ -1005,7 +1027,7 @@ int launch_sky_tiles(const Frame &f, Pass &p, const rt::KParams &k)
         if (!p.two_part) RT_HIP(record_main(sc, p));
         RT_HIP(hipStreamWaitEvent(sky_st, sc->ev_main[wb].get(), 0));
     }
-    RT_HIP(rt::launch_sky(ks, sky_st));
+    if (int rc = launch(sky_st); rc) return rc;
     RT_HIP(hipEventRecord(sc->ev_sky.get(), sky_st));
     return RT_OK;
 }
@@ -1081,7 +1103,9 @@ int accumulate(const Frame &f, const Pass &p, const rt::KParams &k)
 
 // d_var (rt_render_var_device): the frame also yields the variance of each pixel's
 // mean luminance. Its samples' colours must reach the accumulation one by one, so it is planned as
-// under RT_DIAG_NO_PAIRS | RT_DIAG_NO_SKY whatever the scene's options say.
+// under RT_DIAG_NO_PAIRS whatever the scene's options say, and as under RT_DIAG_NO_SKY unless
+// rt_options.sky_moments = 1: then sky_moments_kernel renders the proven-sky tiles, folding each
+// colour into the pixel's moments itself.
 int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P, float *d_rgb, hipStream_t st,
                        uint64_t *d_segments, float *d_var, const Window *win)
 {
@@ -1137,15 +1161,20 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     if (c.order_ok && !pl.pairs && !blocks)
         if (int rc = pass_order(sc, *camera, k, st, &f.ord); rc) return rc;
     // (max_depth 0: every sample's colour is 0, main.cxx:74, not the sky's)
-    f.sky_kernel = f.ord && f.ord->d_perm && f.ord->t.n_sky && P.max_depth > 0 && !(O.diag & RT_DIAG_NO_SKY) && !moments;
-    f.sky_pos0 = f.sky_kernel ? static_cast<uint32_t>(64u * static_cast<uint64_t>(f.ord->n_blocks - f.ord->t.n_sky)) : k.n_pixels;
+    // (a frame with moments: under rt_options.sky_moments = 1 alone, by sky_moments_kernel; a block
+    // list is the order then, its sky blocks last)
+    const uint32_t n_ordered = blocks ? blocks->n_active : f.ord && f.ord->d_perm ? f.ord->n_blocks : 0u;
+    const uint32_t n_sky = blocks ? blocks->cls[2] : f.ord && f.ord->d_perm ? f.ord->t.n_sky : 0u;
+    f.sky_kernel = n_sky && P.max_depth > 0 && !(O.diag & RT_DIAG_NO_SKY) && (!moments || O.sky_moments == 1u);
+    f.sky_pos0 = f.sky_kernel ? static_cast<uint32_t>(64u * static_cast<uint64_t>(n_ordered - n_sky)) : k.n_pixels;
     // the ground tiles: the order's middle class is its tiled blocks of class 1,
     // in ascending order, then the untiled blocks (class 1 too, numbered after every tile)
     f.ground = false;
     f.ground_pos0 = f.ground_pos1 = f.sky_pos0;
 #ifndef RT_NO_GROUND  // A/B build switch: every pass as before the ground kernel
-    // (f.sky_kernel: a culled LDS kernel dealt by tile classes, single samples, no moments, no_sky unset)
-    if (f.sky_kernel && sc->dev.ground_ok && ground_pass_ok(O, P)) {
+    // (f.sky_kernel: a culled LDS kernel dealt by tile classes, single samples, no_sky unset; the ground
+    // kernel stays out of frames with moments, whichever kernel renders their sky)
+    if (f.sky_kernel && !moments && sc->dev.ground_ok && ground_pass_ok(O, P)) {
         const uint32_t n_ground = ground_blocks(f.ord->n_blocks, f.ord->t.n_lead, f.ord->t.n_sky, k.W, k.num_rows, k.tile_lw);
         f.ground = n_ground != 0u;
         f.ground_pos0 = 64u * f.ord->t.n_lead;
@@ -1156,6 +1185,10 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
     ++sc->calls;
     f.s_begin = s_begin, f.s_end = s_end;
     f.win_acc = win ? win->acc : nullptr, f.win_mom = win ? win->mom : nullptr;
+    if (win && f.sky_kernel && f.pipe()) {
+        RT_HIP(sc->ev_enter.make(hipEventDisableTiming));
+        RT_HIP(hipEventRecord(sc->ev_enter.get(), st));
+    }
 
     auto others_running = [&] { return f.pipe() && sc->last_ws >= 0 && hipEventQuery(sc->ev_done[sc->last_ws].get()) == hipErrorNotReady; };
     // a frame issued alone that fits one pass takes it whole (Plan::whole); otherwise ring passes
@@ -1186,7 +1219,7 @@ int render_device_impl(rt_scene *sc, const rt_camera *camera, const rt_params &P
             if (k.deep_depth)
                 if (int rc = launch_deep(f, p, k); rc) return rc;
         }
-        if (f.sky_kernel && s1 == P.spp)
+        if (f.sky_kernel && s1 == s_end)
             if (int rc = launch_sky_tiles(f, p, k); rc) return rc;
         if (c.variant == rt::V_STATS_LDS) sc->dbg_waves = p.stats_waves;
         if (s1 == s_end) RT_HIP(hipEventRecord(sc->ev_end[f.ring].get(), p.xst));

@@ -77,6 +77,7 @@ rt_options library_defaults()
     o.diag = 0;
     o.ring_pass_bytes = 384ull << 20;
     o.tile_classes = 0;  // dealing orders computed on the host
+    o.sky_moments = 0;   // variance frames trace their proven-sky tiles in the main launch
     return o;
 }
 
@@ -97,6 +98,7 @@ int check_options(const rt_options &o)
     if (o.diag & ~(((RT_DIAG_SKY_SERIAL << 1) - 1u) | RT_DIAG_NO_TRAP_END)) return bad("diag (unknown bit)");
     if ((o.diag & RT_DIAG_SHADE_LDS) && (o.diag & RT_DIAG_SHADE_GLOBAL)) return bad("diag (shade_lds with shade_global)");
     if (o.tile_classes > 1) return bad("tile_classes (0 host, 1 device)");
+    if (o.sky_moments > 1) return bad("sky_moments (0 main launch, 1 sky kernel)");
     return RT_OK;
 }
 
@@ -148,6 +150,7 @@ int parse_options(const char *text, rt_options &o)
         else if (key == "wave_queue_rays") ok = u32(n.wave_queue_rays);
         else if (key == "diag") ok = u32(n.diag);
         else if (key == "tile_classes") ok = u32(n.tile_classes);
+        else if (key == "sky_moments") ok = u32(n.sky_moments);
         else {
             known = false;
             for (const auto &d : kDiag)

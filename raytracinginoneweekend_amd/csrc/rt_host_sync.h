@@ -27,6 +27,7 @@ hipError_t static_lds_render(int variant, int cull, size_t *bytes, bool pairs = 
 hipError_t launch_render_list(int variant, const KList &k, uint32_t grid, hipStream_t stream);
 // rt_sky.hip
 hipError_t launch_sky(const KSky &k, hipStream_t stream);
+hipError_t launch_sky_moments(const KSkyMoments &k, hipStream_t stream);
 // rt_ground.hip
 hipError_t launch_ground(int variant, const KGround &k, hipStream_t stream);
 // rt_accum.hip

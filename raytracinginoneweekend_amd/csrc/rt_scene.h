@@ -194,6 +194,9 @@ struct rt_scene {
     // the sky kernel of a pass issued alone runs beside the pass's main and deep launches, on the
     // next render stream (idle: nothing else runs); ev_sky after it
     rthost::Event ev_sky;
+    // a window whose sky_moments_kernel runs on a render stream: recorded on the
+    // caller's stream when the call begins; that kernel, which reads and writes the session's planes, waits
+    rthost::Event ev_enter;
     bool free_valid[rthost::kMaxWs] = {};
     // queue/segment counters of workspace b not known to be zero (set while a render using
     // them is enqueued, cleared once the accumulation that resets them is enqueued after it)
