@@ -18,17 +18,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "too
 import adaptive_cases as AC  # noqa: E402
 import adaptive_ref  # noqa: E402
 import progressive_ref  # noqa: E402
+from support import words as u32  # noqa: E402
 
 F = np.float32
 W, H = AC.W, AC.H
 
 
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(u32(a) if a.dtype == F else a, u32(b) if b.dtype == F else b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(u32(a), u32(b))
 
 
 # ---- the restatement -------------------------------------------------------------------------------

@@ -21,6 +21,7 @@ import adaptive_ref  # noqa: E402
 import progressive_ref  # noqa: E402
 import test_variance_gpu as TV  # noqa: E402
 from motion_cases import huge_a_b  # noqa: E402
+from support import assert_all_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +29,6 @@ F = np.float32
 W, H, SPP, SEED = AC.W, AC.H, AC.SPP, AC.SEED
 SENTINEL = dict(rgb=F(-7.0), var=F(-7.0), rgb8=np.uint8(77), samples=np.uint32(0x2BCD1234))
 PLANES = ("rgb", "var", "rgb8", "samples")
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 class Outs:
@@ -80,11 +77,7 @@ def run_adaptive(ds, cam, p, ap, windows, session=None):
 
 
 def assert_step(g, r, what):
-    for name in PLANES:
-        a, b = g[name], r[name]
-        bad = int(np.count_nonzero(u32(a) != u32(b))) if a.dtype == F else int(np.count_nonzero(a != b))
-        print(what, name, "mismatching values:", bad, "of", b.size)
-        assert a.shape == b.shape and a.dtype == b.dtype and bad == 0, f"{what}: {name}"
+    assert_all_bits(g, r, what, PLANES)
     print(what, "noisy:", g["noisy"], "expected", r["noisy"], "active:", g["info"]["active_blocks"], "expected", r["active_blocks"])
     assert g["noisy"] == r["noisy"], f"{what}: noise count"
     assert np.array_equal(g["d_b"], r["d_b"]), f"{what}: rt_adaptive_blocks"

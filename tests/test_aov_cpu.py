@@ -16,10 +16,7 @@ from raytracinginoneweekend_amd import _abi as abi
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import aov_ref  # noqa: E402
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+from support import assert_bits, words as u32  # noqa: E402
 
 
 def bubble_camera(mode):
@@ -151,8 +148,8 @@ def test_reference_rows_and_sample_prefix():
     part = aov_ref.render(s, m, cam, rt.make_params(W, H, 4, 64, 1234, row_offset=1, row_stride=2))
     full = aov_ref.render(s, m, cam, rt.make_params(W, H, 4, 64, 1234, row_offset=1, row_stride=2, full_frame=True))
     for n in abi.AOV_PLANES:
-        assert np.array_equal(u32(part[n]), u32(whole[n][1::2])), n
-        assert np.array_equal(u32(full[n][1::2]), u32(whole[n][1::2])), n
+        assert_bits(part[n], whole[n][1::2], n)
+        assert_bits(full[n][1::2], whole[n][1::2], n)
         assert (full[n][0::2] == abi.AOV_PLANES[n][2]).all(), n
     pre = aov_ref.render(s, m, cam, rt.make_params(W, H, 8, 64, 1234), samples=3)
     own = aov_ref.render(s, m, cam, rt.make_params(W, H, 3, 64, 1234))

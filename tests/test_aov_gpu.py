@@ -17,6 +17,7 @@ from raytracinginoneweekend_amd import _abi as abi
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import aov_ref  # noqa: E402
+from support import assert_all_bits, assert_bits, words as u32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -24,18 +25,8 @@ PLANES = tuple(abi.AOV_PLANES)
 SEED = 1234
 
 
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def mismatches(got, ref, planes=PLANES):
-    return {n: int(np.count_nonzero(u32(got[n]) != u32(ref[n]))) for n in planes}
-
-
 def assert_same(got, ref, planes=PLANES):
-    bad = mismatches(got, ref, planes)
-    print("mismatching values per plane:", bad)
-    assert not any(bad.values()), bad
+    assert_all_bits(got, ref, "planes", planes)
 
 
 @functools.lru_cache(maxsize=None)
@@ -256,7 +247,7 @@ def test_ordered_between_beauty_frames_in_flight(case_gpu):
     host = buf.cpu().numpy().view(np.uint32)
     assert_same({n: _plane(host, at, words, n, H, W) for n in PLANES}, case_gpu[4])
     for f, ref in zip(frames, alone):
-        assert np.array_equal(u32(f.cpu().numpy()), u32(ref))
+        assert_bits(f.cpu().numpy(), ref)
 
 
 def test_stats_of_the_host_call():
@@ -274,4 +265,4 @@ def test_stats_of_the_host_call():
     assert st.primaries == st.segments == W * rows * samples
     assert st.sphere_tests == 0 and st.box_tests == 0 and st.kernel_ms > 0 and st.wall_ms >= st.kernel_ms
     ref = aov_ref.render(s, m, cam, p, samples)
-    assert np.array_equal(u32(depth), u32(ref["depth"]))
+    assert_bits(depth, ref["depth"])

@@ -18,12 +18,9 @@ from raytracinginoneweekend_amd import _abi as abi
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import aov_ref  # noqa: E402
 import denoise_ref  # noqa: E402
+from support import assert_bits, synthetic_planes, words as u32  # noqa: E402
 
 F = np.float32
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- records -------------------------------------------------------------------------------------
@@ -156,13 +153,8 @@ def test_python_wrapper_checks_shapes_and_dtypes():
 
 # ---- properties of the reference ---------------------------------------------------------------------
 def _random_planes(w, h, seed):
-    g = np.random.default_rng(seed)
-    beauty = g.random((h, w, 3), dtype=np.float32)
-    n = g.standard_normal((h, w, 3)).astype(np.float32)
-    normal = (n / np.sqrt((n * n).sum(-1, keepdims=True))).astype(np.float32)
-    depth = (g.random((h, w), dtype=np.float32) * F(4)).astype(np.float32)
-    albedo = g.random((h, w, 3), dtype=np.float32)
-    return beauty, albedo, normal, depth
+    p = synthetic_planes(w, h, seed=seed)
+    return tuple(p[n] for n in ("beauty", "albedo", "normal", "depth"))
 
 
 def test_reference_single_pixel_is_the_centre_tap_chain():
@@ -179,7 +171,7 @@ def test_reference_single_pixel_is_the_centre_tap_chain():
     for _ in range(3):
         c = (k * c) / k
     out, _ = denoise_ref.denoise(beauty, albedo, normal, depth, 3, 1.0, 1.0, 1.0, 1.0, True)
-    assert np.array_equal(u32(out), u32(c * a1))
+    assert_bits(out, c * a1)
 
 
 def test_reference_taps_beyond_the_image_are_skipped():
@@ -192,7 +184,7 @@ def test_reference_taps_beyond_the_image_are_skipped():
     two, c2 = denoise_ref.denoise(beauty, albedo, normal, depth, 2, *sig)
     three, c3 = denoise_ref.denoise(beauty, albedo, normal, depth, 3, *sig)
     k = F(0.375) * F(0.375)
-    assert np.array_equal(u32(three[:, 1:4]), u32(((k * two) / k)[:, 1:4]))
+    assert_bits(three[:, 1:4], ((k * two) / k)[:, 1:4])
 
     def d2(a, b):
         d = a - b
@@ -214,7 +206,7 @@ def test_reference_taps_beyond_the_image_are_skipped():
             sumw = (F(0) + first[0]) + second[0]
             acc = (F(0) + first[0] * two[y, first[1]]) + second[0] * two[y, second[1]]
             assert isinstance(w, np.float32) and acc.dtype == np.float32
-            assert np.array_equal(u32(three[y, x]), u32(acc / sumw)), (y, x)
+            assert_bits(three[y, x], acc / sumw, (y, x))
     # the last level adds those 6 taps to the census and no other
     assert sum(c3) == sum(c2) + 6 and sum(c2) > 0
 
@@ -244,7 +236,7 @@ def _plain_b3(img, levels):
 def test_reference_without_terms_is_the_plain_b3_blur():
     beauty, albedo, _, _ = _random_planes(7, 6, 3)
     out, census = denoise_ref.denoise(beauty, albedo, None, None, 2, 0.0, 0.0, 0.0, 0.0)
-    assert np.array_equal(u32(out), u32(_plain_b3(beauty, 2)))
+    assert_bits(out, _plain_b3(beauty, 2))
     assert census[0] == 0 and census[1] == 0 and census[2] > 0
 
 

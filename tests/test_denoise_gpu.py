@@ -18,6 +18,7 @@ from raytracinginoneweekend_amd import _abi as abi
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import denoise_ref  # noqa: E402
+from support import assert_bits as assert_same, synthetic_planes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,36 +28,7 @@ KERNELS = pytest.mark.parametrize("direct", [False, True], ids=["tiled", "direct
 GUIDES = ("albedo", "normal", "depth")
 
 
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same(got, ref):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print("mismatching values:", bad, "of", ref.size)
-    assert got.shape == ref.shape and got.dtype == np.float32 and bad == 0
-
-
-@functools.lru_cache(maxsize=None)
-def synthetic(w, h, block=False):
-    """Seeded random planes: beauty in [0, 1), unit normals, depth in [0, 4), albedo in [0, 1);
-    block: the left half carries one colour and sky-like guides (normal 0, depth 0, one albedo)."""
-    g = np.random.default_rng(w * 1000 + h)
-    beauty = g.random((h, w, 3), dtype=np.float32)
-    n = g.standard_normal((h, w, 3)).astype(np.float32)
-    normal = (n / np.sqrt((n * n).sum(-1, keepdims=True))).astype(np.float32)
-    depth = (g.random((h, w), dtype=np.float32) * F(4)).astype(np.float32)
-    albedo = g.random((h, w, 3), dtype=np.float32)
-    if block:
-        half = w // 2
-        beauty[:, :half] = (F(0.25), F(0.5), F(0.75))
-        albedo[:, :half] = (F(0.5), F(0.625), F(0.75))
-        normal[:, :half] = 0
-        depth[:, :half] = 0
-    planes = dict(beauty=beauty, albedo=albedo, normal=normal, depth=depth)
-    for a in planes.values():
-        a.setflags(write=False)
-    return planes
+synthetic = functools.lru_cache(maxsize=None)(synthetic_planes)  # (w, h, block=False), once per module
 
 
 _REFS = {}

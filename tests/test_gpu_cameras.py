@@ -25,6 +25,7 @@ from raytracinginoneweekend_amd import _abi as abi
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import camera_cases as CC  # noqa: E402
+from support import assert_all_bits, assert_bits, words as u32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -34,16 +35,6 @@ VARIANTS = {"ieee_roots": {"ieee_roots": True}, "no_sky": {"no_sky": True}, "nat
             "transpose0": {"transpose_max": 0}, "no_shortcut": {"no_shortcut": True},
             "deep": {"deep_split": 3, "deep_min_items": 0}}
 SENTINEL = 0x5a5a5a5a
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_bits(got, ref, what=""):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(f"{what}: {bad} of {u32(ref).size} values differ")
-    assert bad == 0, f"{what}: {bad} of {u32(ref).size} values differ"
 
 
 _default = {}
@@ -99,13 +90,12 @@ def test_feature_buffers_match_reference(name):
     """aov_kernel has its own copy of the range gate and of the sky blocks: all five planes."""
     ref = CC.aov_reference(name)
     got = rt.render_aov(CC.scene(name), CC.params(name), CC.case(name).camera)
-    bad = {n: int(np.count_nonzero(u32(got[n]) != u32(ref[n]))) for n in PLANES}
-    print(f"{name}: mismatching values per plane: {bad}")
-    assert not any(bad.values()), bad
+    assert_all_bits(got, ref, name, PLANES)
 
 
 def _render_device(name, p, rows, options=None, events=False):
-    """The case through rt_render_device into a sentinel-filled buffer of `rows` rows."""
+    """The case through rt_render_device into a buffer of `rows` rows filled with an integer sentinel,
+    read back as its words: the float32 references are compared as u32(ref), the same bytes."""
     import torch
     c = CC.case(name)
     out = torch.full((rows, c.W, 3), SENTINEL, dtype=torch.int32, device="cuda:0")
@@ -128,7 +118,7 @@ def test_materials_instrumented_witness():
                              rt.options(rt.default_options(), stats=True), events=True)
     print("events:", {k: ev[k] for k in ("metal_absorb", "dielectric", "lambert", "hit", "sky")})
     assert ev["metal_absorb"] > 0 and ev["dielectric"] > 0, ev
-    assert_bits(got, CC.beauty_ref("materials")[0], "materials instrumented")
+    assert_bits(got, u32(CC.beauty_ref("materials")[0]), "materials instrumented")
 
 
 def test_share_rows():
@@ -143,7 +133,7 @@ def test_share_rows():
     assert_bits(img, ref, "share packed")
     assert seg == ref_seg
     full, _ = _render_device("share", CC.params("share", full_frame=True), c.H)
-    assert_bits(full[rows], ref, "share full frame, its rows")
+    assert_bits(full[rows], u32(ref), "share full frame, its rows")
     other = np.ones(c.H, dtype=bool)
     other[rows] = False
     assert (full[other] == SENTINEL).all()

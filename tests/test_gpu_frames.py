@@ -9,6 +9,7 @@ texels (device pow vs glibc powf).
 import hashlib
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -18,14 +19,10 @@ import oracle_binding as O
 import raytracinginoneweekend_amd as rt
 from raytracinginoneweekend_amd import _abi as abi
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+from support import assert_bits as _bits_equal  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-
-
-def _bits_equal(a, b, what=""):
-    a = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-    b = np.ascontiguousarray(b, dtype=np.float32).view(np.uint32)
-    bad = np.count_nonzero(a != b)
-    assert bad == 0, f"{what}: {bad} of {a.size} values differ"
 
 
 def _u8_close(a, b):

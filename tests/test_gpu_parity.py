@@ -6,6 +6,9 @@ linear f32 framebuffer must match bitwise (0 ULP). The u8 epilogue evaluates pow
 double pow; glibc's powf can differ in its last bit, so u8 may differ by 1 LSB on a handful
 of texels (bound asserted below), never more.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
@@ -13,6 +16,9 @@ import golden_io as G
 import oracle_binding as O
 import raytracinginoneweekend_amd as rt
 from raytracinginoneweekend_amd import _abi as abi
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+from support import assert_bits as _bits_equal  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -28,14 +34,6 @@ VARIANTS = {"clustered": {}, "clustered0": {"_opts": {"transpose_max": 0}}, "bru
 def _params(meta, **kw):
     return rt.make_params(meta["width"], meta["height"], meta["spp"], meta["depth"], meta["seed"],
                           meta["row_offset"], meta["row_stride"], meta["num_rows"], **kw)
-
-
-def _bits_equal(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-    b = np.ascontiguousarray(b, dtype=np.float32).view(np.uint32)
-    bad = np.count_nonzero(a != b)
-    assert bad == 0, f"{bad} of {a.size} values differ; max |d| = " \
-                     f"{np.max(np.abs(a.view(np.float32) - b.view(np.float32)))}"
 
 
 @pytest.fixture(scope="module", autouse=True)

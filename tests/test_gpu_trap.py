@@ -3,6 +3,8 @@ glass ball with its cosine in the ball's window is ended at once with colour 0, 
 had run out. Every render here is at most 64x40 and is compared bit for bit with the CPU
 restatement, its segment count included, with the trigger and without it (diag no_trap_end)."""
 import functools
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -12,16 +14,12 @@ import oracle_binding as O
 import raytracinginoneweekend_amd as rt
 from raytracinginoneweekend_amd import _abi as abi
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+from support import assert_bits as _bits_equal  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 W, H = 64, 40
-
-
-def _bits_equal(a, b, what=""):
-    a = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-    b = np.ascontiguousarray(b, dtype=np.float32).view(np.uint32)
-    bad = np.count_nonzero(a != b)
-    assert bad == 0, f"{what}: {bad} of {a.size} values differ"
 
 
 def _materials():

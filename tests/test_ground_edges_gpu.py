@@ -25,7 +25,6 @@ import functools
 import os
 import sys
 
-import numpy as np
 import pytest
 
 import raytracinginoneweekend_amd as rt
@@ -35,6 +34,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "too
 import golden_io as G  # noqa: E402
 import ground_checks as GC  # noqa: E402
 import oracle_binding as O  # noqa: E402
+from support import assert_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -44,17 +44,6 @@ CAMERAS = {"reference": lambda: rt.Camera.default(W, H), "corrected": lambda: rt
 LONE_SPLIT = dict(deep_min_items=1)
 IN_FLIGHT = dict(render_streams=3, in_flight=1)
 RING = 256  # rt_scene::kRing (tests/test_ground_cpu.py pins it)
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_bits(got, ref, what):
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(f"{what}: {bad} of {u32(ref).size} values differ")
-    assert bad == 0, f"{what}: {bad} of {u32(ref).size} values differ"
 
 
 @functools.lru_cache(maxsize=None)

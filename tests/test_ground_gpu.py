@@ -23,6 +23,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "too
 import golden_io as G  # noqa: E402
 import ground_checks as GC  # noqa: E402
 import oracle_binding as O  # noqa: E402
+from support import assert_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -33,17 +34,6 @@ CAMERAS = {"reference": lambda: rt.Camera.default(W, H), "corrected": lambda: rt
 GROUND_TILES = {"reference": 20, "corrected": 15, "redo": 85}
 LONE_SPLIT = dict(deep_min_items=1)  # a lone pass of any size is split
 FAST_TOL_PIX, FAST_TOL_FRAC, FAST_TOL_MEAN = 1e-4, 0.99, 1e-4  # tests/test_gpu_parity.py
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_bits(got, ref, what):
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(f"{what}: {bad} of {u32(ref).size} values differ")
-    assert bad == 0, f"{what}: {bad} of {u32(ref).size} values differ"
 
 
 @functools.lru_cache(maxsize=None)

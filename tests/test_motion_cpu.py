@@ -17,12 +17,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "too
 import temporal_motion_ref as M  # noqa: E402
 from motion_cases import huge_a_b, huge_far_a_b, records_a_b  # noqa: E402
 import temporal_ref as T  # noqa: E402
+from support import assert_bits, words as u32  # noqa: E402
 
 F = np.float32
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def synthetic_planes(w, h, seed):
@@ -69,7 +66,7 @@ def test_equal_tables_give_the_static_restatement_bit_for_bit():
         want = T.accumulate(cur, prev, cam, prev_cam, par)
         got = M.accumulate(cur, prev, cam, prev_cam, par, table, table.copy())
         for a, b in zip(got[:3], want[:3]):
-            assert np.array_equal(u32(a), u32(b))
+            assert_bits(a, b)
         assert np.array_equal(got[3], want[3])
     kept = T.accumulate(cur, prev, cam, cam, par)[3]
     assert (kept == T.KEPT).sum() > w * h // 2 and (kept == T.EDGE).sum() == w
@@ -120,7 +117,7 @@ def test_one_pixel_shift():
     assert np.abs(hist - (xs[:, 1:, None] - 1)).max() < 0.05
     # the left column: off-screen, or nothing but a sliver of column 0 (weight ~1e-4 < 0.01)
     assert not (reason[:, 0] == M.KEPT).any()
-    assert np.array_equal(u32(c[:, 0]), u32(cur["beauty"][:, 0]))
+    assert_bits(c[:, 0], cur["beauty"][:, 0])
     # the static stage on the same planes keeps every pixel at its own column: the motion matters
     cs = T.accumulate(cur, prev, cam, cam, par)[0]
     assert (u32(cs) != u32(c)).any(axis=2).sum() > w * h // 2

@@ -8,9 +8,7 @@ rt.temporal_device(clip=...), in the temporal stage's place on the frames the cl
 the restatement (tests/tools/preview_clip_ref.py), which starts from each frame's planes as the public
 rt_render_var and rt_render_aov calls give them.
 """
-import ctypes as C
 import functools
-import math
 import os
 import sys
 
@@ -23,15 +21,15 @@ from raytracinginoneweekend_amd import render
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import preview_clip_ref  # noqa: E402
+import device_io  # noqa: E402
+from device_io import SENTINEL, read_planes  # noqa: E402
+from support import assert_bits as assert_same, frame_planes, orbit_camera, words as u32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 W, H, SPP, MAX_DEPTH, LEVELS, FRAMES = 70, 37, 4, 8, 2, 3
 OUT_W, OUT_H = 105, 56
-POS, LOOK = (-4.0, 3.2, 5.0), (0.0, 1.0, 0.0)
-STEP_DEG = 1.5
-SENTINEL = -7.0
 DEMOD, NO_TEMPORAL = abi.RT_PREVIEW_DEMODULATE, abi.RT_PREVIEW_NO_TEMPORAL
 MOVED_IDS = (2, 3, 4)
 GUIDES = ("normal", "depth", "alpha", "sphere_id")
@@ -39,16 +37,6 @@ GUIDES = ("normal", "depth", "alpha", "sphere_id")
 
 def clip():
     return rt.temporal_clip(radius=2, gamma=1.0)
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same(got, ref, what=""):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(what, "mismatching values:", bad, "of", ref.size)
-    assert got.shape == ref.shape and got.dtype == ref.dtype and bad == 0, what
 
 
 @functools.lru_cache(maxsize=None)
@@ -66,25 +54,14 @@ def device_scene():
     return rt.DeviceScene(records(), device=0)
 
 
-@functools.lru_cache(maxsize=None)
 def camera(i, w=W, h=H):
-    """Frame i's camera: the default one turned by i steps around the vertical axis through LOOK."""
-    a = math.radians(i * STEP_DEG)
-    dx, dz = POS[0] - LOOK[0], POS[2] - LOOK[2]
-    pos = (LOOK[0] + dx * math.cos(a) + dz * math.sin(a), POS[1], LOOK[2] - dx * math.sin(a) + dz * math.cos(a))
-    focus = float(np.float32(np.linalg.norm(np.subtract(pos, LOOK).astype(F))))
-    return rt.Camera(pos, LOOK, (0, 1, 0), w / h, 42.0, 0.0625, focus, rt.CORRECTED)
+    return orbit_camera(w, h, i)
 
 
 @functools.lru_cache(maxsize=None)
 def frame(i):
     """Frame i's planes (seed 1 + i) from the public synchronous calls."""
-    p, cam = rt.make_params(W, H, SPP, MAX_DEPTH, 1 + i), camera(i)
-    beauty, variance, _ = rt.render_var(records(), p, cam)
-    planes = dict(beauty=beauty, variance=variance, **rt.render_aov(records(), p, cam, 0))
-    for a in planes.values():
-        a.setflags(write=False)
-    return planes
+    return frame_planes(records(), rt.make_params(W, H, SPP, MAX_DEPTH, 1 + i), camera(i))
 
 
 def params(flags=DEMOD, w=W, h=H):
@@ -102,38 +79,13 @@ def reference(schedule):
     return tuple(out)
 
 
-@functools.lru_cache(maxsize=None)
-def hip():
-    rt.lib()
-    return C.CDLL("libamdhip64.so.7")  # the runtime the library is linked to, already loaded
-
-
-def download(address, shape, dtype=np.float32):
-    if not address:
-        return None
-    out = np.empty(shape, dtype=dtype)
-    assert hip().hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(address), C.c_size_t(out.nbytes), C.c_int(2)) == 0
-    return out
-
-
-def read_planes(pv, w=W, h=H):
-    pl = pv.planes()
-    return {n: download(pl[n], (h, w, 3) if ch == 3 else (h, w), dt) for n, (ch, dt) in abi.PREVIEW_PLANES.items()}
-
-
 def plane(ch, dtype=None, w=W, h=H):
-    import torch
-    return torch.full((h, w, ch) if ch > 1 else (h, w), SENTINEL, dtype=dtype or torch.float32, device="cuda:0")
+    return device_io.plane(w, h, ch, dtype)
 
 
-class Images:
-    def __init__(self, w=W, h=H):
-        import torch
-        self.rgb = plane(3, w=w, h=h)
-        self.rgb8 = torch.full((h, w, 3), 77, dtype=torch.uint8, device="cuda:0")
-
-    def host(self):
-        return self.rgb.cpu().numpy(), self.rgb8.cpu().numpy()
+def Images(w=W, h=H):
+    """Sentinel-filled device images; the caller brings the stream."""
+    return device_io.Outputs(w, h, own_stream=False)
 
 
 class HandChain:

@@ -8,9 +8,7 @@ and rt_render_aov calls give them on the same GPU (their own modules prove those
 mode and is shared. The session's planes are read back with hipMemcpy from the addresses
 rt_preview_planes reports.
 """
-import ctypes as C
 import functools
-import math
 import os
 import sys
 
@@ -24,28 +22,18 @@ from raytracinginoneweekend_amd import render
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import preview_ref  # noqa: E402
 import temporal_ref  # noqa: E402
+import device_io  # noqa: E402
+from device_io import SENTINEL, Outputs, read_planes  # noqa: E402
+from support import assert_bits as assert_same, frame_planes, orbit_camera as camera, words as u32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 SCENE_SEED, SPP, MAX_DEPTH, FRAMES = 1234, 4, 8, 3
 SIZES = [(64, 36), (70, 37)]
-POS, LOOK = (-4.0, 3.2, 5.0), (0.0, 1.0, 0.0)  # the default camera's position and look-at point
-STEP_DEG = 1.5                                   # the orbit's step per frame, about the vertical axis through LOOK
-SENTINEL = -7.0
 DEMOD, FEEDBACK, NO_TEMPORAL = abi.RT_PREVIEW_DEMODULATE, abi.RT_PREVIEW_FEEDBACK, abi.RT_PREVIEW_NO_TEMPORAL
 MODES = {"plain": 0, "demodulate": DEMOD, "feedback": FEEDBACK, "both": DEMOD | FEEDBACK, "no-temporal": NO_TEMPORAL,
          "no-temporal-demodulate": NO_TEMPORAL | DEMOD}
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same(got, ref, what=""):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(what, "mismatching values:", bad, "of", ref.size)
-    assert got.shape == ref.shape and got.dtype == ref.dtype and bad == 0, what
 
 
 @functools.lru_cache(maxsize=None)
@@ -59,24 +47,9 @@ def device_scene():
 
 
 @functools.lru_cache(maxsize=None)
-def camera(w, h, i, step=STEP_DEG):
-    """Frame i's camera: the default one turned by i steps around the vertical axis through LOOK."""
-    a = math.radians(i * step)
-    dx, dz = POS[0] - LOOK[0], POS[2] - LOOK[2]
-    pos = (LOOK[0] + dx * math.cos(a) + dz * math.sin(a), POS[1], LOOK[2] - dx * math.sin(a) + dz * math.cos(a))
-    focus = float(np.float32(np.linalg.norm(np.subtract(pos, LOOK).astype(F))))
-    return rt.Camera(pos, LOOK, (0, 1, 0), w / h, 42.0, 0.0625, focus, rt.CORRECTED)
-
-
-@functools.lru_cache(maxsize=None)
 def frame(w, h, i):
     """Frame i's planes (seed 1 + i) from the public synchronous calls."""
-    p, cam = rt.make_params(w, h, SPP, MAX_DEPTH, 1 + i), camera(w, h, i)
-    beauty, variance, _ = rt.render_var(scene(), p, cam)
-    planes = dict(beauty=beauty, variance=variance, **rt.render_aov(scene(), p, cam, 0))
-    for a in planes.values():
-        a.setflags(write=False)
-    return planes
+    return frame_planes(scene(), rt.make_params(w, h, SPP, MAX_DEPTH, 1 + i), camera(w, h, i))
 
 
 def params(w, h, flags, levels=2):
@@ -88,45 +61,6 @@ def reference(w, h, flags, levels):
     """The restatement's three frames of a mode, once."""
     s = preview_ref.Session(params(w, h, flags, levels))
     return tuple(s.frame(frame(w, h, i), camera(w, h, i)) for i in range(FRAMES))
-
-
-@functools.lru_cache(maxsize=None)
-def hip():
-    rt.lib()
-    return C.CDLL("libamdhip64.so.7")  # the runtime the library is linked to, already loaded
-
-
-def download(address, shape, dtype=np.float32):
-    """The device plane at `address` (the stream that wrote it is synchronised)."""
-    if not address:
-        return None
-    out = np.empty(shape, dtype=dtype)
-    rc = hip().hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(address), C.c_size_t(out.nbytes), C.c_int(2))
-    assert rc == 0, f"hipMemcpy device to host: {rc}"
-    return out
-
-
-def read_planes(pv, w, h):
-    pl = pv.planes()
-    return {n: download(pl[n], (h, w, 3) if ch == 3 else (h, w), dt) for n, (ch, dt) in abi.PREVIEW_PLANES.items()}
-
-
-class Outputs:
-    """Sentinel-filled device outputs of a frame call and a stream of their own."""
-
-    def __init__(self, w, h, f32=True, u8=True):
-        import torch
-        self.rgb = torch.full((h, w, 3), SENTINEL, dtype=torch.float32, device="cuda:0") if f32 else None
-        self.rgb8 = torch.full((h, w, 3), 77, dtype=torch.uint8, device="cuda:0") if u8 else None
-        torch.cuda.synchronize()
-        self.stream = torch.cuda.Stream()
-
-    def frame(self, pv, cam, seed):
-        pv.frame(cam, seed, self.rgb.data_ptr() if self.rgb is not None else None,
-                 self.rgb8.data_ptr() if self.rgb8 is not None else None, self.stream.cuda_stream)
-        self.stream.synchronize()
-        return (self.rgb.cpu().numpy() if self.rgb is not None else None,
-                self.rgb8.cpu().numpy() if self.rgb8 is not None else None)
 
 
 def session_frames(w, h, flags, levels, order=range(FRAMES), f32=True, u8=True):
@@ -155,10 +89,7 @@ def test_chain_equality(w, h):
     import torch
     got = session_frames(w, h, 0, 2)
     ds, p = device_scene(), params(w, h, 0, 2)
-
-    def plane(ch, dtype=torch.float32):
-        return torch.full((h, w, ch) if ch > 1 else (h, w), SENTINEL, dtype=dtype, device="cuda:0")
-
+    plane = functools.partial(device_io.plane, w, h)
     beauty, variance, albedo, alpha = plane(3), plane(1), plane(3), plane(1)
     g = [dict(normal=plane(3), depth=plane(1), sphere_id=plane(1, torch.int32)) for _ in range(2)]
     hist = [dict(color=plane(3), variance=plane(1), history=plane(1)) for _ in range(2)]

@@ -6,8 +6,9 @@ after two updates or an appearance update; the session's bytes; a scene that is 
 64 x 36, 4 spp, 2 levels, max_depth 8, a static corrected camera, the huge scene with spheres 2, 3 and
 4 moving. Every comparison is on uint32 (or uint8) views with zero mismatches allowed.
 """
-import ctypes as C
 import functools
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -16,24 +17,18 @@ import raytracinginoneweekend_amd as rt
 from raytracinginoneweekend_amd import _abi as abi
 from raytracinginoneweekend_amd import render
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import device_io  # noqa: E402
+from device_io import SENTINEL, read_planes  # noqa: E402
+from support import assert_bits as assert_same  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 W, H, SPP, MAX_DEPTH, LEVELS = 64, 36, 4, 8, 2
-SENTINEL = -7.0
 DEMOD = abi.RT_PREVIEW_DEMODULATE
 MOVED_IDS = (2, 3, 4)
 GUIDES = ("normal", "depth", "alpha", "sphere_id")
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same(got, ref, what=""):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(what, "mismatching values:", bad, "of", ref.size)
-    assert got.shape == ref.shape and got.dtype == ref.dtype and bad == 0, what
 
 
 @functools.lru_cache(maxsize=None)
@@ -56,38 +51,13 @@ def params(flags, w=W, h=H):
     return rt.preview_params(w, h, SPP, flags=flags, max_depth=MAX_DEPTH, denoise=dict(levels=LEVELS))
 
 
-@functools.lru_cache(maxsize=None)
-def hip():
-    rt.lib()
-    return C.CDLL("libamdhip64.so.7")
-
-
-def download(address, shape, dtype=np.float32):
-    if not address:
-        return None
-    out = np.empty(shape, dtype=dtype)
-    assert hip().hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(address), C.c_size_t(out.nbytes), C.c_int(2)) == 0
-    return out
-
-
-def read_planes(pv, w=W, h=H):
-    pl = pv.planes()
-    return {n: download(pl[n], (h, w, 3) if ch == 3 else (h, w), dt) for n, (ch, dt) in abi.PREVIEW_PLANES.items()}
-
-
 def plane(ch, dtype=None, w=W, h=H):
-    import torch
-    return torch.full((h, w, ch) if ch > 1 else (h, w), SENTINEL, dtype=dtype or torch.float32, device="cuda:0")
+    return device_io.plane(w, h, ch, dtype)
 
 
-class Images:
-    def __init__(self, w=W, h=H):
-        import torch
-        self.rgb = plane(3, w=w, h=h)
-        self.rgb8 = torch.full((h, w, 3), 77, dtype=torch.uint8, device="cuda:0")
-
-    def host(self):
-        return self.rgb.cpu().numpy(), self.rgb8.cpu().numpy()
+def Images(w=W, h=H):
+    """Sentinel-filled device images; the caller brings the stream."""
+    return device_io.Outputs(w, h, own_stream=False)
 
 
 class HandChain:
@@ -155,7 +125,7 @@ class HandChain:
 def session_frame(pv, img, seed, stream):
     pv.frame(camera(), seed, img.rgb.data_ptr(), img.rgb8.data_ptr(), stream.cuda_stream)
     stream.synchronize()
-    return (*img.host(), read_planes(pv))
+    return (*img.host(), read_planes(pv, W, H))
 
 
 def assert_frame(got, want, what):

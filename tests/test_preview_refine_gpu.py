@@ -24,25 +24,17 @@ import moments_ref  # noqa: E402
 import preview_ref  # noqa: E402
 import progressive_ref  # noqa: E402
 from motion_cases import huge_a_b  # noqa: E402
+import device_io  # noqa: E402
+from device_io import Outputs  # noqa: E402
+from support import assert_bits as assert_same, words as u32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 W, H, SPP, MAX_DEPTH, TOTAL = 64, 36, 4, 8, 16
 CALLS = (4, 4, 8)
-SENTINEL = -7.0
 DEMOD, FEEDBACK = abi.RT_PREVIEW_DEMODULATE, abi.RT_PREVIEW_FEEDBACK
 MODES = {"plain": 0, "demodulate": DEMOD, "both": DEMOD | FEEDBACK}
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same(got, ref, what=""):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(what, "mismatching values:", bad, "of", ref.size)
-    assert got.shape == ref.shape and got.dtype == ref.dtype and bad == 0, what
 
 
 @functools.lru_cache(maxsize=None)
@@ -94,20 +86,6 @@ def expected(flags, seed, mode=rt.CORRECTED, total=TOTAL, calls=CALLS, which="a"
     return out
 
 
-class Outputs:
-    def __init__(self):
-        import torch
-        self.rgb = torch.full((H, W, 3), SENTINEL, dtype=torch.float32, device="cuda:0")
-        self.rgb8 = torch.full((H, W, 3), 77, dtype=torch.uint8, device="cuda:0")
-        torch.cuda.synchronize()
-        self.stream = torch.cuda.Stream()
-
-    def refine(self, pv, cam, seed, total, n):
-        pv.refine(cam, seed, total, n, self.rgb.data_ptr(), self.rgb8.data_ptr(), self.stream.cuda_stream)
-        self.stream.synchronize()
-        return self.rgb.cpu().numpy(), self.rgb8.cpu().numpy()
-
-
 @pytest.mark.parametrize("mode", sorted(MODES))
 def test_every_call_is_the_stages_by_hand_and_the_restatement(mode):
     import torch
@@ -116,14 +94,11 @@ def test_every_call_is_the_stages_by_hand_and_the_restatement(mode):
     p, rp = params(flags), frame_params(seed)
     exact, _ = rt.render_f32(records(), rp, cam)
     ds = rt.DeviceScene(records(), device=0)
-
-    def plane(ch, dtype=torch.float32):
-        return torch.full((H, W, ch) if ch > 1 else (H, W), SENTINEL, dtype=dtype, device="cuda:0")
-
+    plane = functools.partial(device_io.plane, W, H)
     try:
         pv = ds.preview(p)
         before = pv.usage()
-        out = Outputs()
+        out = Outputs(W, H)
         # the chain by hand: a progressive session and planes of the caller's
         st = torch.cuda.Stream()
         pg = ds.progressive(cam, rp)
@@ -173,7 +148,7 @@ def test_what_restarts_a_refinement():
     ds = rt.DeviceScene(records(), device=0)
     try:
         pv = ds.preview(params(flags))
-        out = Outputs()
+        out = Outputs(W, H)
         cam, other = camera(), camera(rt.REFERENCE)
         rgb, _ = out.refine(pv, cam, 5, TOTAL, 4)
         assert_same(rgb, expected(flags, 5)[0], "the first call")
@@ -191,7 +166,7 @@ def test_what_restarts_a_refinement():
         assert_same(rgb, expected(flags, 6, rt.REFERENCE, 8, (4,))[0], "another total")
         # a frame call in between: the refinement starts again, and that frame had no history
         rgb, _ = out.refine(pv, cam, 5, TOTAL, 4)
-        frame = Outputs()
+        frame = Outputs(W, H)
         pv.frame(cam, 9, frame.rgb.data_ptr(), frame.rgb8.data_ptr(), frame.stream.cuda_stream)
         frame.stream.synchronize()
         assert pv.planes()["frames"] == 1 and pv.refine_info() == (0, 0)
@@ -229,7 +204,7 @@ def test_an_upscaled_session_does_not_refine():
     try:
         p = rt.preview_params(32, 18, SPP, max_depth=MAX_DEPTH)
         pv = ds.preview(p, rt.preview_upscale(p, W, H))
-        out = Outputs()
+        out = Outputs(W, H)
         with pytest.raises(rt.RtError) as e:
             pv.refine(camera(), 5, TOTAL, 4, out.rgb.data_ptr(), None, out.stream.cuda_stream)
         assert e.value.status == abi.RT_ERR_UNSUPPORTED and "upscaled" in str(e.value)

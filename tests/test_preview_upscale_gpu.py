@@ -13,9 +13,7 @@ FEEDBACK too: the first level of that run is the run that made C_1, V_1; the mod
 reconstruction against the ordinary session's own image); then rt_render_aov_device at the output
 size, rt_upsample_device and rt_preview_merge_device.
 """
-import ctypes as C
 import functools
-import math
 import os
 import sys
 
@@ -26,27 +24,18 @@ import raytracinginoneweekend_amd as rt
 from raytracinginoneweekend_amd import _abi as abi
 from raytracinginoneweekend_amd import render
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+from device_io import SENTINEL, Outputs, plane, read_planes  # noqa: E402
+from support import assert_bits as assert_same, frozen, orbit_camera as camera, words as u32  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 SCENE_SEED, SPP, MAX_DEPTH, FRAMES = 1234, 4, 8, 3
 SIZES = [(32, 18, 64, 36), (35, 19, 70, 37)]
-POS, LOOK = (-4.0, 3.2, 5.0), (0.0, 1.0, 0.0)
-STEP_DEG = 1.5
-SENTINEL = -7.0
 DEMOD, FEEDBACK, NO_TEMPORAL = abi.RT_PREVIEW_DEMODULATE, abi.RT_PREVIEW_FEEDBACK, abi.RT_PREVIEW_NO_TEMPORAL
 MODES = {"plain": 0, "demodulate": DEMOD, "demodulate-feedback": DEMOD | FEEDBACK, "no-temporal": NO_TEMPORAL}
 GUIDES = ("normal", "depth", "alpha", "sphere_id")
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same(got, ref, what=""):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(what, "mismatching values:", bad, "of", ref.size)
-    assert got.shape == ref.shape and got.dtype == ref.dtype and bad == 0, what
 
 
 @functools.lru_cache(maxsize=None)
@@ -60,70 +49,21 @@ def device_scene():
 
 
 @functools.lru_cache(maxsize=None)
-def camera(w, h, i):
-    """Frame i's camera: the default one turned by i steps around the vertical axis through LOOK."""
-    a = math.radians(i * STEP_DEG)
-    dx, dz = POS[0] - LOOK[0], POS[2] - LOOK[2]
-    pos = (LOOK[0] + dx * math.cos(a) + dz * math.sin(a), POS[1], LOOK[2] - dx * math.sin(a) + dz * math.cos(a))
-    focus = float(np.float32(np.linalg.norm(np.subtract(pos, LOOK).astype(F))))
-    return rt.Camera(pos, LOOK, (0, 1, 0), w / h, 42.0, 0.0625, focus, rt.CORRECTED)
-
-
-@functools.lru_cache(maxsize=None)
 def output_guides(w, h, i, samples=0):
     """The feature buffers of the output size from the public synchronous call, once."""
-    g = rt.render_aov(scene(), rt.make_params(w, h, SPP, MAX_DEPTH, 1 + i), camera(w, h, i), samples)
-    for a in g.values():
-        a.setflags(write=False)
-    return g
+    return frozen(rt.render_aov(scene(), rt.make_params(w, h, SPP, MAX_DEPTH, 1 + i), camera(w, h, i), samples))
 
 
 def params(w, h, flags, levels=2):
     return rt.preview_params(w, h, SPP, flags=flags, max_depth=MAX_DEPTH, denoise=dict(levels=levels))
 
 
-@functools.lru_cache(maxsize=None)
-def hip():
-    rt.lib()
-    return C.CDLL("libamdhip64.so.7")  # the runtime the library is linked to, already loaded
-
-
-def download(address, shape, dtype=np.float32):
-    """The device plane at `address` (the stream that wrote it is synchronised)."""
-    if not address:
-        return None
-    out = np.empty(shape, dtype=dtype)
-    rc = hip().hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(address), C.c_size_t(out.nbytes), C.c_int(2))
-    assert rc == 0, f"hipMemcpy device to host: {rc}"
-    return out
-
-
-def read_planes(pv, w, h):
-    pl = pv.planes()
-    return {n: download(pl[n], (h, w, 3) if ch == 3 else (h, w), dt) for n, (ch, dt) in abi.PREVIEW_PLANES.items()}
-
-
 def read_output(pv):
     o = pv.output()
-    w, h = o["width"], o["height"]
-    return {n: download(o[n], (h, w, 3) if ch == 3 else (h, w), dt) for n, (ch, dt) in abi.PREVIEW_OUTPUT_PLANES.items()}
+    return read_planes(pv, o["width"], o["height"], abi.PREVIEW_OUTPUT_PLANES, o)
 
 
-def plane(w, h, ch, dtype=None):
-    import torch
-    return torch.full((h, w, ch) if ch > 1 else (h, w), SENTINEL, dtype=dtype or torch.float32, device="cuda:0")
-
-
-class Images:
-    """Sentinel-filled device images of a frame call."""
-
-    def __init__(self, w, h):
-        import torch
-        self.rgb = plane(w, h, 3)
-        self.rgb8 = torch.full((h, w, 3), 77, dtype=torch.uint8, device="cuda:0")
-
-    def host(self):
-        return self.rgb.cpu().numpy(), self.rgb8.cpu().numpy()
+Images = functools.partial(Outputs, own_stream=False)  # the caller brings the stream
 
 
 def expected_usage(lw, lh, w, h, flags, levels):

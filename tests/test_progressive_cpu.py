@@ -18,15 +18,12 @@ from raytracinginoneweekend_amd import _abi as abi
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import moments_ref  # noqa: E402
 import progressive_ref  # noqa: E402
+from support import assert_bits, words as u32  # noqa: E402
 
 F = np.float32
 SEED = 1234
 W, H = 64, 36
 _FRAMES = {}
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def frame(w, h, spp):
@@ -74,7 +71,7 @@ def test_carried_moments_are_the_prefixes_variance():
     """The moments carried window by window against moments_ref.variance over each whole prefix."""
     _, _, samples = frame(W, H, 23)
     for est, d in zip(progressive_ref.run(samples, (4, 8, 11)), (4, 12, 23)):
-        assert np.array_equal(u32(est["var"]), u32(moments_ref.variance(samples[:, :, :d]))), d
+        assert_bits(est["var"], moments_ref.variance(samples[:, :, :d]), d)
 
 
 def test_noise_count_of_the_restatement():
@@ -91,7 +88,7 @@ def test_texel_of_the_restatement_is_the_goldens():
     est = progressive_ref.run(samples, (4,))[0]
     gold = np.fromfile(os.path.join(G.GOLDEN, "huge_64x36_s4.f32"), dtype=F).reshape(H, W, 3)
     gold8 = np.fromfile(os.path.join(G.GOLDEN, "huge_64x36_s4.u8"), dtype=np.uint8).reshape(H, W, 3)
-    assert np.array_equal(u32(est["rgb"]), u32(gold))
+    assert_bits(est["rgb"], gold)
     assert np.array_equal(est["rgb8"], gold8)
 
 

@@ -20,6 +20,7 @@ import moments_ref  # noqa: E402
 import progressive_ref  # noqa: E402
 import test_variance_gpu as TV  # noqa: E402  (its scenes and the plan variants of its render)
 from motion_cases import huge_a_b  # noqa: E402
+from support import assert_all_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +31,6 @@ SENTINEL = dict(rgb=F(-7.0), var=F(-7.0), rgb8=np.uint8(77))
 CAMERAS = TV.CAMERAS
 scene = TV.scene
 _SAMPLES = {}
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def samples_of(scene_name, w, h, spp, mode, seed=SEED, records=None, **kw):
@@ -68,11 +65,7 @@ class Outs:
 
 
 def assert_estimate(got, want, what):
-    for name in ("rgb", "var", "rgb8"):
-        g, r = got[name], want[name]
-        bad = int(np.count_nonzero(u32(g) != u32(r))) if g.dtype == F else int(np.count_nonzero(g != r))
-        print(what, name, "mismatching values:", bad, "of", r.size)
-        assert g.shape == r.shape and g.dtype == r.dtype and bad == 0, f"{what}: {name}"
+    assert_all_bits(got, want, what, ("rgb", "var", "rgb8"))
     print(what, "noisy:", got["noisy"], "expected", want["noisy"])
     assert got["noisy"] == want["noisy"], f"{what}: noise count"
 

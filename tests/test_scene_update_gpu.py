@@ -6,8 +6,6 @@ The simple scene's pair of records is tests/tools/motion_cases.py's, whose CPU t
 trap windows and the dealing order differ between A and B, so the equality here rests on re-derived
 tables. Sizes 64 x 40 (whole 64-pixel blocks: a classified order) and 48 x 27 (the natural order).
 """
-import ctypes as C
-import functools
 import os
 import sys
 
@@ -19,6 +17,8 @@ from raytracinginoneweekend_amd import _abi as abi
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 from motion_cases import huge_a_b, huge_far_a_b, records_a_b  # noqa: E402
+from device_io import download  # noqa: E402
+from support import assert_all_bits, assert_bits, words as u32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +26,6 @@ F = np.float32
 SPP = 4
 SIZES = ((64, 40), (48, 27))
 AOV = tuple(abi.AOV_PLANES)
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def everything(ds, w, h, brute=True):
@@ -62,18 +58,17 @@ def everything(ds, w, h, brute=True):
     for n, a in planes.items():
         out["aov " + n] = a.cpu().numpy()
     perm, n_lead, n_sky = ds.tile_order(cam, p, st.cuda_stream)
-    out["tile_order perm"], out["tile_order counts"] = perm, np.array([n_lead, n_sky])
+    out["tile_order perm"], out["tile_order counts"] = perm, np.array([n_lead, n_sky], dtype=np.uint32)
     usage = ds.usage()
-    out["usage"] = np.array([usage["lead_tiles"], usage["sky_tiles"], usage["device_bytes"] - usage["workspace_bytes"]])
+    out["usage"] = np.array([usage["lead_tiles"], usage["sky_tiles"], usage["device_bytes"] - usage["workspace_bytes"]],
+                            dtype=np.uint32)  # (4-byte words: the comparer takes no others)
     return out
 
 
 def assert_equal_outputs(got, want, what):
     assert sorted(got) == sorted(want)
+    assert_all_bits(got, want, what)
     for n in want:
-        bad = int(np.count_nonzero(u32(got[n]) != u32(want[n]))) if got[n].shape == want[n].shape else -1
-        print(what, n, "mismatching values:", bad, "of", want[n].size)
-        assert bad == 0, f"{what}: {n}"
         assert not (got[n].dtype == np.float32 and (got[n] == -7.0).any()), f"{what}: {n} holds a sentinel"
 
 
@@ -140,19 +135,11 @@ def test_identical_update_is_free():
     torch.cuda.synchronize()
     c1 = sc.order_counts()
     assert c1["hits"] == c0["hits"] + 1 and c1["host_orders"] == c0["host_orders"] and c1["device_orders"] == c0["device_orders"]
-    assert np.array_equal(u32(rgb.cpu().numpy()), u32(first))
+    assert_bits(rgb.cpu().numpy(), first)
     sc.close()
 
 
 # ---- 4: epochs and tables ----------------------------------------------------------------------------------
-def download(address, n):
-    out = np.empty((n, 4), dtype=F)
-    rt.lib()
-    hip = C.CDLL("libamdhip64.so.7")
-    assert hip.hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(address), C.c_size_t(out.nbytes), C.c_int(2)) == 0
-    return out
-
-
 def test_epochs_and_tables():
     (s, m), _ = records_a_b()
     sc = rt.DeviceScene((s, m))
@@ -160,14 +147,14 @@ def test_epochs_and_tables():
     m0 = sc.motion()
     assert m0["n_spheres"] == 5 and m0["centres"] and m0["prev_centres"] and m0["centres"] != m0["prev_centres"]
     t0 = rt.sphere_table((s, m))
-    assert np.array_equal(u32(download(m0["centres"], 5)), u32(t0)) and np.array_equal(u32(download(m0["prev_centres"], 5)), u32(t0))
+    assert np.array_equal(u32(download(m0["centres"], (5, 4))), u32(t0)) and np.array_equal(u32(download(m0["prev_centres"], (5, 4))), u32(t0))
     moved = s.copy()
     moved["center"][2, 2] = F(0.25)
     sc.update((moved, m))                                   # geometry only
     m1 = sc.motion()
     assert (m1["geometry_epoch"], m1["appearance_epoch"]) == (1, 0)
-    assert np.array_equal(u32(download(m1["centres"], 5)), u32(rt.sphere_table((moved, m))))
-    assert np.array_equal(u32(download(m1["prev_centres"], 5)), u32(t0))
+    assert_bits(download(m1["centres"], (5, 4)), rt.sphere_table((moved, m)))
+    assert_bits(download(m1["prev_centres"], (5, 4)), t0)
     painted = m.copy()
     painted["albedo"][1, 0] = F(0.25)
     sc.update((moved, painted))                             # albedo only
@@ -185,7 +172,7 @@ def test_epochs_and_tables():
     sc.update((resized, m))                                 # both: a radius, and the albedo back
     m4 = sc.motion()
     assert (m4["geometry_epoch"], m4["appearance_epoch"]) == (2, 2)
-    assert np.array_equal(u32(download(m4["prev_centres"], 5)), u32(rt.sphere_table((moved, m))))
+    assert_bits(download(m4["prev_centres"], (5, 4)), rt.sphere_table((moved, m)))
     assert sc.usage()["device_bytes"] == usage_bytes
     sc.close()
 

@@ -28,6 +28,7 @@ import progressive_ref  # noqa: E402
 import test_adaptive_gpu as TA  # noqa: E402  (its output sets and step comparison)
 import test_progressive_gpu as TP  # noqa: E402  (its output sets and estimate comparison)
 import test_variance_gpu as TV  # noqa: E402  (its scenes, params, references and plan variants)
+from support import words  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -453,7 +454,7 @@ def test_a_variance_frame_after_a_scene_update():
     off = var_frame(p, cam, None, records=B)
     for u in (before[3], after[3], fresh[3]):
         assert_kernel_ran(u, SKY_TILES)
-    assert int(np.count_nonzero(TV.u32(before[0]) != TV.u32(after[0]))) > 100  # (the update changed the picture)
+    assert int(np.count_nonzero(words(before[0]) != words(after[0]))) > 100  # (the update changed the picture)
     for i, what in enumerate(("rgb", "var")):
         TV.assert_same(after[i], fresh[i], f"{what} against a fresh scene")
         TV.assert_same(after[i], off[i], f"{what} against a fresh scene without the option")

@@ -16,7 +16,6 @@ import functools
 import os
 import sys
 
-import numpy as np
 import pytest
 
 import raytracinginoneweekend_amd as rt
@@ -24,6 +23,7 @@ import raytracinginoneweekend_amd as rt
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import camera_cases as CC  # noqa: E402
 import oracle_binding as O  # noqa: E402
+from support import assert_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -31,17 +31,6 @@ SKY_CASES = ("up_clear", "rolled", "horizon", "tiny_sky", "wide_sky", "subnormal
 SPPS = (1, 2, 3, 4, 7, 8, 9, 13, 33)
 NO_SKY_SPPS = (4, 9, 33)
 SHARE_CASE, SHARE_SPP, SHARE_OFFSET, SHARE_STRIDE = "up_clear", 9, 1, 3  # 8 of the share's 13 blocks are sky
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_bits(got, ref, what):
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(f"{what}: {bad} of {u32(ref).size} values differ")
-    assert bad == 0, f"{what}: {bad} of {u32(ref).size} values differ"
 
 
 def params(name, spp, **kw):

@@ -8,11 +8,17 @@ each output of the sequence must be its isolated twin bit for bit. Then rt.relea
 The huge scene at 4 spp, depth 64, default camera; A = 64 x 36, B = 24 x 16 (no whole 8 x 8 tiles).
 The filters' and the accumulation's inputs are the isolated renders' own outputs.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import raytracinginoneweekend_amd as rt
 from raytracinginoneweekend_amd import _abi as abi
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+from support import assert_all_bits, assert_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -20,11 +26,6 @@ SEED, SPP, DEPTH = 1234, 4, 64
 A, B = (64, 36), (24, 16)
 GUIDES = ("albedo", "normal", "depth")
 FULL_ROWS = dict(row_offset=1, row_stride=3, full_frame=True)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint8 if a.dtype == np.uint8 else np.uint32)
 
 
 def params(size, **kw):
@@ -125,11 +126,7 @@ def test_every_call_of_the_mixed_sequence_equals_its_isolated_twin(runs):
     for name, outputs, _ in mixed:
         want = isolated[name][0]
         assert set(outputs) == set(want)
-        for plane, got in outputs.items():
-            ref = want[plane]
-            bad = int(np.count_nonzero(bits(got) != bits(ref))) if got.shape == ref.shape else -1
-            print(f"{name} {plane}: {bad} mismatching values of {ref.size}")
-            assert got.dtype == ref.dtype and bad == 0, (name, plane)
+        assert_all_bits(outputs, want, name)
     # the renders are not trivially equal: something was rendered, and A is not B
     assert isolated["f32-A"][0]["rgb"].any() and isolated["rgb8-A"][0]["rgb8"].any()
     assert isolated["var-full-rows-A"][0]["rgb"].shape == (12, 64, 3)
@@ -153,5 +150,5 @@ def test_release_twice_then_a_render(runs):
     rt.release_cached()
     img, st = rt.render_f32(rt.huge_scene_arrays(SEED), params(B))
     want = isolated["f32-B"][0]["rgb"]
-    assert img.shape == want.shape and int(np.count_nonzero(bits(img) != bits(want))) == 0
+    assert_bits(img, want, "a render after two releases")
     assert st.kernel_ms > 0 and st.wall_ms >= st.kernel_ms

@@ -18,12 +18,9 @@ import clip_cases  # noqa: E402
 import temporal_clip_ref as R  # noqa: E402
 import temporal_motion_ref  # noqa: E402
 import temporal_ref  # noqa: E402
+from support import assert_bits, words as u32  # noqa: E402
 
 F = np.float32
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- the record --------------------------------------------------------------------------------------
@@ -227,11 +224,11 @@ def test_restatement_clamps_into_the_box_and_the_cases_say_something(w, h, radiu
     assert (info["lo"] <= info["hi"]).all()
     assert (info["clamped"][kept] >= info["lo"][kept]).all() and (info["clamped"][kept] <= info["hi"][kept]).all()
     inside = (info["resampled"] >= info["lo"]) & (info["resampled"] <= info["hi"])
-    assert np.array_equal(u32(info["clamped"][kept & inside.all(axis=2)]), u32(info["resampled"][kept & inside.all(axis=2)]))
+    assert_bits(info["clamped"][kept & inside.all(axis=2)], info["resampled"][kept & inside.all(axis=2)])
     assert np.array_equal(u32(c[~kept]), u32(cur["beauty"][~kept])) and (n[~kept] == 1).all()
     k = np.fmax(F(1) / n, F(par.alpha_min))
     want = k[..., None] * cur["beauty"] + (F(1) - k)[..., None] * info["clamped"]
-    assert np.array_equal(u32(c[kept]), u32(want[kept]))
+    assert_bits(c[kept], want[kept])
     changed, total = int(info["changed"].sum()), int(kept.sum())
     print(f"{w}x{h} radius {radius} motion {motion}: pixels with history {total}, a channel changed on {changed}")
     assert total > w * h // 4
@@ -285,9 +282,9 @@ def test_a_pixel_alone_in_its_window_takes_its_own_colour():
         c, v, n, reason, info = R.accumulate(cur, prev, cam, cam, par, rt.temporal_clip(radius=radius, gamma=3.0))
         assert (reason == R.KEPT).all() and np.abs(n - 4).max() < 1e-5
         assert np.array_equal(u32(info["lo"]), u32(cur["beauty"])) and np.array_equal(u32(info["hi"]), u32(cur["beauty"]))
-        assert np.array_equal(u32(info["clamped"]), u32(cur["beauty"]))
+        assert_bits(info["clamped"], cur["beauty"])
         k = np.fmax(F(1) / n, F(par.alpha_min))
-        assert np.array_equal(u32(c), u32(k[..., None] * cur["beauty"] + (F(1) - k)[..., None] * cur["beauty"]))
+        assert_bits(c, k[..., None] * cur["beauty"] + (F(1) - k)[..., None] * cur["beauty"])
         assert (u32(info["resampled"]) != u32(cur["beauty"])).any()
 
 

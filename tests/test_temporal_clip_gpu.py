@@ -19,27 +19,17 @@ import raytracinginoneweekend_amd as rt
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import clip_cases  # noqa: E402
 import temporal_clip_ref as R  # noqa: E402
+from device_io import SENTINEL  # noqa: E402
+from support import assert_all_bits as assert_all_same, assert_bits, words as u32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-SENTINEL = -7.0
 CUR = ("beauty", "variance", "normal", "depth", "alpha", "sphere_id")
 PREV = ("color", "variance", "history", "normal", "depth", "sphere_id")
 OUT = ("out_color", "out_variance", "out_history")
 CASES = [(w, h, r, m) for (w, h) in clip_cases.SIZES for r in clip_cases.RADII for m in (False, True)]
 IDS = [f"{w}x{h}-r{r}-{'motion' if m else 'static'}" for w, h, r, m in CASES]
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_all_same(got, ref, what=""):
-    for g, r, n in zip(got, ref, ("color", "variance", "history")):
-        bad = int(np.count_nonzero(u32(g) != u32(r)))
-        print(what, n, "mismatching values:", bad, "of", r.size)
-        assert g.shape == r.shape and g.dtype == np.float32 and bad == 0, f"{what} {n}"
 
 
 @functools.lru_cache(maxsize=None)
@@ -104,7 +94,7 @@ def test_clip_is_the_restatement_bit_for_bit(w, h, radius, motion):
     # (the host call took read-only arrays: they are what they were)
     again = clip_cases.planes.__wrapped__(w, h)
     for a, b in zip(list(cur.values()) + list(prev.values()), list(again[0].values()) + list(again[1].values())):
-        assert np.array_equal(u32(a), u32(b))
+        assert_bits(a, b)
 
 
 # ---- 2: the clamp does something, and gamma reaches the kernel ------------------------------------------
@@ -119,7 +109,7 @@ def test_clip_differs_from_the_plain_stage_and_follows_gamma(motion):
     differ = (u32(plain[0]) != u32(ref[0])).any(axis=2)
     print("pixels where the plain stage differs from the clamped one:", int(differ.sum()))
     assert differ.sum() > (ref[3] == R.KEPT).sum() / 10 and (differ <= ref[4]["changed"]).all()
-    assert_all_same(plain[1:], ref[1:3], "variance and history are the plain stage's")
+    assert_all_same(plain[1:], ref[1:3], "the plain stage's", names=("variance", "history"))
     for gamma in (0.0, 0.5, 2.5):
         clip = clip_cases.clip(radius, gamma=gamma)
         want = R.accumulate(cur, prev, cam, prev_cam, par, clip, *(tabs or (None, None)))

@@ -16,12 +16,9 @@ from raytracinginoneweekend_amd import _abi as abi
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import temporal_ref  # noqa: E402
+from support import assert_bits, words as u32  # noqa: E402
 
 F = np.float32
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- records -------------------------------------------------------------------------------------
@@ -64,7 +61,7 @@ def test_reproject_basis_is_the_restatement_bit_for_bit(name):
     cam = CAMERAS[name]()
     got, ref = rt.reproject_basis(cam), temporal_ref.basis(cam)
     assert got.dtype == np.float32 and got.shape == (12,) and np.isfinite(got).all()
-    assert np.array_equal(u32(got), u32(ref)), (got, ref)
+    assert_bits(got, ref, (got, ref))
     assert np.array_equal(got[9:], np.array(cam.c.origin, dtype=F))
 
 

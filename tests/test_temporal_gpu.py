@@ -19,15 +19,17 @@ from raytracinginoneweekend_amd import _abi as abi
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import denoise_var_ref  # noqa: E402
 import temporal_ref as T  # noqa: E402
+from device_io import SENTINEL  # noqa: E402
+from support import LOOK, POS, frame_planes, shifted_camera as camera  # noqa: E402
+from support import assert_all_bits as assert_all_same, assert_bits as assert_same  # noqa: E402
+from support import census as reason_census  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 SCENE_SEED = 1234
 SPP = 4
-SENTINEL = -7.0
 MODES = {"reference": rt.REFERENCE, "corrected": rt.CORRECTED}
-POS, LOOK = (-4.0, 3.2, 5.0), (0.0, 1.0, 0.0)  # the default camera's position and look-at point
 # (position shift, look-at shift) after which part of the previous frame has left the screen. In
 # REFERENCE mode a ray's direction is the image-plane point itself, so the picture depends on the
 # camera's position far more strongly and the move is smaller.
@@ -36,32 +38,9 @@ CUR = ("beauty", "variance", "normal", "depth", "alpha", "sphere_id")
 PREV = ("color", "variance", "history", "normal", "depth", "sphere_id")
 
 
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same(got, ref, what=""):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(what, "mismatching values:", bad, "of", ref.size)
-    assert got.shape == ref.shape and got.dtype == np.float32 and bad == 0, what
-
-
-def assert_all_same(got, ref, what=""):
-    for g, r, n in zip(got, ref, ("color", "variance", "history")):
-        assert_same(g, r, f"{what} {n}")
-
-
 @functools.lru_cache(maxsize=None)
 def scene():
     return rt.huge_scene_arrays(SCENE_SEED)
-
-
-@functools.lru_cache(maxsize=None)
-def camera(w, h, mode, shift=((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))):
-    """The default camera of a w x h image with its position and look-at point shifted."""
-    pos, look = tuple(np.add(POS, shift[0])), tuple(np.add(LOOK, shift[1]))
-    focus = float(np.float32(np.linalg.norm(np.subtract(pos, look).astype(F))))
-    return rt.Camera(pos, look, (0, 1, 0), w / h, 42.0, 0.0625, focus, mode)
 
 
 AWAY = ((0.0, 0.0, 0.0), tuple(2 * (np.array(POS) - np.array(LOOK))))  # looks along -w of the default camera
@@ -71,13 +50,8 @@ AWAY = ((0.0, 0.0, 0.0), tuple(2 * (np.array(POS) - np.array(LOOK))))  # looks a
 def frame(w, h, mode, seed, shift=((0.0, 0.0, 0.0), (0.0, 0.0, 0.0)), albedo=False):
     """The planes of one frame of the huge scene: beauty and variance of SPP samples, the guides of
     the same samples."""
-    p, cam = rt.make_params(w, h, SPP, 64, seed), camera(w, h, mode, shift)
-    beauty, variance, _ = rt.render_var(scene(), p, cam)
-    g = rt.render_aov(scene(), p, cam, SPP, ("normal", "depth", "alpha", "sphere_id") + (("albedo",) if albedo else ()))
-    planes = dict(beauty=beauty, variance=variance, **g)
-    for a in planes.values():
-        a.setflags(write=False)
-    return planes
+    return frame_planes(scene(), rt.make_params(w, h, SPP, 64, seed), camera(w, h, mode, shift), SPP,
+                        ("normal", "depth", "alpha", "sphere_id") + (("albedo",) if albedo else ()))
 
 
 def cur_of(f):
@@ -93,10 +67,7 @@ def prev_of(f, color=None, variance=None, history=None):
                 normal=f["normal"], depth=f["depth"], sphere_id=f["sphere_id"])
 
 
-def census(reason):
-    c = {name: int((reason == k).sum()) for k, name in T.REASONS.items()}
-    print("reasons:", c)
-    return c
+census = functools.partial(reason_census, reasons=T.REASONS)
 
 
 def device_call(cur, prev, cam, prev_cam, par):

@@ -17,37 +17,28 @@ import raytracinginoneweekend_amd as rt
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import temporal_motion_ref as M  # noqa: E402
 import temporal_ref as T  # noqa: E402
+from device_io import SENTINEL  # noqa: E402
+from support import STILL, frame_planes, shifted_camera  # noqa: E402
+from support import assert_all_bits as assert_all_same, words as u32  # noqa: E402
+from support import census as reason_census  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 SCENE_SEED = 1234
 SPP = 4
-SENTINEL = -7.0
 MODES = {"reference": rt.REFERENCE, "corrected": rt.CORRECTED}
 # The default camera's position and look-at point. In REFERENCE mode a ray's direction is the image-plane
 # point itself and that camera sees none of the moved spheres: there the camera stands in front of the
 # three large spheres and looks at a far point below them, which puts spheres 2 and 3 on some 400 pixels
 # each at 64 x 36 (found with a first-hit tracer on the CPU).
 VIEW = {rt.CORRECTED: ((-4.0, 3.2, 5.0), (0.0, 1.0, 0.0)), rt.REFERENCE: ((0.0, 1.5, 3.0), (0.0, -2.0, -12.0))}
-STILL = ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
 CAMERA_MOVE = ((0.1, 0.05, -0.05), (0.15, 0.05, 0.0))  # a small move: most of the frame stays on screen
 MOVED_IDS = (2, 3, 4)               # the metal sphere, the glass sphere and its bubble
 SHIFT = (0.0, 0.0, 0.15)            # about one pixel at 64x36
 CUR = ("beauty", "variance", "normal", "depth", "alpha", "sphere_id")
 PREV = ("color", "variance", "history", "normal", "depth", "sphere_id")
 SIZES = ((64, 36), (48, 27))
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_all_same(got, ref, what=""):
-    for g, r, n in zip(got, ref, ("color", "variance", "history")):
-        bad = int(np.count_nonzero(u32(g) != u32(r)))
-        print(what, n, "mismatching values:", bad, "of", r.size)
-        assert g.shape == r.shape and g.dtype == np.float32 and bad == 0, f"{what} {n}"
 
 
 @functools.lru_cache(maxsize=None)
@@ -63,22 +54,14 @@ def records(which):
     return s, m
 
 
-@functools.lru_cache(maxsize=None)
 def camera(w, h, mode, shift=STILL):
-    pos, look = tuple(np.add(VIEW[mode][0], shift[0])), tuple(np.add(VIEW[mode][1], shift[1]))
-    focus = float(np.float32(np.linalg.norm(np.subtract(pos, look).astype(F))))
-    return rt.Camera(pos, look, (0, 1, 0), w / h, 42.0, 0.0625, focus, mode)
+    return shifted_camera(w, h, mode, shift, VIEW[mode])
 
 
 @functools.lru_cache(maxsize=None)
 def frame(which, w, h, mode, seed, shift=STILL):
-    p, cam = rt.make_params(w, h, SPP, 64, seed), camera(w, h, mode, shift)
-    beauty, variance, _ = rt.render_var(records(which), p, cam)
-    g = rt.render_aov(records(which), p, cam, SPP, ("normal", "depth", "alpha", "sphere_id"))
-    planes = dict(beauty=beauty, variance=variance, **g)
-    for a in planes.values():
-        a.setflags(write=False)
-    return planes
+    return frame_planes(records(which), rt.make_params(w, h, SPP, 64, seed), camera(w, h, mode, shift), SPP,
+                        ("normal", "depth", "alpha", "sphere_id"))
 
 
 def cur_of(f):
@@ -91,10 +74,7 @@ def prev_of(f):
                 normal=f["normal"], depth=f["depth"], sphere_id=f["sphere_id"])
 
 
-def census(reason):
-    c = {name: int((reason == k).sum()) for k, name in M.REASONS.items()}
-    print("reasons:", c)
-    return c
+census = functools.partial(reason_census, reasons=M.REASONS)
 
 
 def device_call(cur, prev, cam, prev_cam, par, tables, same_table=False, static=False):

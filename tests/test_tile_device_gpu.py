@@ -6,7 +6,6 @@ The contract is equality, not closeness: the device's kernels evaluate the host'
 and frames bit for bit (uint32 views, zero mismatches) with the oracle's or with the frames of a
 scene whose orders come from the host.
 """
-import math
 import os
 import sys
 
@@ -20,27 +19,13 @@ from raytracinginoneweekend_amd import _abi as abi
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import camera_cases as CC  # noqa: E402
+from support import assert_bits as _bits_equal, orbit_camera  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-POS, LOOK = (-4.0, 3.2, 5.0), (0.0, 1.0, 0.0)  # the default camera's position and look-at point
-STEP_DEG = 1.5                                   # the orbit's step per frame
-
-
-def _bits_equal(a, b, what=""):
-    a = np.ascontiguousarray(a).view(np.uint32 if a.dtype.itemsize == 4 else np.uint8)
-    b = np.ascontiguousarray(b).view(np.uint32 if b.dtype.itemsize == 4 else np.uint8)
-    bad = np.count_nonzero(a != b)
-    assert a.shape == b.shape and bad == 0, f"{what}: {bad} of {a.size} values differ"
-
 
 def orbit(w, h, i, mode=rt.REFERENCE):
-    """The default camera turned by i steps around the vertical axis through its look-at point."""
-    a = math.radians(i * STEP_DEG)
-    dx, dz = POS[0] - LOOK[0], POS[2] - LOOK[2]
-    pos = (LOOK[0] + dx * math.cos(a) + dz * math.sin(a), POS[1], LOOK[2] - dx * math.sin(a) + dz * math.cos(a))
-    focus = float(np.float32(np.linalg.norm(np.subtract(pos, LOOK).astype(np.float32))))
-    return rt.Camera(pos, LOOK, (0, 1, 0), w / h, 42.0, 0.0625, focus, mode)
+    return orbit_camera(w, h, i, mode=mode)
 
 
 def _same_order(ds, scene, cam, p, what):

@@ -19,14 +19,11 @@ from raytracinginoneweekend_amd import _abi as abi
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import upsample_cases  # noqa: E402
 import upsample_ref  # noqa: E402
+from support import assert_bits, census, words as u32  # noqa: E402
 
 F = np.float32
 W0, H0, LW0, LH0 = 70, 37, 35, 19
 SIZES = [(32, 18, 64, 36), (35, 19, 70, 37), (23, 12, 67, 35), (64, 36, 64, 36), (1, 1, 5, 3)]
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- records -------------------------------------------------------------------------------------
@@ -223,8 +220,8 @@ def test_restatement_shapes_positions_and_the_plain_weight(lw, lh, w, h):
 def test_census_every_reason_occurs_and_guided_pixels_are_a_fair_share():
     lo, guides = upsample_cases.planes(LW0, LH0, W0, H0)
     _, _, reason, outside = upsample_ref.upsample(lo, guides, rt.upsample_params(W0, H0, LW0, LH0))
-    counts = {name: int((reason == code).sum()) for code, name in upsample_ref.REASONS.items()}
-    print(counts, "taps outside on", int(outside.sum()), "pixels")
+    counts = census(reason, upsample_ref.REASONS)
+    print("taps outside on", int(outside.sum()), "pixels")
     assert all(counts.values()), counts
     share = counts["guided"] / reason.size
     assert 0.2 <= share <= 0.8, share
@@ -272,7 +269,7 @@ def test_one_low_pixel_within_one_ulp():
         lo, guides = upsample_cases.planes(1, 1, 5, 3, seed=seed)
         color, variance, reason, outside = upsample_ref.upsample(lo, guides, rt.upsample_params(5, 3, 1, 1))
         c = lo["color"][0, 0]
-        assert np.array_equal(u32(color[1, 2]), u32(c))
+        assert_bits(color[1, 2], c)
         ulps = np.abs(u32(color).astype(np.int64) - u32(np.broadcast_to(c, (3, 5, 3))).astype(np.int64))
         assert ulps.max() <= 1
         differ += int(ulps.sum())

@@ -20,24 +20,14 @@ from raytracinginoneweekend_amd import _abi as abi
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import upsample_cases  # noqa: E402
 import upsample_ref  # noqa: E402
+from device_io import SENTINEL  # noqa: E402
+from support import assert_bits as assert_same, census, orbit_camera  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 SIZES = [(32, 18, 64, 36), (35, 19, 70, 37), (23, 12, 67, 35), (64, 36, 64, 36), (1, 1, 5, 3)]
-SENTINEL = -7.0
 SCENE_SEED, SPP, MAX_DEPTH = 1234, 4, 8
-POS, LOOK = (-4.0, 3.2, 5.0), (0.0, 1.0, 0.0)  # the default camera's position and look-at point
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same(got, ref, what=""):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(what, "mismatching values:", bad, "of", ref.size)
-    assert got.shape == ref.shape and got.dtype == ref.dtype and bad == 0, what
 
 
 @functools.lru_cache(maxsize=None)
@@ -63,7 +53,7 @@ def run_device(lo, guides, w, h, lw, lh, with_variance):
     st.synchronize()
     after = {n: t.cpu().numpy().view(host[n].dtype) for n, t in dev.items()}
     for n, a in host.items():
-        assert np.array_equal(u32(after[n]), u32(a)), f"input plane {n} changed"
+        assert_same(after[n], a, f"input plane {n} changed")
     return out["out_color"].cpu().numpy(), out["out_variance"].cpu().numpy() if with_variance else None
 
 
@@ -71,7 +61,7 @@ def run_device(lo, guides, w, h, lw, lh, with_variance):
 def test_device_call_equals_the_restatement(lw, lh, w, h):
     lo, guides, (ref_c, ref_v, reason, _) = case(lw, lh, w, h)
     color, variance = run_device(lo, guides, w, h, lw, lh, True)
-    print({upsample_ref.REASONS[k]: int((reason == k).sum()) for k in upsample_ref.REASONS})
+    census(reason, upsample_ref.REASONS)
     assert (color != SENTINEL).all() and (variance != SENTINEL).all()
     assert_same(color, ref_c, "colour")
     assert_same(variance, ref_v, "variance")
@@ -83,25 +73,17 @@ def test_device_call_equals_the_restatement(lw, lh, w, h):
 
 def test_the_census_conditions_hold_on_the_restatement():
     _, _, (_, _, reason, outside) = case(35, 19, 70, 37)
-    counts = {name: int((reason == code).sum()) for code, name in upsample_ref.REASONS.items()}
-    print(counts)
+    counts = census(reason, upsample_ref.REASONS)
     assert all(counts.values()), counts
     assert 0.2 <= counts["guided"] / reason.size <= 0.8
     assert outside.any()
 
 
 # ---- rendered planes --------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def camera(w, h):
-    """The preview module's corrected camera, frame 0 of its orbit (the default position)."""
-    focus = float(np.float32(np.linalg.norm(np.subtract(POS, LOOK).astype(F))))
-    return rt.Camera(POS, LOOK, (0, 1, 0), w / h, 42.0, 0.0625, focus, rt.CORRECTED)
-
-
 def test_host_call_on_rendered_planes_equals_the_restatement():
     scene = rt.huge_scene_arrays(SCENE_SEED)
     lw, lh, w, h = 35, 19, 70, 37
-    cam = camera(w, h)  # one camera for both sizes: depths compare directly
+    cam = orbit_camera(w, h, 0)  # the preview module's corrected camera, frame 0 of its orbit; one camera for both sizes: depths compare directly
     p_lo, p_hi = rt.make_params(lw, lh, SPP, MAX_DEPTH, 1), rt.make_params(w, h, SPP, MAX_DEPTH, 1)
     beauty, variance, _ = rt.render_var(scene, p_lo, cam)
     g_lo = rt.render_aov(scene, p_lo, cam, 0)
@@ -110,8 +92,8 @@ def test_host_call_on_rendered_planes_equals_the_restatement():
     guides = {n: g_hi[n] for n in ("normal", "depth", "alpha", "sphere_id")}
     params = rt.upsample_params(w, h, lw, lh)
     ref_c, ref_v, reason, outside = upsample_ref.upsample(lo, guides, params)
-    counts = {name: int((reason == code).sum()) for code, name in upsample_ref.REASONS.items()}
-    print(counts, "taps outside on", int(outside.sum()), "pixels; surface pixels:", int((guides["alpha"] == 1).sum()))
+    counts = census(reason, upsample_ref.REASONS)
+    print("taps outside on", int(outside.sum()), "pixels; surface pixels:", int((guides["alpha"] == 1).sum()))
     stats = abi.RtStats()
     color, var = rt.upsample(lo, guides, stats=stats)
     assert_same(color, ref_c, "colour")

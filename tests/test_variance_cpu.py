@@ -20,12 +20,9 @@ import aov_ref  # noqa: E402
 import denoise_ref  # noqa: E402
 import denoise_var_ref  # noqa: E402
 import moments_ref  # noqa: E402
+from support import assert_bits, synthetic_planes, words as u32  # noqa: E402
 
 F = np.float32
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 # ---- records -------------------------------------------------------------------------------------
@@ -267,7 +264,7 @@ def test_reference_variance_is_the_unbiased_variance_of_the_mean(spp):
     p = rt.make_params(16, 8, spp, 64, 1234)
     rgb, var, samples = moments_ref.render(s, m, cam, p)
     ref, _ = O.render_f32(s, m, cam.c, p)
-    assert np.array_equal(u32(rgb), u32(ref))
+    assert_bits(rgb, ref)
     assert var.dtype == np.float32 and var.shape == (8, 16) and (var >= 0).all()
     lum = moments_ref.luminance(samples).astype(np.float64)
     want = lum.var(axis=-1, ddof=1) / spp
@@ -295,14 +292,8 @@ def test_reference_variance_layout_follows_the_rows():
 
 # ---- properties of the filter's reference -------------------------------------------------------------
 def _random_planes(w, h, seed):
-    g = np.random.default_rng(seed)
-    beauty = g.random((h, w, 3), dtype=np.float32)
-    n = g.standard_normal((h, w, 3)).astype(np.float32)
-    normal = (n / np.sqrt((n * n).sum(-1, keepdims=True))).astype(np.float32)
-    depth = (g.random((h, w), dtype=np.float32) * F(4)).astype(np.float32)
-    albedo = g.random((h, w, 3), dtype=np.float32)
-    variance = (g.random((h, w), dtype=np.float32) * F(0.01)).astype(np.float32)
-    return beauty, albedo, normal, depth, variance
+    p = synthetic_planes(w, h, variance_scale=0.01, seed=seed)
+    return tuple(p[n] for n in ("beauty", "albedo", "normal", "depth", "variance"))
 
 
 def test_reference_huge_floor_and_zero_variance_turn_the_colour_term_into_one():
@@ -350,7 +341,7 @@ def test_reference_variance_of_a_constant_plane_shrinks_by_the_weights():
                             sv = sv + (wgt * wgt) * v[qy, qx]
                 nxt[y, x] = sv / (sw * sw)
         v = nxt
-    assert np.array_equal(u32(vout), u32(v))
+    assert_bits(vout, v)
     assert (vout < v0).all()
 
 
@@ -362,7 +353,7 @@ def test_reference_prefilter_clamps_at_the_border():
         for i in (-1, 0, 1):
             k = F(0.25) if (i == 0 and j == 0) else F(0.125) if (i == 0 or j == 0) else F(0.0625)
             g = g + k * v[0, 0]
-    assert np.array_equal(u32(denoise_var_ref.prefilter(v)), u32(np.array([[g]], dtype=np.float32)))
+    assert_bits(denoise_var_ref.prefilter(v), np.array([[g]], dtype=np.float32))
     # a constant plane stays constant up to that rounding, whatever the position
     c = denoise_var_ref.prefilter(np.full((5, 4), F(0.7), dtype=np.float32))
     assert (u32(c) == u32(np.float32(g))).all()

@@ -19,24 +19,15 @@ from raytracinginoneweekend_amd import _abi as abi
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import denoise_var_ref  # noqa: E402
 import moments_ref  # noqa: E402
+from device_io import SENTINEL  # noqa: E402  (other modules read it from here too)
+from support import assert_bits as assert_same, frame_planes, synthetic_planes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 SEED = 1234
 GUIDES = ("albedo", "normal", "depth")
-SENTINEL = -7.0
 CAMERAS = {"reference": rt.REFERENCE, "corrected": rt.CORRECTED}
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same(got, ref, what=""):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(what, "mismatching values:", bad, "of", ref.size)
-    assert got.shape == ref.shape and got.dtype == np.float32 and bad == 0, what
 
 
 # ---- the render ----------------------------------------------------------------------------------------
@@ -275,27 +266,8 @@ VAR_SCALE = 0.02  # synthetic variances lie in [0, VAR_SCALE)
 
 @functools.lru_cache(maxsize=None)
 def synthetic(w, h, block=False):
-    """Seeded random planes: beauty in [0, 1), unit normals, depth in [0, 4), albedo in [0, 1),
-    variance in [0, VAR_SCALE); block: the left half carries one colour, sky-like guides (normal 0,
-    depth 0, one albedo) and a variance of 0."""
-    g = np.random.default_rng(w * 1000 + h)
-    beauty = g.random((h, w, 3), dtype=np.float32)
-    n = g.standard_normal((h, w, 3)).astype(np.float32)
-    normal = (n / np.sqrt((n * n).sum(-1, keepdims=True))).astype(np.float32)
-    depth = (g.random((h, w), dtype=np.float32) * F(4)).astype(np.float32)
-    albedo = g.random((h, w, 3), dtype=np.float32)
-    variance = (g.random((h, w), dtype=np.float32) * F(VAR_SCALE)).astype(np.float32)
-    if block:
-        half = w // 2
-        beauty[:, :half] = (F(0.25), F(0.5), F(0.75))
-        albedo[:, :half] = (F(0.5), F(0.625), F(0.75))
-        normal[:, :half] = 0
-        depth[:, :half] = 0
-        variance[:, :half] = 0
-    planes = dict(beauty=beauty, albedo=albedo, normal=normal, depth=depth, variance=variance)
-    for a in planes.values():
-        a.setflags(write=False)
-    return planes
+    """support.synthetic_planes with a variance in [0, VAR_SCALE), once per module."""
+    return synthetic_planes(w, h, block, VAR_SCALE)
 
 
 _DREFS = {}
@@ -376,13 +348,7 @@ REAL = {"64x36": (64, 36, rt.REFERENCE, 4), "128x72": (128, 72, rt.CORRECTED, 8)
 def real(name):
     """Beauty and variance from rt.render_var, guides from rt.render_aov with 4 samples (the huge scene)."""
     w, h, mode, spp = REAL[name]
-    p, cam = params(w, h, spp), rt.Camera.default(w, h, mode)
-    beauty, variance, _ = rt.render_var(scene("huge"), p, cam)
-    g = rt.render_aov(scene("huge"), p, cam, 4, GUIDES)
-    planes = dict(beauty=beauty, variance=variance, **g)
-    for a in planes.values():
-        a.setflags(write=False)
-    return planes
+    return frame_planes(scene("huge"), params(w, h, spp), rt.Camera.default(w, h, mode), 4, GUIDES)
 
 
 @pytest.mark.parametrize("name", sorted(REAL))

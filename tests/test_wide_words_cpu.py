@@ -20,15 +20,12 @@ import raytracinginoneweekend_amd as rt
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import wide_cases as WC  # noqa: E402
+from support import assert_bits, words as u32  # noqa: E402
 
 # "A few seconds" per band on 16 threads. The slowest band measured 2.1 s alone and 5.0 s beside a
 # compiler on the same 8 cores; three times that is the bound, so that only a band that has become
 # several times dearer fails, not a busy machine.
 BAND_SECONDS = 15.0
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_frame_and_bands_reach_the_wide_words():
@@ -133,7 +130,7 @@ def test_wide_seeds_draw_other_streams_and_aliases_the_same():
     base, base_seg = WC.small_ref(WC.BASE_SEED)
     meta, f32, _ = G.render("huge_64x36_s4")
     assert (meta["width"], meta["height"], meta["spp"], meta["seed"]) == (*WC.SMALL, WC.BASE_SEED)
-    assert np.array_equal(u32(base), u32(f32))  # the reference's own frame
+    assert_bits(base, f32)  # the reference's own frame
     for name in WC.WIDE_SEEDS:
         img, _ = WC.small_ref(WC.SEEDS[name])
         changed = int(np.count_nonzero(u32(img) != u32(base)))
@@ -153,7 +150,7 @@ def test_reference_fixture_of_the_wide_seed_is_the_small_case():
     """tests/golden/huge_64x36_s4_seedhi is the reference's own render of the small frame with SEED."""
     meta, f32, _ = G.render("huge_64x36_s4_seedhi")
     assert (meta["width"], meta["height"], meta["spp"], meta["seed"]) == (*WC.SMALL, WC.SEED)
-    assert np.array_equal(u32(WC.small_ref(WC.SEED)[0]), u32(f32))
+    assert_bits(WC.small_ref(WC.SEED)[0], f32)
     wide = G.manifest()["renders"]["wide_huge_4096x1048560_row838848_s5_seedhi"]
     assert wide["seed"] == WC.SEED and wide["width"] <= 4096 and wide["num_rows"] == 1
     assert 2 ** 32 - 2 ** 20 <= wide["width"] * wide["height"] < 2 ** 32

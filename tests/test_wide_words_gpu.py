@@ -34,6 +34,7 @@ from raytracinginoneweekend_amd import render as R
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import wide_cases as WC  # noqa: E402
+from support import assert_all_bits, assert_bits, words as u32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -84,20 +85,12 @@ VARIANTS = {
 }
 
 
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_bits(got, ref, what):
-    bad = int(np.count_nonzero(u32(got) != u32(ref)))
-    print(f"{what}: {bad} of {u32(ref).size} values differ")
-    assert got.shape == ref.shape and bad == 0, f"{what}: {bad} of {u32(ref).size} values differ"
-
-
 def render_device(scene, cam, p, count=False, out=None, out_ptr=None):
     """One rt_render_device call on a fresh scene made with the process-default options (the opts
     fixture's): (frame as uint32 (rows, W, 3), segments or None, rt_scene_usage, word [15] of
-    rt_scene_debug_counters: the instrumented kernel's first bounds violation, 0 = none)."""
+    rt_scene_debug_counters: the instrumented kernel's first bounds violation, 0 = none). The frame
+    comes back as the words of a buffer filled with an integer sentinel; the float32 references are
+    compared as u32(ref), the same bytes under that dtype."""
     import torch
     rows = p.height if p.flags & abi.RT_FLAG_FULL_FRAME else abi.rows_of(p)
     if out is None:
@@ -132,7 +125,7 @@ def test_beauty_matches_restatement(name, variant, opts):
     opts.set(**CASES[name]["base"], **v)
     ref, ref_seg = case_ref(name)
     got, seg, usage, violation = render_device(WC.scene(), cam, p, count)
-    assert_bits(got, ref, f"{name} {variant}")
+    assert_bits(got, u32(ref), f"{name} {variant}")
     if count:
         assert seg == ref_seg
     assert violation == 0
@@ -154,7 +147,7 @@ def test_lone_split_pass_of_the_deep_band_takes_the_deep_launch(opts):
     ref, ref_seg = case_ref("deep-corrected")
     got, seg, usage, _ = render_device(WC.scene(), case_camera("deep-corrected"), case_params("deep-corrected"), True)
     assert usage["deep_launch"] == 8 | 16 and usage["split_passes"] >= 1, usage
-    assert_bits(got, ref, "deep band, lone split pass")
+    assert_bits(got, u32(ref), "deep band, lone split pass")
     assert seg == ref_seg
 
 
@@ -178,9 +171,7 @@ def test_feature_buffers_match_reference(which):
         cam, p, ref, _ = _stage_case(which)
         assert (ref["alpha"] == 0).any() and (ref["alpha"] == 1).any()
     got = rt.render_aov(WC.scene(), p, cam)
-    bad = {n: int(np.count_nonzero(u32(got[n]) != u32(ref[n]))) for n in PLANES}
-    print(f"{which}: mismatching values per plane: {bad}")
-    assert not any(bad.values()), bad
+    assert_all_bits(got, ref, which, PLANES)
 
 
 @pytest.mark.parametrize("which", ["split", "small"])
@@ -209,9 +200,9 @@ def test_row_partitions_of_the_deep_band(opts):
     halves = [(0, n // 2), (n // 2, n - n // 2)]
     whole, _, usage, _ = render_device(scene, cam, case_params(name))
     assert usage["split_passes"] >= 1
-    assert_bits(whole, ref, "one call")
+    assert_bits(whole, u32(ref), "one call")
     parts = [render_device(scene, cam, case_params(name, rows=h))[0] for h in halves]
-    assert_bits(np.concatenate(parts), ref, "two calls of half the rows")
+    assert_bits(np.concatenate(parts), u32(ref), "two calls of half the rows")
     guard, y0 = 2, WC.BANDS["deep"]["row_offset"]
     row_bytes = WC.W * 12
     for calls in ([(0, n)], halves):
@@ -220,7 +211,7 @@ def test_row_partitions_of_the_deep_band(opts):
         assert base > 0
         for h in calls:
             got = render_device(scene, cam, case_params(name, rows=h, full_frame=True), out=buf, out_ptr=base)[0]
-        assert_bits(got[guard:guard + n], ref, f"full frame, {len(calls)} call(s)")
+        assert_bits(got[guard:guard + n], u32(ref), f"full frame, {len(calls)} call(s)")
         assert (got[:guard] == SENTINEL).all() and (got[guard + n:] == SENTINEL).all()
 
 
@@ -234,7 +225,7 @@ def test_seed_aliases_render_equal_bits(seed):
         b = render_device(WC.scene(), cam, WC.small_params((seed + 2 ** k) % 2 ** 64))[0]
         assert_bits(b, a, f"seed {seed} + 2^{k}")
     cam, p = WC.camera("reference"), WC.params("split", seed=WC.SEED + 2 ** 62)
-    assert_bits(render_device(WC.scene(), cam, p)[0], WC.band_ref("split", "reference")[0], "split band, SEED + 2^62")
+    assert_bits(render_device(WC.scene(), cam, p)[0], u32(WC.band_ref("split", "reference")[0]), "split band, SEED + 2^62")
 
 
 # ---- 5. the reference's CUDA variant: a 32-bit engine ------------------------------------------------
@@ -373,7 +364,7 @@ def test_ground_band_matches_restatement(variant):
     n_ground = WC.band_tiles("ground", "reference")[2]
     got, seg, usage, violation, (ground, redone) = render_ground(WC.scene(), cam, p, v, count)
     print(f"ground band, {variant}: {ground} ground samples, {redone} redone, usage {usage}")
-    assert_bits(got, ref, f"ground band, {variant}")
+    assert_bits(got, u32(ref), f"ground band, {variant}")
     if count:
         assert seg == ref_seg
     assert violation == 0
@@ -392,7 +383,7 @@ def test_small_frame_ground_tiles_with_wide_seeds(name):
     ref, ref_seg = WC.small_ref(seed)
     got, seg, _, _, (ground, redone) = render_ground(WC.scene(), WC.small_camera(), WC.small_params(seed), IN_FLIGHT, True)
     print(f"small frame, seed {name}: {ground} ground samples, {redone} redone")
-    assert_bits(got, ref, f"small frame, seed {name}, in flight")
+    assert_bits(got, u32(ref), f"small frame, seed {name}, in flight")
     assert seg == ref_seg
     assert WC.small_ground_tiles() == 4 and ground == 4 * 64 * WC.SMALL[2]
     assert redone <= ground
@@ -407,7 +398,7 @@ def test_redo_frame_with_wide_seeds(name):
     ref, ref_seg = WC.redo_ref(seed)
     got, seg, _, _, (ground, redone) = render_ground(WC.scene(), WC.redo_camera(), WC.redo_params(seed), IN_FLIGHT, True)
     print(f"redo frame, seed {name}: {ground} ground samples, {redone} redone")
-    assert_bits(got, ref, f"redo frame, seed {name}, in flight")
+    assert_bits(got, u32(ref), f"redo frame, seed {name}, in flight")
     assert seg == ref_seg
     assert ground == 85 * 64 * WC.REDO[2]
     assert 0 < redone < ground

@@ -29,6 +29,7 @@ import functools
 import numpy as np
 
 import raytracinginoneweekend_amd as rt
+from support import STILL, shifted_camera
 
 F = np.float32
 SIZES = ((5, 3), (70, 37), (129, 9))
@@ -36,15 +37,12 @@ RADII = (1, 2, 3)
 GAMMA = 1.0
 HISTORY_RANGE = {None: (0.1, 0.9), (5, 3): (0.35, 0.65)}  # the history's colours, by size (None: every other)
 N_SPHERES = 8
-POS, LOOK = (-4.0, 3.2, 5.0), (0.0, 1.0, 0.0)
 MOVE = ((0.1, 0.05, -0.05), (0.15, 0.05, 0.0))
 X_BORDERS, Y_BORDERS = (21, 62, 67, 101), (2, 6, 18, 31)
 
 
-def camera(w, h, shift=((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))):
-    pos, look = tuple(np.add(POS, shift[0])), tuple(np.add(LOOK, shift[1]))
-    focus = float(np.float32(np.linalg.norm(np.subtract(pos, look).astype(F))))
-    return rt.Camera(pos, look, (0, 1, 0), w / h, 42.0, 0.0625, focus, rt.CORRECTED)
+def camera(w, h, shift=STILL):
+    return shifted_camera(w, h, rt.CORRECTED, shift)
 
 
 def _ids(w, h, g):
