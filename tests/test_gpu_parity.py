@@ -2,9 +2,12 @@
 and the CPU restatement (oracle/), bit for bit in f32.
 
 Tolerance: the exact kernels are compiled with -ffp-contract=off and IEEE div/sqrt, so the
-linear f32 framebuffer must match bitwise (0 ULP). The u8 epilogue evaluates powf through a
-double pow; glibc's powf can differ in its last bit, so u8 may differ by 1 LSB on a handful
-of texels (bound asserted below), never more.
+linear f32 framebuffer must match bitwise (0 ULP). The u8 texel is exact too: over its domain, the
+floats with words 0 .. 0x3f811b5e, it has 255 steps (tests/golden/texel_steps.json); every texel is the
+contract's (rt_texel.h: pow in double, narrowed, times 255.f, truncated) on every float, and the
+reference's except at the floats where its powf disagrees with the correctly rounded pow (one float,
+0x3c364a2a, under glibc 2.35), of which a frame may hold 2 (tests/tools/texel_ref.py
+assert_reference_texels). Only the fast-math kernel, whose f32 frame differs, keeps a u8 tolerance.
 """
 import os
 import sys
@@ -19,6 +22,7 @@ from raytracinginoneweekend_amd import _abi as abi
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 from support import assert_bits as _bits_equal  # noqa: E402
+from texel_ref import assert_reference_texels, assert_texels  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -60,13 +64,13 @@ def test_golden_render_f32(name, variant, opts):
 
 @pytest.mark.parametrize("name", RENDERS)
 def test_golden_render_rgb8(name):
-    meta, _, u8 = G.render(name)
+    """The texels of the golden f32 frame (the GPU's own bits: test_golden_render_f32) by the table, and
+    the reference's u8 frame wherever its powf agrees."""
+    meta, f32, u8 = G.render(name)
     scene = G.scene(meta["scene"])
     cam = rt.Camera.default(meta["width"], meta["height"], G.camera_mode(meta))
     img, _ = rt.render_rgb8(scene, _params(meta), cam)
-    diff = np.abs(img.astype(np.int16) - u8.astype(np.int16))
-    assert diff.max() <= 1
-    assert np.count_nonzero(diff) <= max(2, u8.size // 10000)
+    assert_reference_texels(img, u8, f32, name)
 
 
 @pytest.mark.parametrize("scene_name,W,H,spp,depth,mode", [
@@ -172,7 +176,7 @@ def test_device_api_matches_host_api():
     rt.epilogue_rgb8_device(out.data_ptr(), u8.data_ptr(), 128 * 72, stream.cuda_stream)
     torch.cuda.synchronize()
     ref8 = O.epilogue_rgb8(host)
-    assert np.abs(u8.cpu().numpy().astype(int) - ref8.astype(int)).max() <= 1
+    assert_reference_texels(u8.cpu().numpy(), ref8, host, "rt_epilogue_rgb8_device")
     ds.close()
 
 
@@ -435,14 +439,13 @@ def test_cuda_compat_matches_oracle(scene_name, W, H, spp, depth, seed, rows):
 @pytest.mark.gpu
 def test_cuda_impl_replacement_u8():
     """rt_render_cuda_impl(W, H, out) = cuda_impl(W, H, image_texels): the variant's scene,
-    camera, 48 spp, 32 bounces, gamma 1/2.2 and (uint8)(255 c); +-1 LSB against the oracle's
-    f32 frame through the CPU epilogue (powf rounding)."""
+    camera, 48 spp, 32 bounces, gamma 1/2.2 and (uint8)(255 c): the table's texels of the oracle's
+    compat frame (no reference u8 exists for this variant)."""
     W, H = 96, 54
     got = rt.render_cuda_impl(W, H)
     s, m = rt.cuda_scene_arrays()
     want, _ = O.render_cuda_compat(s, m, rt.Camera.cuda(W, H).c, rt.make_params(W, H, 48, 32, 0, cuda_compat=True))
-    ref8 = O.epilogue_rgb8(want)
-    assert np.abs(got.astype(int) - ref8.astype(int)).max() <= 1
+    assert_texels(got, want, "rt_render_cuda_impl")
 
 
 @pytest.mark.gpu
